@@ -15,7 +15,9 @@ Besides `value` (resident input, columns left in HBM) the line carries
   * `parity_sample`: CRC-32 digests of all 13 columns of one whole segment (>= 1 % of the file) from the resident scan
     against the oracle's, computed inside this run,
   * `cpu_baseline`: the oracle port timed on the host in three thread shapes (1 core; 1 scan + 2 inflate threads, the
-    reference's own shape; all cores), with nproc and the CPU model.
+    reference's own shape; all cores), with nproc and the CPU model,
+  * `dump_outputs` (with `--dump-outputs DIR`): the files written there, a seeded sample of the columns the last timed step
+    returned, so that two builds can be compared output for output on the same input.
 
 N>1 (torchrun): weak scaling, every rank scans its own 10 GB file (own seed), no data-path collective;
 `--strong`: ONE file, every rank stages and scans only its own byte window (dhts_open_path_shard).
@@ -130,6 +132,55 @@ class DigestAcc:
         return out
 
 
+class OutputSample:
+    """--dump-outputs: the arrays dhts_bam_next_batch hands its caller, at a fixed seeded sample of the step's rows (all of them when
+    there are few), as float64 (integer columns, string lengths, the global row numbers) and float32 (string bytes, concatenated in row
+    order) -- at most DUMP_LIMIT bytes of arrays (64 MB with the .npy headers): rows are kept in order while they fit"""
+    FIXED = (("flag", np.uint16), ("tid", np.int32), ("pos", np.int64), ("mapq", np.int32), ("mtid", np.int32), ("pnext", np.int64),
+             ("tlen", np.int64), ("rg_idx", np.int32))
+    STRS = ("qname", "cigar", "seq", "qual", "rg")
+    DUMP_LIMIT = 60_000_000
+
+    def __init__(self, n_rows, n_sample=16384, seed=20240611):
+        self.rows = np.sort(np.random.default_rng(seed).choice(n_rows, min(n_rows, n_sample), replace=False)).astype(np.int64)
+        self.r0 = 0
+        self.cols = {k: [] for k, _ in self.FIXED + (("rg_valid", None),)}
+        self.strs = {k: ([], []) for k in self.STRS}
+
+    def __call__(self, ctx, b):
+        n = int(b.n_rows)
+        idx = self.rows[(self.rows >= self.r0) & (self.rows < self.r0 + n)] - self.r0
+        self.r0 += n
+        if not len(idx):
+            return
+        assert not b.seq_packed
+        for k, dt in self.FIXED:
+            self.cols[k].append(ctx.d2h(getattr(b, k), n, dt)[idx])
+        w = ctx.d2h(b.rg_valid, (n + 63) // 64, np.uint64)
+        self.cols["rg_valid"].append(np.unpackbits(w.view(np.uint8), bitorder="little")[:n][idx])
+        for k in self.STRS:
+            c = getattr(b, k)
+            off = ctx.d2h(c.off, n + 1, np.uint32)[idx]
+            ln = ctx.d2h(c.len, n, np.uint32)[idx]
+            self.strs[k][0].append(ln)
+            self.strs[k][1].extend(ctx.d2h(c.bytes + int(o), int(m), np.uint8) for o, m in zip(off, ln))
+
+    def write(self, out_dir):
+        assert self.r0 >= len(self.rows), (self.r0, len(self.rows))
+        lens = {k: np.concatenate(v[0]).astype(np.int64) for k, v in self.strs.items()}
+        per_row = 8 * (1 + len(self.cols) + len(lens)) + 4 * sum(lens.values())
+        keep = int(np.searchsorted(np.cumsum(per_row), self.DUMP_LIMIT, side="right"))
+        arrays = {"row": self.rows[:keep].astype(np.float64)}
+        arrays.update({k: np.concatenate(v)[:keep].astype(np.float64) for k, v in self.cols.items()})
+        for k, (_, pieces) in self.strs.items():
+            arrays[k + "_len"] = lens[k][:keep].astype(np.float64)
+            arrays[k] = np.concatenate(pieces[:keep] or [np.zeros(0, np.uint8)]).astype(np.float32)
+        os.makedirs(out_dir, exist_ok=True)
+        for k, a in arrays.items():
+            np.save(os.path.join(out_dir, k + ".npy"), a)
+        return {"dir": out_dir, "rows": keep, "of_rows": self.r0, "bytes": int(sum(a.nbytes for a in arrays.values())), "files": sorted(k + ".npy" for k in arrays)}
+
+
 def gpu_digest(ctx, hdr, b0, b1, speculative, max_blocks, acc=None):
     """the oracle's digest layout (oracle/dhts_oracle.c orc_bam_digest) over the rows of blocks [b0, b1) of the resident file"""
     ctx.set_block_range(b0, b1, speculative)
@@ -167,7 +218,11 @@ def main():
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the read_bcf (config 3) and region / overlap-join (config 5) legs behind the timed loop")
     ap.add_argument("--no-parity-sample", action="store_true")
     ap.add_argument("--strong", action="store_true", help="N>1: ONE file, every rank stages and scans its own byte window")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the columns the last step returned (rank 0; a seeded "
+                                                         "sample of 16,384 rows, at most 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -238,7 +293,7 @@ def main():
                 torch.cuda.synchronize()
                 dist.barrier()
 
-        def step():
+        def step(sink=None):
             nb = ctx.bgzf_index()
             if strong:
                 ctx._chk(L.dhts_bam_set_file_shard(ctx.h, rank, world))
@@ -247,6 +302,8 @@ def main():
             rows, out_bytes, first = 0, 0, None
             while True:
                 b = ctx.next_batch(args.max_blocks)
+                if sink is not None:
+                    sink(ctx, b)
                 if b.n_rows and first is None:
                     first = b.first_rec_uoff
                 if b.n_rows:
@@ -277,6 +334,15 @@ def main():
             assert rows == n_records, (rows, n_records)
         ktimes = ctx.kernel_times()
         ctx.set_timing(False)
+        # The columns of a step stay in HBM and the next batch reuses their buffers, and copying them out inside a timed step would
+        # stall the next batch's prefetch: the last step is run once more after the clock has stopped, on the same resident input and
+        # from the same start, and the sample is taken from its batches as they come.
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            last = (rows, nb, out_bytes, dict(spans))
+            sample = OutputSample(rows)
+            assert step(sample) + (dict(spans),) == last, "the replayed step differs from the last timed step"
+            dumped = sample.write(args.dump_outputs)
 
         # ---- multi-rank bookkeeping ----
         if dist is not None:
@@ -513,7 +579,7 @@ def main():
                    "parallelism": f"bgzf-block-range shards x{world}" + (" of one file, byte-window staging" if strong else "")},
         "bgzf_GBps": round(total_file_bytes / sec_per_step / 1e9, 3),
         "roofline": roof, "operator": operator, "parity_sample": parity, "cpu_baseline": cpu, "kernels": kt, "gen_seconds": round(gen_s, 1),
-        "bcf": bcf_leg, "region": region_leg,
+        "bcf": bcf_leg, "region": region_leg, "dump_outputs": dumped,
     }
     if strong:
         line["staged_bytes_total"] = staged_total

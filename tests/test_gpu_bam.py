@@ -846,10 +846,8 @@ def _bed_join_check(data, bed, max_blocks=0, as_path=None):
 @pytest.mark.gpu
 def test_overlap_join_with_the_reference_bed(tmp_path):
     """the reference's test/data/targets.bed x range.bam: read_bed's rows (duckhts.test:241-251) as the join's intervals, checked against the
-    oracle and, where it is built, against the reference's own cgranges"""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import region_oracle as ro
+    oracle and against the reference's own cgranges (its answers stored in tests/golden/overlap_cgranges_cases.json)"""
+    import json
     data, bed = read_golden("range.bam"), read_golden("targets.bed")
     rows, exp, t = _bed_join_check(data, bed)
     assert len(rows) == 4                                  # (the targets lie in the first 20 bases; the reads of range.bam begin near 900: no pairs)
@@ -857,16 +855,8 @@ def test_overlap_join_with_the_reference_bed(tmp_path):
     moved = b"".join(b"\t".join([f[0], b"%d" % (int(f[1]) * 100 + 1000), b"%d" % (int(f[2]) * 100 + 1000)] + f[3:]) + b"\n" for f in (ln.split(b"\t") for ln in bed.splitlines() if ln))
     rows, exp, t = _bed_join_check(data, moved)
     assert len(rows) == 4 and sum(len(x) for x in exp) > 20
-    lib = os.path.join(ROOT, "oracle", "_ref", "libcgranges.so")
-    if os.path.exists(lib):
-        names = [bytes(x).decode() for x in t["ref_names"]]
-        tid, beg, end = ro.bed_join_intervals(rows, t["ref_names"])
-        q = []
-        for i in range(t["n_rows"]):
-            st = int(t["POS"][i]) - 1
-            q.append((names[int(t["tid"][i])], st, ro.endpos(st, int(t["FLAG"][i]), t["CIGAR"][i])))
-        ref = ro.cgranges_overlap(lib, names, tid, beg, end, q)
-        assert all(a.tolist() == b.tolist() for a, b in zip(exp, ref))
+    ref = json.loads(read_golden("overlap_cgranges_cases.json"))["moved_targets_bed"]
+    assert len(exp) == len(ref) and all(a.tolist() == b for a, b in zip(exp, ref))
     # the same BED as a file: plain, and bgzipped by the device (duckhts.test:260-284 read the .bed.gz)
     p = tmp_path / "targets.bed"; p.write_bytes(bed)
     _bed_join_check(data, bed, as_path=str(p))

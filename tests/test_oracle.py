@@ -331,26 +331,20 @@ def test_overlap_join_matches_cgranges_golden():
         assert nm == names[int(t["tid"][i])] and st == int(t["POS"][i]) - 1 and en == ro.endpos(st, int(t["FLAG"][i]), t["CIGAR"][i])
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libcgranges.so")), reason="reference cgranges not built here")
 def test_overlap_join_matches_reference_build_on_random_intervals():
+    """1, 7 and 2000 seeded random intervals; the expected pairs are cr_overlap answers of the reference's own cgranges build
+    (tests/golden/overlap_cgranges_cases.json, generated by make_overlap_golden.py)"""
+    import json
     import sys
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import region_oracle as ro
-    lib = os.path.join(ROOT, "oracle", "_ref", "libcgranges.so")
     t = orc.bam_read(read_golden("range.bam"))
-    names = [bytes(x).decode() for x in t["ref_names"]]
-    rng = np.random.default_rng(11)
-    for n in (1, 7, 2000):
-        tid = rng.integers(0, len(names), n).astype(np.int32)
-        beg = rng.integers(0, 30000, n).astype(np.int64)
-        end = beg + rng.choice([0, 1, 2, 30, 700, 20000], n)
-        q = []
-        for i in range(t["n_rows"]):
-            st = int(t["POS"][i]) - 1
-            q.append((names[int(t["tid"][i])], st, ro.endpos(st, int(t["FLAG"][i]), t["CIGAR"][i])))
-        ref = ro.cgranges_overlap(lib, names, tid, beg, end, q)
-        got = ro.overlap_join(t, tid, beg, end)
-        assert all(a.tolist() == b.tolist() for a, b in zip(got, ref))
+    cases = json.loads(read_golden("overlap_cgranges_cases.json"))["random_intervals"]
+    assert [len(c["tid"]) for c in cases] == [1, 7, 2000]
+    for c in cases:
+        got = ro.overlap_join(t, np.array(c["tid"], np.int32), np.array(c["beg"], np.int64), np.array(c["end"], np.int64))
+        assert len(got) == len(c["overlaps"]) == t["n_rows"]
+        assert all(a.tolist() == b for a, b in zip(got, c["overlaps"]))
 
 
 def test_read_bed_rows_pins_from_the_sql_tests():

@@ -761,8 +761,9 @@ __device__ __forceinline__ void hw_block(uint8_t *smem, int64_t bi, const uint8_
             }
             bool has_eob = true;
             if (!alpha) has_eob = lens[256] != 0;
-            if (!alpha) { if (left < 0 || (left > 0 && nz != 1u) || !has_eob) { status = DHTS_BLK_ERR_INFLATE; break; } }
-            else { if (left < 0 || (left > 0 && nz > 1u)) { status = DHTS_BLK_ERR_INFLATE; break; } }
+            // an incomplete code is legal only as ONE 1-bit codeword, or as an empty distance code (zlib's inftrees.c rule: a single
+            // codeword of 2 bits or more and several codewords short of the Kraft sum are "invalid literal/lengths / distances set")
+            if (left < 0 || (left > 0 && !(nz == 1u && maxlen == 1u) && !(alpha && nz == 0u)) || !has_eob) { status = DHTS_BLK_ERR_INFLATE; break; }
             W_LANES { if (lane < 16) { tb[48 * alpha + lane] = t_lim[lane]; tb[48 * alpha + 16 + lane] = t_first[lane]; tb[48 * alpha + 32 + lane] = t_offs[lane]; } }
             W_SYNC();
             // ranks -> canonical order
@@ -979,7 +980,9 @@ __device__ __forceinline__ void hw_block(uint8_t *smem, int64_t bi, const uint8_
             if (!eob_seen && seg_end >= limit_bits) { status = DHTS_BLK_ERR_INFLATE; break; }     // the payload ended without an end-of-block symbol
             uint64_t ovf;
             W_BALLOT(ovf, (uint32_t)lane < n_ok && (PL(ln).flags & HWF_OVF) != 0u);
-            if (ovf && used_profile) { force_even = true; continue; }       // (an uneven cut overfilled a slice: the segment again with the even cut, nothing has been placed yet)
+            // (an uneven cut overfilled a slice: the segment again with the even cut, nothing has been placed yet -- so the end-of-block
+            // symbol the segment reached is not seen yet either, or the loop would end with the segment's output missing)
+            if (ovf && used_profile) { force_even = true; eob_seen = false; continue; }
             if (ovf) {
                 // ---- a staging slice was too small: lane 0 decodes the whole segment and appends to the block's slot itself ----
                 HWD_CNT(10, 1);
@@ -998,6 +1001,13 @@ __device__ __forceinline__ void hw_block(uint8_t *smem, int64_t bi, const uint8_
                 if (outpos + xch[HX_START * 64] > 65536u) { status = DHTS_BLK_ERR_INFLATE; break; }
                 nlit_tot += xch[HX_A * 64]; ntok_tot += xch[HX_B * 64]; run = xch[HX_C * 64]; outpos += xch[HX_START * 64];
                 p0 = seg_end; first_seg = false;
+                W_SYNC();
+                {   // the run still open behind the segment's last token: "511 literals, no match" tokens, as behind a placed segment
+                    const uint32_t q_end = run / DHTS_TOK_PURE;
+                    if (ntok_tot + q_end + 64u > DHTS_TOK_STRIDE) { status = DHTS_BLK_ERR_INFLATE; break; }
+                    W_LANES { for (uint32_t k = (uint32_t)lane; k < q_end; k += 64u) tok[ntok_tot + k] = DHTS_TOK_PURE << 23; }
+                    ntok_tot += q_end; run -= q_end * DHTS_TOK_PURE;
+                }
                 W_SYNC();
                 HWD_T(t_sf); HWD_ADD(5, t_s2, t_sf);
                 continue;

@@ -301,10 +301,12 @@ __device__ __forceinline__ void huff_decode_body(uint8_t *smem, const uint8_t *_
 #pragma unroll 1
         for (int pass = 0; pass < 2 && status == 0; pass++) {
             if (pass == 1) {
+                // an incomplete code is legal only as ONE 1-bit codeword (Kraft remainder 2^14), or as an empty distance code (zlib's
+                // inftrees.c rule: a single codeword of 2 bits or more and several codewords short of the Kraft sum are errors)
                 int left = build_limits(ll, cntl, lane, bsl);
-                if (left < 0 || (left > 0 && nz_l != 1) || !has_eob) { status = DHTS_BLK_ERR_INFLATE; break; }
+                if (left < 0 || (left > 0 && !(nz_l == 1 && left == (1 << 14))) || !has_eob) { status = DHTS_BLK_ERR_INFLATE; break; }
                 left = build_limits(dl, cntd, lane, bsd);
-                if (left < 0 || (left > 0 && nz_d > 1)) { status = DHTS_BLK_ERR_INFLATE; break; }
+                if (left < 0 || (left > 0 && !(nz_d == 1 && left == (1 << 14)) && nz_d != 0)) { status = DHTS_BLK_ERR_INFLATE; break; }
                 for (uint32_t k = 0; k < hi_rows; k++) lsym_hi[k * A_ST + lane] = 0;
                 br = br0;
             }

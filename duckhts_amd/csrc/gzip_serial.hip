@@ -62,9 +62,12 @@ struct GzBits {
 };
 
 // canonical Huffman code (RFC 1951 3.2.2) of `n` symbols with lengths len[]: count[l], symbols in code order, and a primary table of
-// 2^BITS entries (sym << 4 | len; 0 = longer code or none) indexed by the next bits as they come (LSB first = reversed code)
+// 2^BITS entries (sym << 4 | len; 0 = longer code or none) indexed by the next bits as they come (LSB first = reversed code).
+// false for an over-subscribed code, and for an incomplete one unless it is a single 1-bit codeword and `one_bit_ok` (zlib's inftrees.c:
+// the code-length code must be complete; a literal/length or distance code may be one 1-bit codeword).  The fixed codes are built
+// unchecked (30 distance codes of 5 bits are incomplete by design).
 template <int BITS>
-__device__ __forceinline__ bool gz_build(const uint8_t *len, int n, uint16_t *count, uint16_t *symbol, uint16_t *fast) {
+__device__ __forceinline__ bool gz_build(const uint8_t *len, int n, uint16_t *count, uint16_t *symbol, uint16_t *fast, bool one_bit_ok) {
     for (int l = 0; l <= 15; l++) count[l] = 0;
     for (int s = 0; s < n; s++) count[len[s]]++;
     for (int i = 0; i < (1 << BITS); i++) fast[i] = 0;
@@ -83,7 +86,8 @@ __device__ __forceinline__ bool gz_build(const uint8_t *len, int n, uint16_t *co
         }
         code <<= 1;
     }
-    return true;                                      // (an incomplete code is let through, as zlib lets a single-code distance tree through; a code word without a symbol fails when it is met)
+    if (left > 0 && !(one_bit_ok && count[1] == 1 && n - count[0] == 1)) return false;              // incomplete
+    return true;                                      // (the one 1-bit codeword's sibling has no symbol: it fails when it is met)
 }
 template <int BITS>
 __device__ __forceinline__ int gz_decode(GzBits &b, const uint16_t *count, const uint16_t *symbol, const uint16_t *fast) {
@@ -214,16 +218,16 @@ gz_inflate_serial(const uint8_t *__restrict__ in, unsigned long long in_len, uin
                     for (int s = 144; s < 256; s++) lens[s] = 9;
                     for (int s = 256; s < 280; s++) lens[s] = 7;
                     for (int s = 280; s < 288; s++) lens[s] = 8;
-                    gz_build<GZ_LL_BITS>(lens, 288, ll_count, ll_sym, ll_fast);
+                    gz_build<GZ_LL_BITS>(lens, 288, ll_count, ll_sym, ll_fast, true);
                     for (int s = 0; s < 30; s++) lens[s] = 5;
-                    gz_build<GZ_D_BITS>(lens, 30, d_count, d_sym, d_fast);
+                    gz_build<GZ_D_BITS>(lens, 30, d_count, d_sym, d_fast, true);
                 } else {                                                                  // dynamic codes
                     const uint32_t hlit = b.take(5) + 257, hdist = b.take(5) + 1, hclen = b.take(4) + 4;
                     if (hlit > 286 || hdist > 30) { bad = true; break; }
                     uint8_t cl[19]; for (int k = 0; k < 19; k++) cl[k] = 0;
                     for (uint32_t k = 0; k < hclen; k++) cl[gz_clorder[k]] = (uint8_t)b.take(3);
                     if (b.past_end()) { trunc = true; break; }
-                    if (!gz_build<7>(cl, 19, cl_count, cl_sym, cl_fast)) { bad = true; break; }
+                    if (!gz_build<7>(cl, 19, cl_count, cl_sym, cl_fast, false)) { bad = true; break; }
                     uint32_t k = 0;
                     while (k < hlit + hdist) {
                         const int s = gz_decode<7>(b, cl_count, cl_sym, cl_fast);
@@ -242,9 +246,9 @@ gz_inflate_serial(const uint8_t *__restrict__ in, unsigned long long in_len, uin
                     if (bad) break;
                     if (b.past_end()) { trunc = true; break; }
                     if (lens[256] == 0) { bad = true; break; }                            // no end-of-block code
-                    if (!gz_build<GZ_LL_BITS>(lens, (int)hlit, ll_count, ll_sym, ll_fast)) { bad = true; break; }
+                    if (!gz_build<GZ_LL_BITS>(lens, (int)hlit, ll_count, ll_sym, ll_fast, true)) { bad = true; break; }
                     uint8_t dl[32]; for (uint32_t i = 0; i < hdist; i++) dl[i] = lens[hlit + i];
-                    if (!gz_build<GZ_D_BITS>(dl, (int)hdist, d_count, d_sym, d_fast)) { bad = true; break; }
+                    if (!gz_build<GZ_D_BITS>(dl, (int)hdist, d_count, d_sym, d_fast, true)) { bad = true; break; }
                 }
                 // ---- symbols
                 for (;;) {

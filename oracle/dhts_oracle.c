@@ -175,10 +175,13 @@ int orc_inflate_raw(const uint8_t *src, size_t slen, uint8_t *dst, size_t dcap, 
                 }
             }
             if (lens[256] == 0) return -1;              /* no end-of-block code */
+            /* an incomplete code is legal only as ONE 1-bit codeword (zlib inftrees.c; libdeflate agrees): a single codeword of
+             * 2 bits or more, or several codewords short of the Kraft sum, are errors ("invalid literal/lengths set" /
+             * "invalid distances set").  An empty distance code (huff_build 0) is legal: a match in that block fails. */
             int r = huff_build(&lc, lens, (int)nlen);
-            if (r < 0 || (r > 0 && nlen - lc.count[0] != 1)) return -1;
+            if (r < 0 || (r > 0 && !(nlen - lc.count[0] == 1 && lc.count[1] == 1))) return -1;
             r = huff_build(&dc, lens + nlen, (int)ndist);
-            if (r < 0 || (r > 0 && ndist - dc.count[0] != 1)) return -1;
+            if (r < 0 || (r > 0 && !(ndist - dc.count[0] == 1 && dc.count[1] == 1))) return -1;
             r = inf_codes(&s, &lc, &dc);
             if (r < 0) return r;
         } else return -1;

@@ -4,7 +4,9 @@
 //   (1) replayed and checked against the block's CRC32 / ISIZE trailer, and
 //   (2) compared word for word with the output of the lane-per-block kernel (phase A of bgzf_inflate.hip, host build of the same
 //       kernel text: tools/hostsim/_gen/phaseA_extract.inc), including the error status of damaged blocks.
-// usage: sim_wave [--flip N seed] file...
+// usage: sim_wave [--per-block] [--flip N seed] file...
+//   --per-block: one line per BGZF block (both kernels' status, the replay's verdict on the wave kernel's output: 0 replays to the
+//   trailer, 1 CRC32 / ISIZE differ, 2 a distance reaches in front of the block); failing blocks are then expected, as with --flip
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +48,7 @@ static int replay(const std::vector<uint8_t> &d, uint64_t coff, uint32_t clen, c
         for (uint32_t k = 0; k < run; k++) out.push_back(L[lp++]);
         if (run != DHTS_TOK_PURE) {
             const uint32_t len = ((t >> 15) & 255u) + 3, dist = (t & 0x7fffu) + 1;
-            if (dist > out.size()) return 1;
+            if (dist > out.size()) return 2;
             for (uint32_t k = 0; k < len; k++) out.push_back(out[out.size() - dist]);
         }
     }
@@ -60,8 +62,10 @@ static int replay(const std::vector<uint8_t> &d, uint64_t coff, uint32_t clen, c
 
 int main(int argc, char **argv) {
     for (uint32_t k = 0; k < 256; k++) { uint32_t c = k; for (int j = 0; j < 8; j++) c = (c & 1u) ? (0xEDB88320u ^ (c >> 1)) : (c >> 1); crct[k] = c; }
-    int flips = 0; unsigned seed = 1; int a = 1;
-    if (argc > 3 && !strcmp(argv[1], "--flip")) { flips = atoi(argv[2]); seed = (unsigned)atoi(argv[3]); a = 4; }
+    int flips = 0; unsigned seed = 1; int a = 1; bool per_block = false;
+    if (argc > 1 && !strcmp(argv[1], "--per-block")) { per_block = true; a = 2; }
+    if (argc > a + 2 && !strcmp(argv[a], "--flip")) { flips = atoi(argv[a + 1]); seed = (unsigned)atoi(argv[a + 2]); a += 3; }
+    const bool damaged = flips || per_block;        // blocks that fail are expected: the two kernels must fail the same ones
     int rc = 0;
     for (; a < argc; a++) {
         FILE *f = fopen(argv[a], "rb"); if (!f) { fprintf(stderr, "cannot open %s\n", argv[a]); return 2; }
@@ -97,7 +101,11 @@ int main(int argc, char **argv) {
         int bad = 0, mism = 0, differ = 0;
         for (int64_t b = 0; b < nb; b++) {
             const InflateMeta &m1 = meta[b], &m2 = meta2[b];
-            if (m1.status != 0 && m2.status == 0 && flips) {
+            if (per_block) {
+                const int rp = m2.status ? -1 : replay(d, coff[b], clen[b], lit2.data() + (size_t)b * DHTS_LIT_STRIDE, tok2.data() + (size_t)b * DHTS_TOK_STRIDE, m2);
+                printf("%s: block %lld lane %d wave %d replay %d\n", argv[a], (long long)b, m1.status, m2.status, rp);
+            }
+            if (m1.status != 0 && m2.status == 0 && damaged) {
                 // the wave kernel leaves the distance-beyond-the-output test to bgzf_lz_resolve: the replay (which makes that test) must fail
                 if (!replay(d, coff[b], clen[b], lit2.data() + (size_t)b * DHTS_LIT_STRIDE, tok2.data() + (size_t)b * DHTS_TOK_STRIDE, m2)) { differ++; fprintf(stderr, "block %lld: lane kernel rejects it, the wave kernel's output replays cleanly\n", (long long)b); }
                 else bad++;
@@ -115,10 +123,10 @@ int main(int argc, char **argv) {
                     for (uint32_t i = 0; i < m1.nlit && i < m2.nlit; i++) if (L1[i] != L2[i]) { fprintf(stderr, "  first literal difference at %u\n", i); break; }
                 }
             }
-            if (!flips && replay(d, coff[b], clen[b], L2, T2, m2)) mism++;
+            if (!damaged && replay(d, coff[b], clen[b], L2, T2, m2)) mism++;
         }
         printf("%s: blocks %lld failed %d mismatching %d differing-from-lane-kernel %d (LDS=%d)\n", argv[a], (long long)nb, bad, mism, differ, (int)HW_LDS_BYTES);
-        if (mism || differ || (bad && !flips)) rc = 1;
+        if (mism || differ || (bad && !damaged)) rc = 1;
     }
 #ifdef HW_STATS
     printf("segments %llu; pass-1 rounds executed (by round index):", g_hw_stat_seg);

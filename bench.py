@@ -8,16 +8,21 @@ compressed bytes already in HBM when the timed region starts and the columns lef
 Workload at N=1: BASELINE.json configs[1], "read_bam full scan of a synthetic 10 GB BGZF BAM on 1xMI355X".
 The file is generated in full: `reps` segments of `--unique-records` records each, record i of the whole file drawn
 from (seed, i) -- every segment is different data, coordinate-sorted over the whole file.
-It is written to a scratch file, staged with dhts_open_path, and removed at the end.
+The segments are made on the device (tools/synth_gpu.hip: the bytes tools/synth_bam.c writes with zlib level 6, in a
+fraction of the host's time).  A plain run stages the file from host memory; with `--full`, or N>1, it is written to a
+scratch file, staged with dhts_open_path, and removed at the end.
 
-Besides `value` (resident input, columns left in HBM) the line carries
+A plain run does only what the headline needs: it makes the input, warms up, times the steps, writes `--dump-outputs`
+and prints the line: `value` (resident input, columns left in HBM), `ms_per_step`, the per-kernel times of the timed
+steps and the roofline made from them.  `--full` adds the legs that take runs of their own:
   * `operator`: the same file through the DuckDB table function (mini host): pread + H2D + scan + D2H + DataChunk fill,
-  * `parity_sample`: CRC-32 digests of all 13 columns of one whole segment (>= 1 % of the file) from the resident scan
-    against the oracle's, computed inside this run,
+  * `parity_sample`: CRC-32 digests of all 13 columns of every segment of the file from the resident scan against the
+    oracle's, computed inside this run,
   * `cpu_baseline`: the oracle port timed on the host in three thread shapes (1 core; 1 scan + 2 inflate threads, the
     reference's own shape; all cores), with nproc and the CPU model,
-  * `dump_outputs` (with `--dump-outputs DIR`): the files written there, a seeded sample of the columns the last timed step
-    returned, so that two builds can be compared output for output on the same input.
+  * `bcf`, `region`: configs 3 and 5 by tools/bench_bcf.py and tools/bench_overlap.py.
+Without `--full` these keys are null.  `dump_outputs` (with `--dump-outputs DIR`): the files written there, a seeded
+sample of the columns the last timed step returned, so that two builds can be compared output for output on the same input.
 
 N>1 (torchrun): weak scaling, every rank scans its own 10 GB file (own seed), no data-path collective;
 `--strong`: ONE file, every rank stages and scans only its own byte window (dhts_open_path_shard).
@@ -50,20 +55,21 @@ def scratch_dir(need_bytes):
     return tempfile.gettempdir()
 
 
-def generate_file(path, synth, seed, n_u, reps, threads):
-    """the whole file, segment by segment; returns (per-segment byte sizes, header bytes, inflated bytes)"""
+def generate_file(path, synth, seed, n_u, reps, threads, device):
+    """the whole file: the header block on the host, the segments on the device; returns (the file's bytes, per-segment byte sizes,
+    header bytes, inflated bytes), and writes the bytes to path too unless path is None"""
     total_n = n_u * reps
-    sizes, raw = [], 0
-    buf = np.empty(n_u * 260 + (1 << 20), np.uint8)
-    with open(path, "wb") as f:
-        head, _ = synth.bam_segment(0, seed=seed, total_n=total_n, with_header=True, with_eof=False, threads=threads)
-        f.write(head.tobytes())
-        for k in range(reps):
-            seg, st = synth.bam_segment(n_u, seed=seed, total_n=total_n, rec0=k * n_u, with_header=False, with_eof=False, threads=threads, out=buf)
-            seg.tofile(f)
-            sizes.append(int(seg.nbytes)); raw += st["raw_bytes"]
-        f.write(EOF_BLOCK)
-    return sizes, int(head.nbytes), raw
+    head, _ = synth.bam_segment(0, seed=seed, total_n=total_n, with_header=True, with_eof=False, threads=threads)
+    hl = int(head.nbytes)
+    buf = np.empty(hl + n_u * reps * 260 + (1 << 20) + len(EOF_BLOCK), np.uint8)
+    buf[:hl] = head
+    segs, sizes, raw = synth.bam_segments_gpu(n_u, 0, reps, seed=seed, total_n=total_n, device=device, out=buf[hl:-len(EOF_BLOCK)])
+    end = hl + segs.nbytes
+    buf[end:end + len(EOF_BLOCK)] = np.frombuffer(EOF_BLOCK, np.uint8)
+    data = buf[:end + len(EOF_BLOCK)]
+    if path is not None:
+        data.tofile(path)
+    return data, sizes, hl, raw
 
 
 def crc_str(off, ln, data):
@@ -213,6 +219,8 @@ def main():
     ap.add_argument("--unique-records", type=int, default=4_000_000, help="records per generated segment")
     ap.add_argument("--target-gb", type=float, default=10.0, help="compressed size of the file per GPU (GB)")
     ap.add_argument("--max-blocks", type=int, default=24576, help="BGZF blocks per batch (24,576 is the largest that keeps in-batch offsets below 2^32)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the parity check over the whole file, the CPU baseline, "
+                                                         "the operator leg and the read_bcf / region legs (the --no-* options below leave some out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-operator", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the read_bcf (config 3) and region / overlap-join (config 5) legs behind the timed loop")
@@ -258,10 +266,12 @@ def main():
     ncpu, cpu_model = cpu_info()
     gen_threads = max(1, min(32, ncpu // (1 if strong else min(world, max(1, ncpu)))))
     sdir = scratch_dir(args.target_gb * 1e9 * (1 if strong else 1))
-    path = os.path.join(sdir, f"dhts_bench_{os.getpid() if not strong else 'strong'}_{rank if not strong else 0}.bam")
-    sizes = hdr_bytes = raw_bytes = None
+    # the legs of --full and the N>1 staging read the input as a file; a plain run stages it from host memory
+    to_file = args.full or world > 1
+    path = os.path.join(sdir, f"dhts_bench_{os.getpid() if not strong else 'strong'}_{rank if not strong else 0}.bam") if to_file else None
+    data = sizes = hdr_bytes = raw_bytes = None
     if not strong or rank == 0:
-        sizes, hdr_bytes, raw_bytes = generate_file(path, synth, seed, n_u, reps, gen_threads)
+        data, sizes, hdr_bytes, raw_bytes = generate_file(path, synth, seed, n_u, reps, gen_threads, local_rank if world > 1 else 0)
     if strong:
         import torch
         meta = [sizes, hdr_bytes, raw_bytes, path]
@@ -282,7 +292,8 @@ def main():
             L.dhts_resident_bytes.restype = C.c_uint64
             ctx._chk(L.dhts_open_path_shard(ctx.h, os.fsencode(path), rank, world, hdr_bytes))
         else:
-            ctx.open(path)
+            ctx.open(path if to_file else data)
+        data = None
         staged_bytes = int(L.dhts_resident_bytes(ctx.h))
         spans = {}
 
@@ -446,7 +457,7 @@ def main():
         parity, cpu = None, None
         k_s = reps // 2
         seg_off = hdr_bytes + sum(sizes[:k_s])
-        if (not args.no_parity_sample or not args.no_cpu_baseline) and world == 1:
+        if args.full and (not args.no_parity_sample or not args.no_cpu_baseline) and world == 1:
             import orc
             with open(path, "rb") as f:
                 head_b = f.read(hdr_bytes)
@@ -511,7 +522,7 @@ def main():
 
     # ---- the operator: the same file through the DuckDB table function (pread + H2D + scan + D2H + DataChunk fill) ----
     operator = None
-    if not args.no_operator and world == 1:
+    if args.full and not args.no_operator and world == 1:
         host = os.path.join(ROOT, "tests", "minihost", "minihost")
         thr = max(1, min(16, ncpu - 2))                       # (16 = one GPU's share of the box's cores; profiles/r04/fill_threads_r04.jsonl: 132 M records/s with 8 fill threads, 182 M with 16 and 32)
         qual_mode = {}
@@ -556,13 +567,14 @@ def main():
         except Exception as e:                                   # (a bench line without these legs is still a bench line)
             return {"error": repr(e)[:300]}
     bcf_leg = region_leg = None
-    if not args.no_extra_configs and world == 1:
+    if args.full and not args.no_extra_configs and world == 1:
         bcf_leg = tool_lines("bench_bcf.py", ["--steps", "3", "--warmup", "1", "--cpu-sample-records", "20000"], 400)
         region_leg = tool_lines("bench_overlap.py", ["--steps", "3", "--warmup", "1", "--target-gb", "1.0", "--indexed-records", "4000000",
                                                      "--queries", "region,overlap,indexed1,indexed10k"], 500)
 
     try:
-        os.unlink(path)
+        if path is not None:
+            os.unlink(path)
     except OSError:
         pass
     if dist is not None:

@@ -6,7 +6,7 @@ grep -q passed "$out/tests.txt" || exit 1
 grep -q failed "$out/tests.txt" && exit 1
 DHTS_LIB=build/lib_bdiag.so timeout -k 10 300 python tools/dbg/diag.py > "$out/diag.txt" 2>&1; head -10 "$out/diag.txt"
 if [ -n "${PMC:-}" ]; then timeout -k 10 500 bash tools/dbg/pmc_lz.sh "$out/pmc" > "$out/pmc.txt" 2>&1; tail -2 "$out/pmc.txt"; fi
-python bench.py --steps 5 --warmup 2 --no-extra-configs --no-operator --no-cpu-baseline > "$out/bench.json" 2> "$out/bench.err"; python - "$out/bench.json" <<'PY'
+python bench.py --steps 5 --warmup 2 --full --no-extra-configs --no-operator --no-cpu-baseline > "$out/bench.json" 2> "$out/bench.err"; python - "$out/bench.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 print(d["value"], d["ms_per_step"], d["roofline"]["frac"], d["roofline"]["path_frac"], d["parity_sample"]["equal"])

@@ -600,6 +600,7 @@ static_assert(BR_R >= BR_FLUSH + BR_SPAN + 265u, "far sources must always be flu
 #define B_NULLTOK 0xffffffffu
 // knock-out experiments (tools/dbg/time_lz.py; the output is wrong on purpose): -DB_EXP_NOCRC, -DB_EXP_NOLIT, -DB_EXP_NOFAR, -DB_EXP_NOROUNDS,
 // -DB_EXP_NOREPLAY, -DB_EXP_NOSTORE leave out one part of the kernel each, so that its cost can be read off the launch time
+// (NOROUNDS leaves out the windowed far copies too: round 1 makes them; NOFAR turns far matches into near ones and so removes their loads)
 #ifdef B_EXP_NOSTORE
 #define B_EXP_STORE(p_, v_) do { asm volatile("" :: "v"((v_).x), "v"((v_).y), "v"((v_).z), "v"((v_).w)); } while (0)
 #else
@@ -614,7 +615,7 @@ static_assert(BR_R >= BR_FLUSH + BR_SPAN + 265u, "far sources must always be flu
 #define B_SEQ_T 6u                        /* pending matches at or below which the rounds of a batch give way to the in-order replay */
 #endif
 #ifdef DHTS_DIAG
-__device__ unsigned long long g_diag[8];   // batches, rounds, easy, hard, lit_iters, long_lit
+__device__ unsigned long long g_diag[8];   // batches, rounds, easy, hard, overlapping (8 <= dist < len <= 32), far, matches, oversized
 #define DIAG_ADD(i, v) do { dcnt[i] += (unsigned long long)(v); } while (0)
 #define DIAG_T(var) unsigned long long var = clock64()
 __device__ unsigned long long g_diagt[8];
@@ -642,6 +643,13 @@ __device__ __forceinline__ void win_st_n(uint8_t *win, uint32_t p, uint64_t v, u
     const uint32_t i = ridx(p), m = n < 8 ? n : 8;
     if (i + m <= BR_R) lds_st_n(win + i, v, n);
     else for (uint32_t k = 0; k < m; k++) win[ridx(p + k)] = (uint8_t)(v >> (8 * k));
+}
+// k mod d for k <= 64 and 0 < d < 2^15, inv = 1 / d from v_rcp_f32: the truncated quotient is off by one at most
+__device__ __forceinline__ uint32_t lz_small_mod(uint32_t k, uint32_t d, float inv) {
+    const uint32_t q = (uint32_t)((float)k * inv);
+    int32_t r = (int32_t)(k - __umul24(q, d));
+    if (r < 0) r += (int32_t)d; else if (r >= (int32_t)d) r -= (int32_t)d;
+    return (uint32_t)r;
 }
 // x^(8*nbytes) mod P (reflected)
 __device__ __forceinline__ uint32_t crc_xpow8(uint32_t nbytes) {
@@ -783,16 +791,29 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
             // the block's own output is always readable 40 bytes past a far source: ms + 40 < bend)
             const uint32_t md = dst + lrun, ms = md - mdist, mspan = mlen < mdist ? mlen : mdist;
             const uint32_t bend = outpos + tot_adv, rlo = bend > BR_R ? bend - BR_R : 0u;
+            const uint32_t rs = ridx(ms), rd = ridx(md);
 #ifdef B_EXP_NOFAR
             const bool farm = false;
 #else
             const bool farm = mlen > 0 && ms < rlo;
 #endif
+            // A match of 3..32 bytes that wraps in the ring neither at its source nor at its destination, and whose source does not
+            // overlap its destination (or is one repeated byte), is copied lane-parallel in the rounds below through windows that
+            // overlap each other instead of a chain of ever smaller stores, as a short memcpy does: 8..32 bytes as four 8-byte windows
+            // at min(8j, mlen - 8), 4..7 bytes as two 4-byte windows at 0 and mlen - 4, 3 bytes as 2 + 1.  Every window lies inside
+            // the match (the bytes behind it are literals already in place), and bytes covered twice get the same value.
+            const bool wcopy = mlen > 0 && mlen <= 32u && rd + mlen <= BR_R && (farm || (rs + mlen <= BR_R && (mdist >= mlen || mdist == 1u)));
+            const bool farbig = farm && !wcopy;                 // long or wrapping far match: placed on its own, before the rounds
+            const uint32_t wk1 = mlen < 16u ? mlen - 8u : 8u, wk2 = mlen < 24u ? mlen - 8u : 16u, wk3 = mlen < 32u ? mlen - 8u : 24u;
             uint64_t fv0 = 0, fv1 = 0, fv2 = 0, fv3 = 0;
             if (farm) {
+                // a windowed far copy of 8+ bytes fetches its four windows; every other far match its first 32 bytes
                 const uint8_t *g = dstp + ms;
-                uint64_t a[2]; __builtin_memcpy(a, g, 16); fv0 = a[0]; fv1 = a[1];
-                if (mlen > 16u) { uint64_t b[2]; __builtin_memcpy(b, g + 16, 16); fv2 = b[0]; fv3 = b[1]; }
+                const bool w8 = wcopy && mlen >= 8u;
+                __builtin_memcpy(&fv0, g, 8);
+                __builtin_memcpy(&fv1, g + (w8 ? wk1 : 8u), 8);
+                __builtin_memcpy(&fv2, g + (w8 ? wk2 : 16u), 8);
+                __builtin_memcpy(&fv3, g + (w8 ? wk3 : 24u), 8);
             }
             // ---- literals ----
             while (litpos + tot_lit > stage_hi && stage_hi < m.nlit) { STAGE_ISSUE(); STAGE_COMMIT(); }
@@ -800,7 +821,6 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
             // the first 8 bytes of every run lane-parallel: one (usually unaligned) 64-bit ring read, then an exact-length store; the few
             // runs that are longer (3 % on BAM data) are finished one at a time by the whole wave, a byte per lane -- a second and third
             // lane-parallel step would cost the whole wave a full iteration each for one or two lanes' bytes
-            DIAG_ADD(4, 1);
 #ifdef B_EXP_NOLIT
             if (false) {
 #else
@@ -832,18 +852,8 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
             // pending match always sees an empty set, so every round makes progress; cell granularity only delays.
             uint32_t sh = 4; while ((tot_adv >> sh) > 63u) sh++;
             uint64_t dmask = 0, smask = 0;
-            if (farm) {
-                const uint32_t rdm = ridx(md);
-                if (mlen <= 32u && rdm + 40u <= BR_R) {
-                    // the usual case: whole 8-byte pieces out of the registers, then the exact tail
-                    uint8_t *dp = win + rdm;
-                    const uint32_t full = mlen >> 3, tail = mlen & 7u;
-                    if (full > 0u) __builtin_memcpy(dp, &fv0, 8);
-                    if (full > 1u) __builtin_memcpy(dp + 8, &fv1, 8);
-                    if (full > 2u) __builtin_memcpy(dp + 16, &fv2, 8);
-                    if (full > 3u) __builtin_memcpy(dp + 24, &fv3, 8);
-                    if (tail) { const uint64_t vt = full == 0u ? fv0 : full == 1u ? fv1 : full == 2u ? fv2 : fv3; lds_st_n(dp + 8u * full, vt, tail); }
-                } else {
+            if (__ballot(farbig) != 0ull) {
+                if (farbig) {
                     const uint8_t *g = dstp + ms;
                     win_st_n(win, md, fv0, mlen);
                     if (mlen > 8u) win_st_n(win, md + 8, fv1, mlen - 8u);
@@ -851,6 +861,7 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
                     if (mlen > 24u) win_st_n(win, md + 24, fv3, mlen - 24u);
                     for (uint32_t c = 32; c < mlen; c += 8) { uint64_t v; __builtin_memcpy(&v, g + c, 8); win_st_n(win, md + c, v, mlen - c); }
                 }
+                LZ_SYNC();                               // these copies are in the ring before anybody reads them
             }
             if (mlen > 0) {
                 const uint32_t lo = (md - outpos) >> sh, hi = (md - outpos + mlen - 1) >> sh;
@@ -860,19 +871,26 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
                     smask = ((~0ull) >> (63u - shi)) & ((~0ull) << slo);
                 }
             }
+            // a windowed far match is pending like a near one and always ready (its bytes are in fv*, smask = 0): it is copied by the
+            // first round, and its destination is owed to the later lanes of that round like any other
 #ifdef B_EXP_NOROUNDS
             uint64_t P = 0;
 #else
-            uint64_t P = __ballot(mlen > 0 && !farm);
+            uint64_t P = __ballot(mlen > 0 && !farbig);
 #endif
             DIAG_T(t_b2);
             DIAG_TADD(7, t_b, t_b2);
-            LZ_SYNC();                                   // far copies are in the ring before anybody reads them
-            DIAG_ADD(6, __popcll(P)); DIAG_ADD(5, __popcll(__ballot(farm)));
+            DIAG_ADD(6, __popcll(__ballot(mlen > 0 && !farm))); DIAG_ADD(5, __popcll(__ballot(farm)));
+            DIAG_ADD(4, __popcll(__ballot(mlen > 0 && !farm && mlen <= 32u && mdist >= 8u && mdist < mlen)));
             // Parallel rounds while they pay: on BAM data 84 % of a batch's matches are ready in the first round, 11 % in the second,
             // and the dependency chains of the rest would cost a full round for one or two copies each.  As soon as B_SEQ_T or fewer
             // matches are pending (or a round found nothing it could copy) the rest is replayed one match at a time in stream order
             // -- always ready by construction, no readiness test -- by the whole wave (one byte per lane).
+            // One copy body serves the three kinds of ready lane, which differ only in where a window's value comes from: the ring
+            // (near), the replicated source byte (dist 1), or fv* (far).  All loads of a lane come before its stores, so overlapping
+            // sources (1 < dist < len), like matches that wrap in the ring and long ones, stay pending for the sequential replay.
+            const uint8_t *sp = win + (farm ? 0u : rs); uint8_t *dp = win + rd;      // (a far lane's loads are discarded: any address)
+            const bool d1 = mdist == 1u;
             bool more = P != 0ull;
             while (more) {
                 DIAG_ADD(1, 1);
@@ -880,24 +898,27 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
                 const uint64_t e = pending ? dmask : 0ull;
                 const uint32_t el = wave_shr1(wave_incl_scan_or((uint32_t)e)), eh = wave_shr1(wave_incl_scan_or((uint32_t)(e >> 32)));
                 const uint64_t owed = ((uint64_t)eh << 32) | el;                   // exclusive prefix-OR over earlier lanes
-                const bool ready = pending && ((smask & owed) == 0ull);
-                // lane-parallel, 8 bytes per step with unaligned 64-bit LDS accesses: byte runs (dist 1), non-overlapping copies, and
-                // overlapping copies with dist >= 8 (a chunk never reads what it writes; chunks go in order).  Matches whose source or
-                // destination would wrap in the ring, and long ones, stay pending for the sequential replay.
-                const uint32_t rs = ridx(ms), rd = ridx(md);
-                const bool easy = ready && (mlen <= 32u) && (mdist >= 8u || mdist >= mlen || mdist == 1u) && (rs + 40u <= BR_R) && (rd + 40u <= BR_R);
+                const bool easy = pending && ((smask & owed) == 0ull) && wcopy;
                 if (easy) {
-                    const uint8_t *sp = win + rs; uint8_t *dp = win + rd;
-                    const uint32_t full = mlen >> 3, tail = mlen & 7u;
-                    if (mdist == 1u) {
-                        const uint64_t rep = (uint64_t)sp[0] * 0x0101010101010101ull;
-#pragma unroll
-                        for (uint32_t c = 0; c < 4; c++) if (c < full) __builtin_memcpy(dp + 8 * c, &rep, 8);
-                        if (tail) lds_st_n(dp + 8 * full, rep, tail);
+                    if (mlen >= 8u) {
+                        uint64_t v0 = lds_ld64(sp), v1 = lds_ld64(sp + wk1), v2 = lds_ld64(sp + wk2), v3 = lds_ld64(sp + wk3);
+                        const uint32_t r4 = __builtin_amdgcn_perm((uint32_t)v0, (uint32_t)v0, 0u);
+                        const uint64_t rep = ((uint64_t)r4 << 32) | r4;
+                        v0 = farm ? fv0 : d1 ? rep : v0; v1 = farm ? fv1 : d1 ? rep : v1;
+                        v2 = farm ? fv2 : d1 ? rep : v2; v3 = farm ? fv3 : d1 ? rep : v3;
+                        __builtin_memcpy(dp, &v0, 8); __builtin_memcpy(dp + wk1, &v1, 8);
+                        __builtin_memcpy(dp + wk2, &v2, 8); __builtin_memcpy(dp + wk3, &v3, 8);
+                    } else if (mlen >= 4u) {
+                        const uint32_t k = mlen - 4u;
+                        uint32_t a, b; __builtin_memcpy(&a, sp, 4); __builtin_memcpy(&b, sp + k, 4);
+                        const uint32_t r4 = __builtin_amdgcn_perm(a, a, 0u);
+                        a = farm ? (uint32_t)fv0 : d1 ? r4 : a; b = farm ? (uint32_t)(fv0 >> (8u * k)) : d1 ? r4 : b;
+                        __builtin_memcpy(dp, &a, 4); __builtin_memcpy(dp + k, &b, 4);
                     } else {
-#pragma unroll
-                        for (uint32_t c = 0; c < 4; c++) if (c < full) { const uint64_t v = lds_ld64(sp + 8 * c); __builtin_memcpy(dp + 8 * c, &v, 8); }
-                        if (tail) lds_st_n(dp + 8 * full, lds_ld64(sp + 8 * full), tail);
+                        uint16_t a; __builtin_memcpy(&a, sp, 2); uint8_t b = sp[2];
+                        const uint32_t r4 = __builtin_amdgcn_perm((uint32_t)a, (uint32_t)a, 0u);
+                        a = farm ? (uint16_t)fv0 : d1 ? (uint16_t)r4 : a; b = farm ? (uint8_t)(fv0 >> 16) : d1 ? (uint8_t)r4 : b;
+                        __builtin_memcpy(dp, &a, 2); dp[2] = b;
                     }
                 }
                 const uint64_t E = __ballot(easy);
@@ -916,7 +937,13 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
                 const uint32_t src0 = d0 - di;
                 if (l0 <= di) { for (uint32_t k = lane; k < l0; k += 64) win[ridx(d0 + k)] = win[ridx(src0 + k)]; }
                 else if (di == 1u) { const uint8_t v = win[ridx(src0)]; for (uint32_t k = lane; k < l0; k += 64) win[ridx(d0 + k)] = v; }
-                else { for (uint32_t k = lane; k < l0; k += 64) win[ridx(d0 + k)] = win[ridx(src0 + (k % di))]; }
+                else {
+                    // overlapping: byte k comes from src0 + k mod di; one modulo in front of the loop, then r advances by 64 mod di
+                    const float inv = __builtin_amdgcn_rcpf((float)di);
+                    uint32_t r = lz_small_mod((uint32_t)lane, di, inv);
+                    const uint32_t step = lz_small_mod(64u, di, inv);
+                    for (uint32_t k = lane; k < l0; k += 64) { win[ridx(d0 + k)] = win[ridx(src0 + r)]; r += step; if (r >= di) r -= di; }
+                }
             }
             LZ_SYNC();
             DIAG_T(t_c);

@@ -12,7 +12,7 @@ d = (C.c_ulonglong*24)()
 if not hasattr(ctx.L, 'dhts_debug_diag'):
     print(rows, nb, '(no -DDHTS_DIAG build: counters only)'); sys.exit(0)
 ctx.L.dhts_debug_diag(C.c_void_p(ctx.h), d)
-names=['batches','rounds','easy','hard','lit_iters','far','matches','oversized']
+names=['batches','rounds','easy','hard','overlap_8_32','far','matches','oversized']
 print(rows, nb, {n:int(v) for n,v in zip(names,d)})
 
 t=[int(x) for x in d[8:16]]

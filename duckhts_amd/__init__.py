@@ -109,6 +109,8 @@ def lib():
         L.dhts_bam_is_text.argtypes = [C.c_void_p]
         L.dhts_debug_sam_records.restype = C.c_int64
         L.dhts_debug_sam_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64)]
+        L.dhts_debug_fastq_records.restype = C.c_int64
+        L.dhts_debug_fastq_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64)]
         L.dhts_bam_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dhts_bam_set_block_range.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int]
         L.dhts_shard_cut.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -246,7 +248,7 @@ class Context:
         return self.header()
 
     def bam_is_text(self):
-        """after bam_open: 0 BAM, 1 bgzipped SAM text, 2 plain SAM text (uncompressed or plain gzip)"""
+        """after bam_open: 0 BAM, 1 bgzipped SAM text, 2 plain SAM text (uncompressed or plain gzip), 3 / 4 FASTQ and 5 / 6 FASTA likewise"""
         return self.L.dhts_bam_is_text(self.h)
 
     def debug_sam_records(self):
@@ -255,6 +257,14 @@ class Context:
         size = self._chk(self.L.dhts_debug_sam_records(self.h, None, 0, C.byref(n)))
         buf = np.zeros(max(size, 1), np.uint8)
         self._chk(self.L.dhts_debug_sam_records(self.h, buf.ctypes.data, size, C.byref(n)))
+        return buf[:size].tobytes(), n.value
+
+    def debug_fastq_records(self):
+        """the BAM records the device encoder made of the last FASTQ / FASTA batch: (bytes, number of records)"""
+        n = C.c_int64(0)
+        size = self._chk(self.L.dhts_debug_fastq_records(self.h, None, 0, C.byref(n)))
+        buf = np.zeros(max(size, 1), np.uint8)
+        self._chk(self.L.dhts_debug_fastq_records(self.h, buf.ctypes.data, size, C.byref(n)))
         return buf[:size].tobytes(), n.value
 
     def header(self):

@@ -10,6 +10,7 @@
 #include "bcf_records.hip"
 #include "vcf_text.hip"
 #include "sam_text.hip"
+#include "fastq_text.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -184,6 +185,8 @@ struct dhts_ctx {
     DevBuf s_out, s_ctr, s_patch, s_name_off, s_name_bytes, s_name_id, s_name_hash, s_pdst, s_pval, s_pwid; uint32_t s_name_hmask = 0; int32_t s_n_names = 0;
     uint32_t s_patch_cap = 0;          // SamPatch entries the measure pass may record (set at the first SAM batch, grown when one needs more)
     int64_t s_last_nrec = 0; uint64_t s_last_len = 0;     // records / bytes of the last SAM batch (dhts_debug_sam_records)
+    int fastq = 0;                    // read_bam on raw reads (fastq_text.hip; sam_text is set as well): 1 FASTQ, 2 FASTA
+    DevBuf f_len, f_flag, f_psum, f_rank, f_mark, f_next, f_plus, f_exit, f_entry, f_stop, f_isstart, f_recrank, f_recline;
     DevBuf v_pos_hi;                   // VCF text: the high words of the batch's 0-based positions (BcfStream::pos_hi)
     DevBuf v_keep, v_endsv; uint64_t proj_gen = 1, keep_gen = 0; int32_t keep_none = 0, fmt_none = 0; bool keep_all = true, fmt_keep_all = true; DevBuf v_fkeep;   // VCF text: the INFO keys the projection reads (VcfArgs::info_keep)
     DevBuf v_cnt, v_base, v_line_off, v_rec_len, v_out, v_ctr, v_undef, v_patch, vd_ctg_off, vd_ctg_bytes, vd_ctg_id, vd_id_off, vd_id_bytes, vd_id_id, vd_id_typ, vd_id_ftyp, vd_ctg_hash, vd_id_hash, v_tok_off, v_tok_bytes, v_tok_bits;
@@ -403,7 +406,7 @@ static void stop_stager(dhts_ctx *c) {
 }
 static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
-    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false;
+    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
@@ -452,6 +455,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_join.inc"
 #include "dhts_bam_scan.inc"
 #include "dhts_sam_scan.inc"
+#include "dhts_fastq_scan.inc"
 #include "dhts_bcf_scan.inc"
 #include "dhts_fetch.inc"
 

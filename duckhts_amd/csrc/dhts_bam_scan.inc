@@ -372,6 +372,8 @@ static int rows_queue(dhts_ctx *c, const BamStream &st, int64_t ntiles, const Ti
 static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask, dhts_bam_batch *out);
 static int sam_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, uint64_t &enc_len, int64_t &nrec, uint64_t &carry_start, bool &rejected, uint64_t &t0);
 static int sam_line_start(dhts_ctx *c, int64_t i, uint64_t &off);
+static int fastq_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, uint64_t &enc_len, int64_t &nrec, uint64_t &carry_start, bool &rejected, uint64_t &t0);
+static int fastq_record_start(dhts_ctx *c, int64_t i, uint64_t &off);
 int dhts_bam_next_batch(dhts_ctx *c, int64_t max_blocks, uint32_t colmask, dhts_bam_batch *out) {
     if (!c || !out) return -1;
     for (;;) {
@@ -405,7 +407,7 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
     // SAM text (dhts_sam_scan.inc): the batch's complete lines become BAM records; the record stage below runs over them, every one complete
     const uint8_t *sam_enc = nullptr; int64_t sam_nrec = 0; uint64_t sam_carry = 0, sam_t0 = 0; bool sam_rej = false;
     if (c->sam_text) {
-        if (sam_text_records(c, B, sam_enc, ulen, sam_nrec, sam_carry, sam_rej, sam_t0)) return -1;
+        if (c->fastq ? fastq_text_records(c, B, sam_enc, ulen, sam_nrec, sam_carry, sam_rej, sam_t0) : sam_text_records(c, B, sam_enc, ulen, sam_nrec, sam_carry, sam_rej, sam_t0)) return -1;
         if (sam_nrec == 0) { out->end_uoff = out_base + sam_carry; out->first_rec_uoff = NONE64; return batch_end(c, B, sam_carry, sam_rej, false, &out->status); }
         u = (uint8_t *)sam_enc; final_batch = true;
     }
@@ -758,7 +760,7 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
     if (bam_overlap_join(c, st, bc, nrows, out)) return -1;
     if (c->sam_text) {
         // back to text offsets: the carry starts at the first line that was not encoded, or at the line of a record bam_read1's checks refuse
-        if (rec_err || nrows < sam_nrec) { rec_err = true; if (sam_line_start(c, nrows, carry_start)) return -1; }
+        if (rec_err || nrows < sam_nrec) { rec_err = true; if (c->fastq ? fastq_record_start(c, nrows, carry_start) : sam_line_start(c, nrows, carry_start)) return -1; }
         else { carry_start = sam_carry; rec_err = sam_rej; }
         have_first_rec = true; first_rec_rel = (uint32_t)sam_t0;
     }

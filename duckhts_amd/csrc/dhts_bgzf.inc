@@ -179,24 +179,24 @@ static int64_t index_impl(dhts_ctx *c, bool extend) {
     const int64_t old_nb = c->n_blocks;
     if (!extend) c->huff_b0 = c->huff_nb = 0;
     if (c->comp_len == 0) { c->n_blocks = 0; return 0; }
-    if (!extend && !c->growing && c->comp_len >= 16) {
+    if (!extend && !c->growing && c->comp_len >= 1) {                      // (a FASTQ / FASTA file may be a few bytes long)
         // not gzip at all but VCF text (hts_detect_format: "##fileformat=VCF"): the bytes are the stream; pieces of 65,280 bytes stand in for blocks
-        uint8_t head[1024];                                  // (hts_detect_format looks at up to 1 KiB: a headerless SAM line is recognised by its columns)
+        uint8_t head[1024] = {0};                              // (hts_detect_format looks at up to 1 KiB: a headerless SAM line is recognised by its columns)
         size_t nhead = c->comp_len < sizeof(head) ? (size_t)c->comp_len : sizeof(head);
         HIPCHK(c, hipMemcpy(head, c->comp.p, nhead, hipMemcpyDeviceToHost));
         uint64_t text_len = c->comp_len;
         // gzip, but not BGZF (no FEXTRA, or an extra field that does not start with the BC subfield: bgzf.c check_header :896-905): the members are
         // inflated by the serial decoder (gzip_serial.hip) and what they hold is read as the uncompressed file would be
-        if (head[0] == 0x1f && head[1] == 0x8b && head[2] == 8 && !((head[3] & 4) && head[10] == 6 && head[11] == 0 && head[12] == 'B' && head[13] == 'C' && head[14] == 2 && head[15] == 0)) {
+        if (c->comp_len >= 16 && head[0] == 0x1f && head[1] == 0x8b && head[2] == 8 && !((head[3] & 4) && head[10] == 6 && head[11] == 0 && head[12] == 'B' && head[13] == 'C' && head[14] == 2 && head[15] == 0)) {
             if (gz_plain_inflate(c)) return -1;
             text_len = c->gz_len;
             memset(head, 0, sizeof(head));
             nhead = text_len < sizeof(head) ? (size_t)text_len : sizeof(head);
             if (nhead) HIPCHK(c, hipMemcpy(head, c->gz_out.p, nhead, hipMemcpyDeviceToHost));
-            if (memcmp(head, "##fileformat=VCF", 16) != 0 && !sam_text_detect(head, nhead) && !c->gz_any) return fail(c, "read_bcf: a plain-gzip file is read when it holds VCF text; this one does not (BAM / BCF inside plain gzip is not read by this build)");
+            if (memcmp(head, "##fileformat=VCF", 16) != 0 && !sam_text_detect(head, nhead) && !fastq_text_detect(head, nhead) && !c->gz_any) return fail(c, "read_bcf: a plain-gzip file is read when it holds VCF text; this one does not (BAM / BCF inside plain gzip is not read by this build)");
         }
-        // VCF text, or SAM text (hts_detect_format: an @HD / @SQ / @RG / @PG / @CO line, or a first line whose columns look like SAM)
-        const bool text_fmt = memcmp(head, "##fileformat=VCF", 16) == 0 || sam_text_detect(head, nhead);
+        // VCF text, SAM text (hts_detect_format: an @HD / @SQ / @RG / @PG / @CO line, or a first line whose columns look like SAM), FASTQ / FASTA
+        const bool text_fmt = memcmp(head, "##fileformat=VCF", 16) == 0 || sam_text_detect(head, nhead) || fastq_text_detect(head, nhead);
         if ((c->gz_plain && c->gz_any) || ((c->gz_plain || !(head[0] == 0x1f && head[1] == 0x8b)) && text_fmt)) {      // (gz_any: bgunzip wants the bytes, whatever they are)
             const uint64_t P = 65280; const int64_t nb = (int64_t)((text_len + P - 1) / P);
             c->h_coff.resize(nb); c->h_clen.resize(nb); c->h_isize.resize(nb); c->h_uoff.resize(nb + 1);

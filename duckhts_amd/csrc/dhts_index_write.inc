@@ -8,10 +8,10 @@
 // Bins are written in ascending order (the reference writes them in khash order; readers do not depend on it).
 // Builds a BAI for the open BAM with one full scan (the scan state is rewound before and after).  Returns the index size.
 static int64_t bam_build_index_impl(dhts_ctx *c, int min_shift);
-int64_t dhts_bam_build_index(dhts_ctx *c) { if (c && c->sam_text) return fail(c, "bam_index: SAM text cannot be indexed here (%s)", SAM_SEQ_ONLY); return bam_build_index_impl(c, 0); }
+int64_t dhts_bam_build_index(dhts_ctx *c) { if (c && c->fastq) return fail(c, "bam_index: FASTQ/FASTA text cannot be indexed (%s)", FASTQ_SEQ_ONLY); if (c && c->sam_text) return fail(c, "bam_index: SAM text cannot be indexed here (%s)", SAM_SEQ_ONLY); return bam_build_index_impl(c, 0); }
 // min_shift > 0: CSI with that min_shift, the depth from the longest reference (sam_index, htslib sam.c:989-1007: hts_adjust_csi_settings
 // from n_lvls = 0); min_shift <= 0: BAI
-extern "C" int64_t dhts_bam_build_index_csi(dhts_ctx *c, int min_shift) { if (c && c->sam_text) return fail(c, "bam_index: SAM text cannot be indexed here (%s)", SAM_SEQ_ONLY); return bam_build_index_impl(c, min_shift); }
+extern "C" int64_t dhts_bam_build_index_csi(dhts_ctx *c, int min_shift) { if (c && c->fastq) return fail(c, "bam_index: FASTQ/FASTA text cannot be indexed (%s)", FASTQ_SEQ_ONLY); if (c && c->sam_text) return fail(c, "bam_index: SAM text cannot be indexed here (%s)", SAM_SEQ_ONLY); return bam_build_index_impl(c, min_shift); }
 static int64_t bam_build_index_impl(dhts_ctx *c, int min_shift) {
     if (!c) return -1;
     HIPCHK(c, hipSetDevice(c->device));

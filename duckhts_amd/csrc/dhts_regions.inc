@@ -68,6 +68,7 @@ static bool parse_region_token(const std::vector<std::string> &names, const std:
 // Returns 0, or 1 when no usable region remains (the reference reports "No reads found for region(s): ...").
 int dhts_bam_set_regions(dhts_ctx *c, const char *regions) {
     if (!c || !c->bam_open) return -1;
+    if (c->fastq && regions && regions[0]) return fail(c, "read_bam: region queries on FASTQ/FASTA text are not supported (%s)", FASTQ_SEQ_ONLY);
     if (c->sam_text && regions && regions[0]) return fail(c, "read_bam: region queries on SAM text are not supported (%s; the reference needs a .tbi / .csi index for them)", SAM_SEQ_ONLY);
     HIPCHK(c, hipSetDevice(c->device));
     c->rg_active = false; c->rg_all = false; c->rg_nocoor = false; c->rg_empty_window = false; c->rg_beg.clear(); c->rg_end.clear(); c->rg_tid_first.clear();
@@ -251,6 +252,7 @@ static std::vector<std::pair<uint64_t, uint64_t>> merged_windows(const IdxWindow
 // builds afterwards on the context that holds the staged ranges.
 extern "C" int dhts_bam_region_segments(dhts_ctx *c, const void *index_bytes, uint64_t n, uint64_t *beg, uint64_t *end, int64_t cap, int64_t *count) {
     if (!c || !c->bam_open || !count) return -1;
+    if (c->fastq) return fail(c, "read_bam: region segments of FASTQ/FASTA text are not supported (%s)", FASTQ_SEQ_ONLY);
     if (c->sam_text) return fail(c, "read_bam: region segments of SAM text are not supported (%s)", SAM_SEQ_ONLY);
     std::vector<QIv> q;
     if (c->rg_active) for (size_t t = 0; t + 1 < c->rg_tid_first.size(); t++) for (uint32_t k = c->rg_tid_first[t]; k < c->rg_tid_first[t + 1]; k++) q.push_back({(int32_t)t, c->rg_beg[k], c->rg_end[k]});
@@ -330,6 +332,7 @@ int dhts_scan_window_stats(const dhts_ctx *c, int64_t *n_windows, int64_t *n_blo
 }
 int dhts_bam_load_index(dhts_ctx *c, const void *bytes, uint64_t n) {
     if (!c || !c->bam_open) return -1;
+    if (c->fastq) return fail(c, "read_bam: an index on FASTQ/FASTA text is not supported (%s)", FASTQ_SEQ_ONLY);
     if (c->sam_text) return fail(c, "read_bam: an index on SAM text is not supported (%s)", SAM_SEQ_ONLY);
     std::vector<QIv> q;
     if (c->rg_active) for (size_t t = 0; t + 1 < c->rg_tid_first.size(); t++) for (uint32_t k = c->rg_tid_first[t]; k < c->rg_tid_first[t + 1]; k++) q.push_back({(int32_t)t, c->rg_beg[k], c->rg_end[k]});

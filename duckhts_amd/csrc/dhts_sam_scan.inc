@@ -132,7 +132,7 @@ static int sam_line_start(dhts_ctx *c, int64_t i, uint64_t &off) {
     uint32_t w = 0; HIPCHK(c, hipMemcpy(&w, (const uint32_t *)c->v_line_off.p + i, 4, hipMemcpyDeviceToHost)); off = w; return 0;
 }
 
-extern "C" int dhts_bam_is_text(const dhts_ctx *c) { return (!c || !c->bam_open || !c->sam_text) ? 0 : c->plain_text ? 2 : 1; }
+extern "C" int dhts_bam_is_text(const dhts_ctx *c) { return (!c || !c->bam_open || !c->sam_text) ? 0 : (c->plain_text ? 2 : 1) + 2 * c->fastq; }
 // debugging aid (include/duckhts_amd_debug.h): the BAM records the encoder made of the last SAM text batch
 extern "C" int64_t dhts_debug_sam_records(dhts_ctx *c, uint8_t *dst, uint64_t cap, int64_t *nrec) {
     if (!c || !c->sam_text) return -1;

@@ -345,7 +345,7 @@ static void producer_main(BamScan *g, Producer *p) {
     // a plain whole-file scan on one device starts decoding while the file is still being staged: the block table is built over the
     // resident prefix and extended as more bytes arrive (DHTS_STREAM=0 stages the whole file first)
     static const bool env_nostream = getenv("DHTS_STREAM") && atoi(getenv("DHTS_STREAM")) == 0;
-    const bool streaming = p->world == 1 && bind->region.empty() && !env_nostream && dhts_bam_is_text(bind->ctx) != 2;   // (uncompressed text is staged first)
+    const bool streaming = p->world == 1 && bind->region.empty() && !env_nostream && (dhts_bam_is_text(bind->ctx) == 0 || dhts_bam_is_text(bind->ctx) % 2 != 0);   // (uncompressed text -- 2, 4, 6 -- is staged first)
     int staged_all = 1;
     if (g->seg_count >= 0) rc = dhts_open_path_segments(c, bind->path.c_str(), bind->header_bytes, g->seg_beg.data(), g->seg_end.data(), g->seg_count);
     else if (p->world > 1) rc = dhts_open_path_shard(c, bind->path.c_str(), p->rank, p->world, bind->header_bytes);
@@ -499,7 +499,7 @@ static void bam_read_global_init(duckdb_init_info info) {
     g->n_workers = thr;
     std::vector<int> devs = device_list();
     if (!bind->region.empty()) devs.resize(1);          // an index window is one short scan: a single device serves it
-    if (dhts_bam_is_text(bind->ctx) != 0) devs.resize(1);   // SAM text is one sequential scan (the C ABI refuses shards of it)
+    if (dhts_bam_is_text(bind->ctx) != 0) devs.resize(1);   // SAM / FASTQ / FASTA text is one sequential scan (the C ABI refuses shards of it)
     for (size_t k = 0; k < devs.size(); k++) {
         Producer *p = new Producer(); p->device = devs[k]; p->rank = (int)k; p->world = (int)devs.size();
         for (int q = 0; q < 3; q++) { HostBatch *hb = new HostBatch(); p->free_slots.push_back(hb); p->all.push_back(hb); }
@@ -1178,6 +1178,183 @@ extern "C" __attribute__((visibility("default"))) void register_read_bcf_functio
     API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
 }
 
+// ================================================================================================
+// read_fastq -- mirrors register_read_fastq_function src/seq_reader.c:752-775, seq_read_bind 235-325, seq_read_init 334-402,
+// seq_read_function 413-639.  The rows come out of the same read_bam batches (fastq_text.hip): NAME = QNAME, SEQUENCE = SEQ ('' for an
+// empty read), QUALITY = QUAL (NULL where read_bam shows '*'), DESCRIPTION always NULL (the reference sets no CO tag under default
+// options).  One thread (duckdb_init_set_max_threads(info, 1)); mate_path runs a second context and interleaves the rows.
+// Registered by duckhts_init_c_api only when DHTS_SEQ_FUNCTIONS=1.
+// ================================================================================================
+enum { FQ_COL_NAME = 0, FQ_COL_DESCRIPTION, FQ_COL_SEQUENCE, FQ_COL_QUALITY, FQ_COL_MATE, FQ_COL_PAIR_ID };
+static const uint32_t kFqMask = (1u << DHTS_BAM_QNAME) | (1u << DHTS_BAM_SEQ) | (1u << DHTS_BAM_QUAL);
+struct FqBind { std::string path, mate_path; bool paired = false, interleaved = false; dhts_ctx *ctx[2] = {nullptr, nullptr}; };
+struct FqStream {
+    dhts_ctx *ctx = nullptr; void *arena = nullptr; uint64_t cap = 0; dhts_bam_batch hb; int64_t pos = 0; bool done = false; std::string err;
+    // the next record of the stream (its row in hb), or -1 at the end: EOF or the first record the reader refuses (sam_read1 < 0)
+    int64_t next() {
+        for (;;) {
+            if (pos < hb.n_rows) return pos++;
+            if (done) return -1;
+            dhts_bam_batch b;
+            if (dhts_bam_next_batch(ctx, 0, kFqMask, &b) != 0) { err = dhts_error(ctx); done = true; return -1; }
+            if (b.status != 0) done = true;
+            memset(&hb, 0, sizeof(hb)); pos = 0;
+            if (b.n_rows == 0) continue;
+            const uint64_t need = dhts_bam_batch_host_bytes(&b, kFqMask);
+            if (need > cap) { if (arena) dhts_host_free(arena); arena = dhts_host_alloc(need + need / 4); cap = arena ? need + need / 4 : 0; }
+            if (!arena || dhts_bam_batch_fetch(ctx, &b, kFqMask, arena, cap, &hb) != 0) { err = arena ? dhts_error(ctx) : "read_fastq: out of pinned host memory"; done = true; memset(&hb, 0, sizeof(hb)); return -1; }
+        }
+    }
+    const char *name(int64_t r, uint32_t *n) const { *n = hb.qname.len[r]; return (const char *)hb.qname.bytes + hb.qname.off[r]; }
+};
+struct FqScan { FqStream st[2]; bool paired = false, interleaved = false, done = false; int pending_mate = 0, interleaved_mate = 1; int64_t mate_row = -1; std::vector<idx_t> column_ids; std::vector<char> tmp;
+                ~FqScan() { for (auto &s : st) if (s.arena) dhts_host_free(s.arena); } };
+static void destroy_fq_bind(void *p) { FqBind *b = (FqBind *)p; if (!b) return; for (auto c : b->ctx) if (c) dhts_destroy(c); delete b; }
+static void destroy_fq_scan(void *p) { delete (FqScan *)p; }
+
+static void fastq_read_bind(duckdb_bind_info info) {
+    auto set_error = API(void, duckdb_bind_set_error, duckdb_bind_info, const char *);
+    auto dfree = API(void, duckdb_free, void *);
+    duckdb_value pv = API(duckdb_value, duckdb_bind_get_parameter, duckdb_bind_info, idx_t)(info, 0);
+    char *file_path = API(char *, duckdb_get_varchar, duckdb_value)(pv);
+    API(void, duckdb_destroy_value, duckdb_value *)(&pv);
+    if (!file_path || strlen(file_path) == 0) { set_error(info, "read_fastq requires a file path"); if (file_path) dfree(file_path); return; }   // seq_reader.c:240-246
+    FqBind *b = new FqBind();
+    b->path = file_path; dfree(file_path);
+    char err[768];
+    if (!file_exists(b->path)) { snprintf(err, sizeof(err), "Failed to open file: %s", b->path.c_str()); set_error(info, err); delete b; return; }   // seq_reader.c:250-256
+    if (char *m = get_named_varchar(info, "mate_path")) { b->mate_path = m; b->paired = true; dfree(m); }
+    b->interleaved = get_named_bool(info, "interleaved") != 0;
+    if (b->paired && b->interleaved) { set_error(info, "read_fastq: use mate_path or interleaved, not both"); delete b; return; }                     // seq_reader.c:287-291
+    // the files are staged whole here; the scan reads them batch by batch (a file that is not FASTQ / FASTA text is refused: INTEGRATION.md)
+    for (int k = 0; k < (b->paired ? 2 : 1); k++) {
+        const std::string &path = k ? b->mate_path : b->path;
+        if (k && !file_exists(path)) { set_error(info, "Failed to open mate FASTQ file"); destroy_fq_bind(b); return; }                              // seq_reader.c:369-370 (raised at init there)
+        b->ctx[k] = dhts_create(device_list()[0]);
+        if (!b->ctx[k]) { set_error(info, "read_fastq: no MI355X (gfx950) device available; this build has no CPU fallback"); destroy_fq_bind(b); return; }
+        if (dhts_open_path(b->ctx[k], path.c_str()) != 0 || dhts_bgzf_index(b->ctx[k]) <= 0 || dhts_bam_open(b->ctx[k]) != 0 || dhts_bam_is_text(b->ctx[k]) < 3) {
+            snprintf(err, sizeof(err), "read_fastq: %s is not read as FASTQ/FASTA text by this build (a first record the FASTQ parser refuses counts as that)", path.c_str());
+            set_error(info, err); destroy_fq_bind(b); return;
+        }
+    }
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto add = API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR), t_us = mk(DUCKDB_TYPE_USMALLINT);
+    add(info, "NAME", t_varchar); add(info, "DESCRIPTION", t_varchar); add(info, "SEQUENCE", t_varchar); add(info, "QUALITY", t_varchar);            // seq_reader.c:311-320
+    if (b->paired || b->interleaved) { add(info, "MATE", t_us); add(info, "PAIR_ID", t_varchar); }
+    rm(&t_varchar); rm(&t_us);
+    API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, b, destroy_fq_bind);
+}
+static void fastq_read_init(duckdb_init_info info) {
+    FqBind *bind = (FqBind *)API(void *, duckdb_init_get_bind_data, duckdb_init_info)(info);
+    FqScan *g = new FqScan();
+    g->paired = bind->paired; g->interleaved = bind->interleaved;
+    for (int k = 0; k < (bind->paired ? 2 : 1); k++) {
+        g->st[k].ctx = bind->ctx[k]; memset(&g->st[k].hb, 0, sizeof(g->st[k].hb));
+        dhts_bam_set_seq_packed(bind->ctx[k], 1); dhts_bam_set_qual_packed(bind->ctx[k], 0);
+        if (dhts_bam_rewind(bind->ctx[k]) != 0) { API(void, duckdb_init_set_error, duckdb_init_info, const char *)(info, "Failed to open sequence file"); delete g; return; }
+    }
+    const idx_t n = API(idx_t, duckdb_init_get_column_count, duckdb_init_info)(info);
+    for (idx_t i = 0; i < n; i++) g->column_ids.push_back(API(idx_t, duckdb_init_get_column_index, duckdb_init_info, idx_t)(info, i));
+    API(void, duckdb_init_set_max_threads, duckdb_init_info, idx_t)(info, 1);
+    API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, g, destroy_fq_scan);
+}
+static void fastq_read_function(duckdb_function_info info, duckdb_data_chunk output) {
+    FqScan *g = (FqScan *)API(void *, duckdb_function_get_init_data, duckdb_function_info)(info);
+    auto set_size = API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t);
+    if (!g || g->done) { set_size(output, 0); return; }
+    const idx_t vector_size = API(idx_t, duckdb_vector_size, void)();
+    auto get_vec = API(duckdb_vector, duckdb_data_chunk_get_vector, duckdb_data_chunk, idx_t);
+    auto get_data = API(void *, duckdb_vector_get_data, duckdb_vector);
+    auto assign_len = API(void, duckdb_vector_assign_string_element_len, duckdb_vector, idx_t, const char *, idx_t);
+    auto fail_scan = [&](const char *msg) { API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, msg); g->done = true; set_size(output, 0); };
+    idx_t row_count = 0;
+    while (row_count < vector_size) {
+        FqStream *s = &g->st[0]; int64_t r; int mate = 0;
+        if (g->paired) {                                                                             // seq_reader.c:476-511
+            if (g->pending_mate) { s = &g->st[1]; r = g->mate_row; mate = 2; g->pending_mate = 0; }
+            else {
+                const int64_t r1 = g->st[0].next(), r2 = g->st[1].next();
+                if (r1 < 0 || r2 < 0) {
+                    if (r1 < 0 && r2 < 0) { g->done = true; break; }
+                    fail_scan("read_fastq: mate files have different record counts"); return;
+                }
+                uint32_t n1, n2; const char *q1 = g->st[0].name(r1, &n1), *q2 = g->st[1].name(r2, &n2);
+                const size_t l1 = strnlen(q1, n1), l2 = strnlen(q2, n2);                             // (strcmp reads C strings)
+                if (l1 != l2 || memcmp(q1, q2, l1) != 0) {
+                    char msg[256]; snprintf(msg, sizeof(msg), "read_fastq: mate files out of sync (QNAME mismatch: '%.*s' vs '%.*s')", (int)l1, q1, (int)l2, q2);
+                    fail_scan(msg); return;
+                }
+                r = r1; mate = 1; g->pending_mate = 1; g->mate_row = r2;
+            }
+        } else {                                                                                     // seq_reader.c:512-531
+            r = s->next();
+            if (r < 0) {
+                if (g->interleaved && g->interleaved_mate == 2) { fail_scan("read_fastq: interleaved file has an unpaired record"); return; }
+                g->done = true; break;
+            }
+            if (g->interleaved) { mate = g->interleaved_mate; g->interleaved_mate = mate == 1 ? 2 : 1; }
+        }
+        const dhts_bam_batch &b = s->hb;
+        const uint32_t l_seq = b.seq.len[r];
+        for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
+            duckdb_vector vec = get_vec(output, ci);
+            switch (g->column_ids[ci]) {
+            case FQ_COL_NAME: { uint32_t n; const char *q = s->name(r, &n); assign_len(vec, row_count, q, strnlen(q, n)); break; }
+            case FQ_COL_DESCRIPTION: set_null(vec, row_count); break;
+            case FQ_COL_SEQUENCE:
+                if (l_seq == 0) { assign_len(vec, row_count, "", 0); break; }
+                if (g->tmp.size() < (size_t)l_seq + 32) g->tmp.resize((size_t)l_seq + 32 + l_seq / 2);
+                expand_seq(b.seq.bytes + b.seq.off[r], l_seq, g->tmp.data());
+                assign_len(vec, row_count, g->tmp.data(), l_seq);
+                break;
+            case FQ_COL_QUALITY: {
+                // "seq_len > 0 && qual[0] != 255": the batch shows an absent QUAL as the one character '*' (a one-base read of quality 9 reads the same: INTEGRATION.md)
+                const uint32_t n = b.qual.len[r]; const char *q = (const char *)b.qual.bytes + b.qual.off[r];
+                if (l_seq == 0 || (n == 1 && q[0] == '*' )) set_null(vec, row_count); else assign_len(vec, row_count, q, n);
+                break;
+            }
+            case FQ_COL_MATE:
+                if (g->paired || g->interleaved) ((uint16_t *)get_data(vec))[row_count] = (uint16_t)mate; else set_null(vec, row_count);
+                break;
+            case FQ_COL_PAIR_ID: {
+                if (!(g->paired || g->interleaved)) { set_null(vec, row_count); break; }
+                uint32_t n; const char *q = s->name(r, &n); size_t len = strnlen(q, n);
+                if (len >= 2 && q[len - 2] == '/' && (q[len - 1] == '1' || q[len - 1] == '2')) len -= 2;     // strip_pair_suffix, seq_reader.c:171-182
+                assign_len(vec, row_count, q, len);
+                break;
+            }
+            default: break;
+            }
+        }
+        row_count++;
+    }
+    for (auto &st : g->st) if (!st.err.empty()) { fail_scan(st.err.c_str()); return; }
+    set_size(output, row_count);
+}
+extern "C" __attribute__((visibility("default"))) void register_read_fastq_function(duckdb_connection connection) {                    // seq_reader.c:752-775
+    duckdb_table_function tf = API(duckdb_table_function, duckdb_create_table_function, void)();
+    API(void, duckdb_table_function_set_name, duckdb_table_function, const char *)(tf, "read_fastq");
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    auto named = API(void, duckdb_table_function_add_named_parameter, duckdb_table_function, const char *, duckdb_logical_type);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR);
+    API(void, duckdb_table_function_add_parameter, duckdb_table_function, duckdb_logical_type)(tf, t_varchar);
+    named(tf, "mate_path", t_varchar);
+    rm(&t_varchar);
+    duckdb_logical_type t_bool = mk(DUCKDB_TYPE_BOOLEAN);
+    named(tf, "interleaved", t_bool);
+    rm(&t_bool);
+    API(void, duckdb_table_function_set_bind, duckdb_table_function, duckdb_table_function_bind_t)(tf, fastq_read_bind);
+    API(void, duckdb_table_function_set_init, duckdb_table_function, duckdb_table_function_init_t)(tf, fastq_read_init);
+    API(void, duckdb_table_function_set_function, duckdb_table_function, duckdb_table_function_t)(tf, fastq_read_function);
+    API(void, duckdb_table_function_supports_projection_pushdown, duckdb_table_function, bool)(tf, true);
+    API(duckdb_state, duckdb_register_table_function, duckdb_connection, duckdb_table_function)(connection, tf);
+    API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
+}
+
+
 extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(duckdb_extension_info info, struct duckdb_extension_access *access) {
     // duckdb_extension.h:1151-1158,1182-1194: fetch the API table, connect, register, disconnect
     const void *api = access->get_api(info, DUCKHTS_API_VERSION);
@@ -1193,6 +1370,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     register_read_bam_function(conn);
     register_bgzip_function(conn); register_bgunzip_function(conn);           // (the readers between them in src/duckhts.c are not on this path)
     register_bam_index_function(conn); register_bcf_index_function(conn); register_tabix_index_function(conn);
+    // read_fastq (src/duckhts.c registers it between the readers) is opt-in until the registered set is widened: DHTS_SEQ_FUNCTIONS=1
+    if (const char *e = getenv("DHTS_SEQ_FUNCTIONS")) if (atoi(e) == 1) register_read_fastq_function(conn);
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);
     return true;
 }

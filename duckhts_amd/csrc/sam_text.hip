@@ -354,10 +354,11 @@ sam_scatter_values(uint8_t *__restrict__ out, const uint32_t *__restrict__ dst, 
 // ---- host: is this stream SAM text?  hts_detect_format2 (htslib hts.c:690-705, 734-743) on its first bytes ------------------------------
 // headered: "@HD\t", "@SQ\t", "@RG\t", "@PG\t" or "@CO\t"; headerless: the first line's columns (parse_tabbed_text, hts.c:484-539) match
 // "ZiZiiCZiiZZOOOOOOOOOOOOOOOOOOOOO+" (colmatch, hts.c:544-553) for at least 9 columns, 11 when the line ended inside the bytes looked at
+static int fastq_text_detect(const uint8_t *s, size_t len);
 static bool sam_text_detect(const uint8_t *s, size_t len) {
     if (len > 1024) len = 1024;
     if (len >= 4 && s[0] == '@' && (!memcmp(s, "@HD\t", 4) || !memcmp(s, "@SQ\t", 4) || !memcmp(s, "@RG\t", 4) || !memcmp(s, "@PG\t", 4) || !memcmp(s, "@CO\t", 4))) return true;
-    if (len >= 1 && (s[0] == '@' || s[0] == '>')) return false;                  // (FASTQ / FASTA / a header this build does not read)
+    if (fastq_text_detect(s, len)) return false;                                 // ('>' / '@' + is_fastaq come in front of the column rule: fastq_text.hip)
     char cols[24]; int nc = 0, complete = 0;
     const uint8_t *str = s, *end = s + len; unsigned seen = 0;
     for (const uint8_t *p = s; p < end; p++) {

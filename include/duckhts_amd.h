@@ -301,7 +301,8 @@ void dhts_bam_set_qual_packed(dhts_ctx *, int on);
 void dhts_bam_set_seq_packed(dhts_ctx *, int on);                    /* SEQ stays 4 bits per base in the batch: (l + 1) / 2 bytes per row, high nibble first, "=ACMGRSVTWYHKDBN"; len = bases, 0 = "*" */
 void dhts_set_super_blocks(dhts_ctx *, int64_t n_blocks);             /* phase A look-ahead (default 524,288 blocks = 67 GB of scratch for a 10 GB file); the table functions use 196,608 */
 int dhts_bcf_is_text(const dhts_ctx *);                              /* after dhts_bcf_open: 0 binary BCF, 1 bgzipped VCF text, 2 plain VCF text (also: VCF text inside plain, non-BGZF gzip -- inflated by the serial device decoder at open, bgzf.c:828-905) */
-int dhts_bam_is_text(const dhts_ctx *);                              /* after dhts_bam_open: 0 BAM, 1 bgzipped SAM text, 2 plain SAM text (uncompressed, or inside plain gzip). SAM text
+int dhts_bam_is_text(const dhts_ctx *);                              /* after dhts_bam_open: 0 BAM, 1 bgzipped SAM text, 2 plain SAM text (uncompressed, or inside plain gzip),
+                                                                      * 3 bgzipped FASTQ, 4 plain FASTQ, 5 bgzipped FASTA, 6 plain FASTA (empty header; one unmapped record per read).  Text
                                                                       * is one sequential scan: regions, index building, shards and header_bytes / region_segments fail on it */
 int dhts_bcf_set_projection(dhts_ctx *, const int32_t *col_ids, int32_t n);   /* default: every schema column */
 int dhts_bcf_set_block_range(dhts_ctx *, int64_t b0, int64_t b1, int speculative_start);

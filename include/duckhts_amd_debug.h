@@ -20,6 +20,8 @@ int64_t dhts_debug_index_prefix(dhts_ctx *, uint64_t nbytes);
 int64_t dhts_debug_vcf_records(dhts_ctx *, uint8_t *dst, uint64_t cap, uint32_t *rec_off, int64_t nrec);
 /* tests: the BAM records (block_size prefixes included) the device encoder made of the last SAM text batch; returns their byte count, *nrec = records */
 int64_t dhts_debug_sam_records(dhts_ctx *, uint8_t *dst, uint64_t cap, int64_t *nrec);
+/* tests: the same for the last FASTQ / FASTA batch (the encoders share the buffer); -1 when the context is not reading FASTQ / FASTA */
+int64_t dhts_debug_fastq_records(dhts_ctx *, uint8_t *dst, uint64_t cap, int64_t *nrec);
 /* tools/dbg: phase A (kernel 0: lane per block, 1: wave per block) / phase B alone over blocks [b0, b0 + nb); ms per launch */
 double dhts_debug_time_huff(dhts_ctx *, int64_t b0, int64_t nb, int reps);
 double dhts_debug_time_lz(dhts_ctx *, int64_t b0, int64_t nb, int reps);

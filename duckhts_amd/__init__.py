@@ -67,6 +67,11 @@ class BcfBatch(C.Structure):
                 ("first_rec_uoff", C.c_uint64), ("end_uoff", C.c_uint64)]
 
 
+class FastaBatch(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("name_off", C.c_void_p), ("name_bytes", C.c_void_p), ("name_nbytes", C.c_uint64),
+                ("seq_off", C.c_void_p), ("seq_bytes", C.c_void_p), ("seq_nbytes", C.c_uint64)]
+
+
 # DUCKDB_TYPE_* element codes -> the canonical type tags of the test oracle's column blob
 _CANON_TYPE = {17: 1, 5: 2, 11: 3, 1: 4, 4: 5, 10: 6}
 ENC_PLAIN, ENC_CONTIG, ENC_DICT, ENC_SAMPLE, ENC_FLOAT_TEXT = 0, 1, 2, 3, 4
@@ -78,7 +83,8 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_kernel_time_reset", "dhts_set_timing", "dhts_bcf_open", "dhts_bcf_info_get", "dhts_bcf_set_projection", "dhts_bcf_set_block_range", "dhts_bcf_set_region", "dhts_bcf_load_index",
            "dhts_bcf_rewind", "dhts_bcf_next_batch",
            "dhts_open_path_range", "dhts_open_path_shard", "dhts_bam_set_file_shard", "dhts_bam_header_bytes", "dhts_voffset",
-           "dhts_host_alloc", "dhts_host_free", "dhts_release_pools", "dhts_device_mem_info", "dhts_shard_window", "dhts_bcf_build_index", "dhts_bgzf_wrap", "dhts_bgzf_compress", "dhts_bgzip_file", "dhts_bgunzip_file", "dhts_bcf_is_text", "dhts_bam_is_text", "dhts_bam_set_seq_packed", "dhts_bcf_header_bytes", "dhts_bcf_region_segments", "dhts_set_super_blocks", "dhts_bam_build_index_csi", "dhts_tabix_build_index", "dhts_bcf_batch_host_bytes", "dhts_bcf_batch_fetch", "dhts_resident_from_cache", "dhts_bam_region_segments", "dhts_open_path_segments", "dhts_open_path_async", "dhts_stage_wait", "dhts_bgzf_index_staged", "dhts_blocks_ahead", "dhts_bam_batch_host_bytes", "dhts_bam_batch_fetch", "dhts_bam_batch_fetch_begin", "dhts_bam_batch_fetch_wait", "dhts_bcf_batch_fetch_begin", "dhts_bcf_batch_fetch_wait", "dhts_device_numa_node", "dhts_bind_thread_to_node", "dhts_bind_thread_near_device", "dhts_bam_set_qual_packed"]
+           "dhts_host_alloc", "dhts_host_free", "dhts_release_pools", "dhts_device_mem_info", "dhts_shard_window", "dhts_bcf_build_index", "dhts_bgzf_wrap", "dhts_bgzf_compress", "dhts_bgzip_file", "dhts_bgunzip_file", "dhts_bcf_is_text", "dhts_bam_is_text", "dhts_bam_set_seq_packed", "dhts_bcf_header_bytes", "dhts_bcf_region_segments", "dhts_set_super_blocks", "dhts_bam_build_index_csi", "dhts_tabix_build_index", "dhts_bcf_batch_host_bytes", "dhts_bcf_batch_fetch", "dhts_resident_from_cache", "dhts_bam_region_segments", "dhts_open_path_segments", "dhts_open_path_async", "dhts_stage_wait", "dhts_bgzf_index_staged", "dhts_blocks_ahead", "dhts_bam_batch_host_bytes", "dhts_bam_batch_fetch", "dhts_bam_batch_fetch_begin", "dhts_bam_batch_fetch_wait", "dhts_bcf_batch_fetch_begin", "dhts_bcf_batch_fetch_wait", "dhts_device_numa_node", "dhts_bind_thread_to_node", "dhts_bind_thread_near_device", "dhts_bam_set_qual_packed",
+           "dhts_fasta_build_index", "dhts_fasta_index_bytes", "dhts_fasta_gzi_bytes", "dhts_fasta_load_index", "dhts_fasta_open_regions", "dhts_fasta_fetch", "dhts_fasta_batch_host_bytes", "dhts_fasta_batch_fetch"]
 
 
 def lib():
@@ -139,6 +145,17 @@ def lib():
         L.dhts_bcf_set_region.argtypes = [C.c_void_p, C.c_char_p]
         L.dhts_bcf_load_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.dhts_bcf_next_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(BcfBatch)]
+        L.dhts_fasta_build_index.restype = C.c_int64
+        L.dhts_fasta_build_index.argtypes = [C.c_void_p]
+        L.dhts_fasta_index_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.dhts_fasta_gzi_bytes.restype = C.c_int64
+        L.dhts_fasta_gzi_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.dhts_fasta_load_index.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64]
+        L.dhts_fasta_open_regions.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        L.dhts_fasta_fetch.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(FastaBatch)]
+        L.dhts_fasta_batch_host_bytes.restype = C.c_uint64
+        L.dhts_fasta_batch_host_bytes.argtypes = [C.POINTER(FastaBatch)]
+        L.dhts_fasta_batch_fetch.argtypes = [C.c_void_p, C.POINTER(FastaBatch), C.c_void_p, C.c_uint64, C.POINTER(FastaBatch)]
         _LIB = L
     return _LIB
 
@@ -423,6 +440,44 @@ class Context:
         self.L.dhts_open_path_segments.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64]
         self._chk(self.L.dhts_open_path_segments(self.h, os.fsencode(path), int(header_bytes), beg.ctypes.data, end.ctypes.data, len(beg)))
         return self
+
+    # ---- fasta_index / read_fasta regions ----
+    def fasta_build_index(self):
+        """(.fai bytes, .gzi bytes) of the resident FASTA (open + bgzf_index first); the .gzi is b"" for uncompressed input"""
+        n = self._chk(self.L.dhts_fasta_build_index(self.h))
+        fai = np.zeros(max(n, 1), np.uint8)
+        self._chk(self.L.dhts_fasta_index_bytes(self.h, fai.ctypes.data, n))
+        m = self._chk(self.L.dhts_fasta_gzi_bytes(self.h, None, 0))
+        gzi = np.zeros(max(m, 1), np.uint8)
+        if m:
+            self._chk(self.L.dhts_fasta_gzi_bytes(self.h, gzi.ctypes.data, m))
+        return fai[:n].tobytes(), gzi[:m].tobytes()
+
+    def fasta_load_index(self, fai):
+        self._chk(self.L.dhts_fasta_load_index(self.h, bytes(fai), len(fai)))
+        return self
+
+    def fasta_open_regions(self, path, regions):
+        self._chk(self.L.dhts_fasta_open_regions(self.h, os.fsencode(path), regions.encode() if isinstance(regions, str) else regions))
+        return self
+
+    def resident_bytes(self):
+        return int(self.L.dhts_resident_bytes(self.h))
+
+    def fasta_fetch(self, regions):
+        """[(name, sequence)] of the regions 'a:1-10,b', through the device batch and the host fetch"""
+        b, hb = FastaBatch(), FastaBatch()
+        self._chk(self.L.dhts_fasta_fetch(self.h, regions.encode() if isinstance(regions, str) else regions, C.byref(b)))
+        need = int(self.L.dhts_fasta_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(need, np.uint8)
+        self._chk(self.L.dhts_fasta_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, C.byref(hb)))
+        base = arena.ctypes.data
+        n = hb.n_rows
+        noff = arena[hb.name_off - base: hb.name_off - base + (n + 1) * 8].view(np.uint64)
+        soff = arena[hb.seq_off - base: hb.seq_off - base + (n + 1) * 8].view(np.uint64)
+        nb = arena[hb.name_bytes - base: hb.name_bytes - base + hb.name_nbytes].tobytes()
+        sb = arena[hb.seq_bytes - base: hb.seq_bytes - base + hb.seq_nbytes].tobytes()
+        return [(nb[int(noff[i]):int(noff[i + 1])], sb[int(soff[i]):int(soff[i + 1])]) for i in range(n)]
 
     def next_batch(self, max_blocks=0, colmask=0x1FFF):
         b = BamBatch()
@@ -800,6 +855,28 @@ def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, s
             else:
                 out[k] = [x for v in vals for x in v]
         return out
+    finally:
+        ctx.close()
+
+
+def fasta_index(src, device=0):
+    """fasta_index on the device: (.fai bytes, .gzi bytes) of a FASTA file (path or bytes), uncompressed or BGZF"""
+    ctx = Context(device)
+    try:
+        ctx.open(src)
+        ctx.bgzf_index()
+        return ctx.fasta_build_index()
+    finally:
+        ctx.close()
+
+
+def fasta_fetch(path, fai, regions, device=0):
+    """read_fasta(region := ...): [(name, sequence)] of the regions by the .fai bytes; stages only what the regions read"""
+    ctx = Context(device)
+    try:
+        ctx.fasta_load_index(fai)
+        ctx.fasta_open_regions(path, regions)
+        return ctx.fasta_fetch(regions)
     finally:
         ctx.close()
 

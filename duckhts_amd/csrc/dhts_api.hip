@@ -11,6 +11,7 @@
 #include "vcf_text.hip"
 #include "sam_text.hip"
 #include "fastq_text.hip"
+#include "fasta_index.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -32,6 +33,7 @@
 #include <vector>
 #include <map>
 #include <algorithm>
+#include <functional>
 #include <limits.h>
 #include <atomic>
 #include <condition_variable>
@@ -155,6 +157,16 @@ struct StageProg {
         cv.notify_all();
     }
 };
+// fasta_index / read_fasta regions (fasta_index.hip, dhts_fasta_index.inc): per-batch scratch of the builder, what it built, the loaded
+// .fai, the inflated text of a BGZF file and the columns of the last fetch
+struct FastaState {
+    DevBuf gtmp, cls, gchunk, gbase, cl, flag, csum, hrank, err, hdr, fshort, rec, ndst, names;
+    std::string fai_text; std::vector<uint8_t> gzi;
+    struct Ent { uint64_t len, off; uint32_t blen, llen; };
+    std::vector<std::string> idx_names; std::vector<Ent> ents; std::map<std::string, int> by_name; bool loaded = false;
+    DevBuf text; uint64_t text_len = 0; bool text_ready = false;
+    DevBuf o_noff, o_soff, o_name, o_seq, rg;
+};
 struct dhts_ctx;
 static void stop_stager(dhts_ctx *c);
 struct dhts_ctx {
@@ -186,6 +198,7 @@ struct dhts_ctx {
     uint32_t s_patch_cap = 0;          // SamPatch entries the measure pass may record (set at the first SAM batch, grown when one needs more)
     int64_t s_last_nrec = 0; uint64_t s_last_len = 0;     // records / bytes of the last SAM batch (dhts_debug_sam_records)
     int fastq = 0;                    // read_bam on raw reads (fastq_text.hip; sam_text is set as well): 1 FASTQ, 2 FASTA
+    FastaState fa;
     DevBuf f_len, f_flag, f_psum, f_rank, f_mark, f_next, f_plus, f_exit, f_entry, f_stop, f_isstart, f_recrank, f_recline;
     DevBuf v_pos_hi;                   // VCF text: the high words of the batch's 0-based positions (BcfStream::pos_hi)
     DevBuf v_keep, v_endsv; uint64_t proj_gen = 1, keep_gen = 0; int32_t keep_none = 0, fmt_none = 0; bool keep_all = true, fmt_keep_all = true; DevBuf v_fkeep;   // VCF text: the INFO keys the projection reads (VcfArgs::info_keep)
@@ -406,7 +419,7 @@ static void stop_stager(dhts_ctx *c) {
 }
 static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
-    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0;
+    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
@@ -456,6 +469,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_scan.inc"
 #include "dhts_sam_scan.inc"
 #include "dhts_fastq_scan.inc"
+#include "dhts_fasta_index.inc"
 #include "dhts_bcf_scan.inc"
 #include "dhts_fetch.inc"
 

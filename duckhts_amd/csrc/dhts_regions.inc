@@ -24,8 +24,12 @@ static long long parse_decimal_sep(const char *str, const char **strend) {
 
 // hts_parse_region (hts.c:3995-4150) for one region token; name lookup through `names`.  Returns false when the token does not
 // name a known reference / is malformed (hts_reglist_create then skips it with a warning, region.c:203-215).
+static bool parse_region_token_fn(const std::function<int(const std::string &)> &getid, const std::string &tok, int &tid, int64_t &beg, int64_t &end);
 static bool parse_region_token(const std::vector<std::string> &names, const std::string &tok, int &tid, int64_t &beg, int64_t &end) {
-    auto getid = [&](const std::string &nm) -> int { for (size_t i = 0; i < names.size(); i++) if (names[i] == nm) return (int)i; return -1; };
+    return parse_region_token_fn([&](const std::string &nm) -> int { for (size_t i = 0; i < names.size(); i++) if (names[i] == nm) return (int)i; return -1; }, tok, tid, beg, end);
+}
+// the same with the name lookup handed in (the .fai of read_fasta keeps a map: dhts_fasta_index.inc)
+static bool parse_region_token_fn(const std::function<int(const std::string &)> &getid, const std::string &tok, int &tid, int64_t &beg, int64_t &end) {
     const int64_t POS_MAX = ((((int64_t)INT32_MAX) << 32) | 0xffffffffll);       // HTS_POS_MAX = INT64_MAX in htslib >= 1.10
     (void)POS_MAX;
     const int64_t PMAX = INT64_MAX;

@@ -230,7 +230,12 @@ static bool host_is_bgzf_header(const uint8_t *p);
 // file[0, header_bytes) and the windows [beg[k], end[k] + length of the BGZF block at end[k]) from dhts_bam_region_segments, merged where
 // they touch, laid out one after the other in file order.  dhts_bgzf_index, dhts_bam_open, dhts_bam_set_regions and dhts_bam_load_index
 // follow as for a whole file; the block table maps resident blocks back to file offsets, so virtual offsets stay those of the file.
+// `raw`: the file is not BGZF and [beg[k], end[k]) are plain byte ranges (the region windows of an uncompressed FASTA: dhts_fasta_index.inc)
+static int open_path_ranges(dhts_ctx *c, const char *path, uint64_t header_bytes, const uint64_t *beg, const uint64_t *end, int64_t n, bool raw);
 extern "C" int dhts_open_path_segments(dhts_ctx *c, const char *path, uint64_t header_bytes, const uint64_t *beg, const uint64_t *end, int64_t n) {
+    return open_path_ranges(c, path, header_bytes, beg, end, n, false);
+}
+static int open_path_ranges(dhts_ctx *c, const char *path, uint64_t header_bytes, const uint64_t *beg, const uint64_t *end, int64_t n, bool raw) {
     if (!c || n < 0 || (n > 0 && (!beg || !end))) return -1;
     discard_prefetch(c);
     int fd = open(path, O_RDONLY);
@@ -244,7 +249,7 @@ extern "C" int dhts_open_path_segments(dhts_ctx *c, const char *path, uint64_t h
         uint64_t b = beg[k], e = end[k];
         if (b >= fsize) continue;
         if (e == ~0ull || e >= fsize) e = fsize;
-        else {
+        else if (!raw) {
             uint8_t h[18];
             if (e + 18 > fsize || pread(fd, h, 18, (off_t)e) != 18 || !host_is_bgzf_header(h)) { close(fd); return fail(c, "index does not match the file (no BGZF block at offset %llu)", (unsigned long long)e); }
             e += ((uint64_t)h[16] | ((uint64_t)h[17] << 8)) + 1;

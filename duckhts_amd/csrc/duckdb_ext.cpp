@@ -1354,6 +1354,162 @@ extern "C" __attribute__((visibility("default"))) void register_read_fastq_funct
     API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
 }
 
+// ================================================================================================
+// read_fasta -- mirrors register_read_fasta_function src/seq_reader.c:645-662, seq_read_bind 235-325, seq_read_init 334-402,
+// seq_read_function 413-472 (regions) and 533-583 (records).  Without a region the rows come out of the read_bam batches of FASTA text
+// like read_fastq's (NAME = QNAME, SEQUENCE = SEQ, '' when empty; DESCRIPTION is the CO tag in the reference, which fastq_parse1 makes only
+// under the fastq_aux option the reference never sets, so it is NULL).  With a region: one row per region in the order given, from the
+// device .fai fetch (dhts_fasta_load_index / dhts_fasta_open_regions / dhts_fasta_fetch); the index is <path>.fai or index_path and is
+// never built here.  One thread.  Registered by duckhts_init_c_api only when DHTS_SEQ_FUNCTIONS=1.
+// ================================================================================================
+struct FaBind { std::string path, region, index_path; int n_regions = 0; dhts_ctx *ctx = nullptr; };
+struct FaScan { FqStream st; bool regions = false, done = false; dhts_ctx *rctx = nullptr; void *arena = nullptr; dhts_fasta_batch hb; int64_t pos = 0; std::string err; std::vector<idx_t> column_ids; std::vector<char> tmp;
+                ~FaScan() { if (st.arena) dhts_host_free(st.arena); if (arena) dhts_host_free(arena); if (rctx) dhts_destroy(rctx); } };
+static void destroy_fa_bind(void *p) { FaBind *b = (FaBind *)p; if (!b) return; if (b->ctx) dhts_destroy(b->ctx); delete b; }
+static void destroy_fa_scan(void *p) { delete (FaScan *)p; }
+// parse_regions_duckdb (seq_reader.c:192-229): pieces between commas, blanks and tabs trimmed, empty ones dropped
+static std::vector<std::string> fasta_split_regions(const std::string &all) {
+    std::vector<std::string> out; size_t p = 0;
+    while (p <= all.size()) {
+        size_t e = all.find(',', p); if (e == std::string::npos) e = all.size();
+        size_t a = p, b = e; while (a < b && (all[a] == ' ' || all[a] == '\t')) a++; while (b > a && (all[b - 1] == ' ' || all[b - 1] == '\t')) b--;
+        if (b > a) out.push_back(all.substr(a, b - a));
+        p = e + 1;
+    }
+    return out;
+}
+static void fasta_read_bind(duckdb_bind_info info) {
+    auto set_error = API(void, duckdb_bind_set_error, duckdb_bind_info, const char *);
+    auto dfree = API(void, duckdb_free, void *);
+    duckdb_value pv = API(duckdb_value, duckdb_bind_get_parameter, duckdb_bind_info, idx_t)(info, 0);
+    char *file_path = API(char *, duckdb_get_varchar, duckdb_value)(pv);
+    API(void, duckdb_destroy_value, duckdb_value *)(&pv);
+    if (!file_path || strlen(file_path) == 0) { set_error(info, "read_fasta requires a file path"); if (file_path) dfree(file_path); return; }   // seq_reader.c:240-246
+    FaBind *b = new FaBind();
+    b->path = file_path; dfree(file_path);
+    char err[768];
+    if (!file_exists(b->path)) { snprintf(err, sizeof(err), "Failed to open file: %s", b->path.c_str()); set_error(info, err); delete b; return; }   // seq_reader.c:250-256
+    if (char *r = get_named_varchar(info, "region")) { b->region = r; dfree(r); b->n_regions = (int)fasta_split_regions(b->region).size(); }
+    if (char *x = get_named_varchar(info, "index_path")) { b->index_path = x; dfree(x); }
+    if (b->n_regions == 0) {                                     // a whole-file scan: the file is staged here, the scan reads it batch by batch
+        b->ctx = dhts_create(device_list()[0]);
+        if (!b->ctx) { set_error(info, "read_fasta: no MI355X (gfx950) device available; this build has no CPU fallback"); destroy_fa_bind(b); return; }
+        if (dhts_open_path(b->ctx, b->path.c_str()) != 0 || dhts_bgzf_index(b->ctx) <= 0 || dhts_bam_open(b->ctx) != 0 || dhts_bam_is_text(b->ctx) < 3) {
+            snprintf(err, sizeof(err), "read_fasta: %s is not read as FASTQ/FASTA text by this build (a first record the FASTQ parser refuses counts as that)", b->path.c_str());
+            set_error(info, err); destroy_fa_bind(b); return;
+        }
+    }
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto add = API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR);
+    add(info, "NAME", t_varchar); add(info, "DESCRIPTION", t_varchar); add(info, "SEQUENCE", t_varchar);                                             // seq_reader.c:311-313
+    rm(&t_varchar);
+    API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, b, destroy_fa_bind);
+}
+static void fasta_read_init(duckdb_init_info info) {
+    FaBind *bind = (FaBind *)API(void *, duckdb_init_get_bind_data, duckdb_init_info)(info);
+    auto init_error = API(void, duckdb_init_set_error, duckdb_init_info, const char *);
+    FaScan *g = new FaScan();
+    memset(&g->hb, 0, sizeof(g->hb)); memset(&g->st.hb, 0, sizeof(g->st.hb));
+    if (bind->n_regions > 0) {                                   // seq_reader.c:383-390: the index is loaded, never built
+        g->regions = true;
+        const std::string fai_path = bind->index_path.empty() ? bind->path + ".fai" : bind->index_path;
+        std::string fai; bool have = false;
+        if (FILE *f = fopen(fai_path.c_str(), "rb")) { char buf[65536]; size_t n; while ((n = fread(buf, 1, sizeof(buf), f)) > 0) fai.append(buf, n); fclose(f); have = true; }
+        g->rctx = have ? dhts_create(device_list()[0]) : nullptr;
+        if (have && !g->rctx) { init_error(info, "read_fasta: no MI355X (gfx950) device available; this build has no CPU fallback"); delete g; return; }
+        if (!have || dhts_fasta_load_index(g->rctx, fai.data(), fai.size()) != 0 || dhts_fasta_open_regions(g->rctx, bind->path.c_str(), bind->region.c_str()) != 0) {
+            init_error(info, "read_fasta: region query requires a FASTA index (.fai); run fasta_index(path) first"); delete g; return;
+        }
+        dhts_fasta_batch db;
+        if (dhts_fasta_fetch(g->rctx, bind->region.c_str(), &db) != 0) {
+            // fai_fetch64 fails region by region (seq_reader.c:432-441): name the first one that does
+            std::string bad;
+            for (auto &r : fasta_split_regions(bind->region)) { dhts_fasta_batch one; if (dhts_fasta_fetch(g->rctx, r.c_str(), &one) != 0) { bad = r; break; } }
+            g->err = "read_fasta: invalid or missing region '" + bad + "'";
+        } else {
+            const uint64_t need = dhts_fasta_batch_host_bytes(&db);
+            g->arena = dhts_host_alloc(need);
+            if (!g->arena || dhts_fasta_batch_fetch(g->rctx, &db, g->arena, need, &g->hb) != 0) { init_error(info, g->arena ? dhts_error(g->rctx) : "read_fasta: out of pinned host memory"); delete g; return; }
+        }
+    } else {
+        g->st.ctx = bind->ctx;
+        dhts_bam_set_seq_packed(bind->ctx, 1); dhts_bam_set_qual_packed(bind->ctx, 0);
+        if (dhts_bam_rewind(bind->ctx) != 0) { init_error(info, "Failed to open sequence file"); delete g; return; }
+    }
+    const idx_t n = API(idx_t, duckdb_init_get_column_count, duckdb_init_info)(info);
+    for (idx_t i = 0; i < n; i++) g->column_ids.push_back(API(idx_t, duckdb_init_get_column_index, duckdb_init_info, idx_t)(info, i));
+    API(void, duckdb_init_set_max_threads, duckdb_init_info, idx_t)(info, 1);
+    API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, g, destroy_fa_scan);
+}
+static void fasta_read_function(duckdb_function_info info, duckdb_data_chunk output) {
+    FaScan *g = (FaScan *)API(void *, duckdb_function_get_init_data, duckdb_function_info)(info);
+    auto set_size = API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t);
+    if (!g || g->done) { set_size(output, 0); return; }
+    const idx_t vector_size = API(idx_t, duckdb_vector_size, void)();
+    auto get_vec = API(duckdb_vector, duckdb_data_chunk_get_vector, duckdb_data_chunk, idx_t);
+    auto assign_len = API(void, duckdb_vector_assign_string_element_len, duckdb_vector, idx_t, const char *, idx_t);
+    auto fail_scan = [&](const char *msg) { API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, msg); g->done = true; set_size(output, 0); };
+    if (!g->err.empty()) { fail_scan(g->err.c_str()); return; }
+    idx_t row_count = 0;
+    while (row_count < vector_size) {
+        if (g->regions) {                                                                            // seq_reader.c:425-472
+            if (g->pos >= g->hb.n_rows) { g->done = true; break; }
+            const int64_t r = g->pos++;
+            for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
+                duckdb_vector vec = get_vec(output, ci);
+                switch (g->column_ids[ci]) {
+                case FQ_COL_NAME: assign_len(vec, row_count, (const char *)g->hb.name_bytes + g->hb.name_off[r], g->hb.name_off[r + 1] - g->hb.name_off[r]); break;
+                case FQ_COL_DESCRIPTION: set_null(vec, row_count); break;
+                case FQ_COL_SEQUENCE: assign_len(vec, row_count, (const char *)g->hb.seq_bytes + g->hb.seq_off[r], g->hb.seq_off[r + 1] - g->hb.seq_off[r]); break;
+                default: break;
+                }
+            }
+            row_count++;
+            continue;
+        }
+        const int64_t r = g->st.next();
+        if (r < 0) { g->done = true; break; }
+        const dhts_bam_batch &b = g->st.hb;
+        const uint32_t l_seq = b.seq.len[r];
+        for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
+            duckdb_vector vec = get_vec(output, ci);
+            switch (g->column_ids[ci]) {
+            case FQ_COL_NAME: { uint32_t n; const char *q = g->st.name(r, &n); assign_len(vec, row_count, q, strnlen(q, n)); break; }
+            case FQ_COL_DESCRIPTION: set_null(vec, row_count); break;
+            case FQ_COL_SEQUENCE:
+                if (l_seq == 0) { assign_len(vec, row_count, "", 0); break; }
+                if (g->tmp.size() < (size_t)l_seq + 32) g->tmp.resize((size_t)l_seq + 32 + l_seq / 2);
+                expand_seq(b.seq.bytes + b.seq.off[r], l_seq, g->tmp.data());
+                assign_len(vec, row_count, g->tmp.data(), l_seq);
+                break;
+            default: break;
+            }
+        }
+        row_count++;
+    }
+    if (!g->st.err.empty()) { fail_scan(g->st.err.c_str()); return; }
+    set_size(output, row_count);
+}
+extern "C" __attribute__((visibility("default"))) void register_read_fasta_function(duckdb_connection connection) {                    // seq_reader.c:645-662
+    duckdb_table_function tf = API(duckdb_table_function, duckdb_create_table_function, void)();
+    API(void, duckdb_table_function_set_name, duckdb_table_function, const char *)(tf, "read_fasta");
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    auto named = API(void, duckdb_table_function_add_named_parameter, duckdb_table_function, const char *, duckdb_logical_type);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR);
+    API(void, duckdb_table_function_add_parameter, duckdb_table_function, duckdb_logical_type)(tf, t_varchar);
+    named(tf, "region", t_varchar);
+    named(tf, "index_path", t_varchar);
+    rm(&t_varchar);
+    API(void, duckdb_table_function_set_bind, duckdb_table_function, duckdb_table_function_bind_t)(tf, fasta_read_bind);
+    API(void, duckdb_table_function_set_init, duckdb_table_function, duckdb_table_function_init_t)(tf, fasta_read_init);
+    API(void, duckdb_table_function_set_function, duckdb_table_function, duckdb_table_function_t)(tf, fasta_read_function);
+    API(void, duckdb_table_function_supports_projection_pushdown, duckdb_table_function, bool)(tf, true);
+    API(duckdb_state, duckdb_register_table_function, duckdb_connection, duckdb_table_function)(connection, tf);
+    API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
+}
 
 extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(duckdb_extension_info info, struct duckdb_extension_access *access) {
     // duckdb_extension.h:1151-1158,1182-1194: fetch the API table, connect, register, disconnect
@@ -1371,7 +1527,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     register_bgzip_function(conn); register_bgunzip_function(conn);           // (the readers between them in src/duckhts.c are not on this path)
     register_bam_index_function(conn); register_bcf_index_function(conn); register_tabix_index_function(conn);
     // read_fastq (src/duckhts.c registers it between the readers) is opt-in until the registered set is widened: DHTS_SEQ_FUNCTIONS=1
-    if (const char *e = getenv("DHTS_SEQ_FUNCTIONS")) if (atoi(e) == 1) register_read_fastq_function(conn);
+    // read_fasta and fasta_index are opt-in with it, in the reference's order (src/duckhts.c:56-58): read_fasta, read_fastq, fasta_index
+    if (const char *e = getenv("DHTS_SEQ_FUNCTIONS")) if (atoi(e) == 1) { register_read_fasta_function(conn); register_read_fastq_function(conn); register_fasta_index_function(conn); }
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);
     return true;
 }

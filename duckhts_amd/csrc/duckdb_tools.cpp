@@ -19,7 +19,7 @@
 #define API(ret, name, ...) ((ret(*)(__VA_ARGS__))duckdb_ext_api[SLOT_##name])
 
 namespace {
-struct OneRow { bool emitted = false; std::string path, format; int64_t bytes_in = 0, bytes_out = 0; bool four = false; };
+struct OneRow { bool emitted = false; std::string path, format; int64_t bytes_in = 0, bytes_out = 0; bool four = false, two = false; };
 void destroy_row(void *p) { delete (OneRow *)p; }
 
 char *named_varchar(duckdb_bind_info info, const char *name) {
@@ -75,7 +75,7 @@ void row_scan(duckdb_function_info info, duckdb_data_chunk output) {
     ((bool *)data(vec(output, 0)))[0] = true;
     str(vec(output, 1), 0, r->path.c_str());
     if (r->four) { ((int64_t *)data(vec(output, 2)))[0] = r->bytes_in; ((int64_t *)data(vec(output, 3)))[0] = r->bytes_out; }
-    else str(vec(output, 2), 0, r->format.c_str());
+    else if (!r->two) str(vec(output, 2), 0, r->format.c_str());
     r->emitted = true;
     setn(output, 1);
 }
@@ -207,6 +207,43 @@ void bam_index_bind(duckdb_bind_info info) { index_bind_common(info, 0); }
 void bcf_index_bind(duckdb_bind_info info) { index_bind_common(info, 1); }
 void tabix_index_bind(duckdb_bind_info info) { index_bind_common(info, 2); }
 
+// ---- fasta_index (src/seq_reader.c:676-750 -> fai_build3, htslib faidx.c:540-620): <path>.fai or index_path, and <path>.gzi for BGZF ----
+// The files are written under temporary names and renamed when all of them are complete: an error leaves no partial file behind.
+bool write_whole(const std::string &tmp, const void *p, size_t n) {
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = fwrite(p, 1, n, f) == n;
+    return (fclose(f) == 0) && ok;
+}
+void fasta_index_bind(duckdb_bind_info info) {
+    const std::string path = positional_path(info);
+    if (path.empty()) { bind_error(info, "fasta_index requires a file path"); return; }
+    const std::string index_path = take(named_varchar(info, "index_path"));
+    const std::string fai_path = index_path.empty() ? path + ".fai" : index_path, gzi_path = path + ".gzi";
+    const std::string tmp_fai = fai_path + ".tmp" + std::to_string((long)getpid()), tmp_gzi = gzi_path + ".tmp" + std::to_string((long)getpid());
+    bool ok = false;
+    if (dhts_ctx *c = dhts_create(device_id())) {
+        int64_t n = -1, m = 0;
+        if (dhts_open_path(c, path.c_str()) == 0 && dhts_bgzf_index(c) >= 0 && (n = dhts_fasta_build_index(c)) >= 0 && (m = dhts_fasta_gzi_bytes(c, nullptr, 0)) >= 0) {
+            std::vector<uint8_t> fai((size_t)n + 1), gzi((size_t)m + 1);
+            ok = dhts_fasta_index_bytes(c, fai.data(), (uint64_t)n) == 0 && (m == 0 || dhts_fasta_gzi_bytes(c, gzi.data(), (uint64_t)m) == m);
+            ok = ok && write_whole(tmp_fai, fai.data(), (size_t)n) && (m == 0 || write_whole(tmp_gzi, gzi.data(), (size_t)m));
+            ok = ok && (m == 0 || rename(tmp_gzi.c_str(), gzi_path.c_str()) == 0) && rename(tmp_fai.c_str(), fai_path.c_str()) == 0;
+            if (!ok) { unlink(tmp_fai.c_str()); unlink(tmp_gzi.c_str()); }
+        } else if (getenv("DHTS_TRACE")) fprintf(stderr, "[dhts] fasta_index: %s\n", dhts_error(c));
+        dhts_destroy(c);
+    }
+    if (!ok) { bind_error(info, "fasta_index: failed to build index for " + path); return; }
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    auto add = API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type);
+    duckdb_logical_type tb = mk(DUCKDB_TYPE_BOOLEAN), tv = mk(DUCKDB_TYPE_VARCHAR);
+    add(info, "success", tb); add(info, "index_path", tv);                       // seq_reader.c:702-707
+    rm(&tb); rm(&tv);
+    OneRow *r = new OneRow(); r->two = true; r->path = index_path;               // the parameter, or "" (seq_reader.c:710)
+    API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, r, destroy_row);
+}
+
 struct Param { const char *name; int type; };
 void register_one(duckdb_connection connection, const char *name, duckdb_table_function_bind_t bind, const std::vector<Param> &params) {
     duckdb_table_function tf = API(duckdb_table_function, duckdb_create_table_function, void)();
@@ -241,6 +278,9 @@ __attribute__((visibility("default"))) void register_bam_index_function(duckdb_c
 }
 __attribute__((visibility("default"))) void register_bcf_index_function(duckdb_connection connection) {                             // hts_index_builder.c:346-364
     register_one(connection, "bcf_index", bcf_index_bind, {{"index_path", DUCKDB_TYPE_VARCHAR}, {"min_shift", DUCKDB_TYPE_INTEGER}, {"threads", DUCKDB_TYPE_INTEGER}});
+}
+__attribute__((visibility("default"))) void register_fasta_index_function(duckdb_connection connection) {                           // seq_reader.c:736-750
+    register_one(connection, "fasta_index", fasta_index_bind, {{"index_path", DUCKDB_TYPE_VARCHAR}});
 }
 __attribute__((visibility("default"))) void register_tabix_index_function(duckdb_connection connection) {                           // hts_index_builder.c:366-390
     register_one(connection, "tabix_index", tabix_index_bind, {{"preset", DUCKDB_TYPE_VARCHAR}, {"index_path", DUCKDB_TYPE_VARCHAR}, {"min_shift", DUCKDB_TYPE_INTEGER}, {"threads", DUCKDB_TYPE_INTEGER},

@@ -376,6 +376,39 @@ int dhts_bam_batch_fetch(dhts_ctx *, const dhts_bam_batch *b, uint32_t colmask, 
 int dhts_bam_batch_fetch_begin(dhts_ctx *, const dhts_bam_batch *dev_batch, uint32_t colmask, void *dst, uint64_t cap, dhts_bam_batch *host_batch, int slot);
 int dhts_bam_batch_fetch_wait(dhts_ctx *, int slot);
 
+/* ---- fasta_index / read_fasta(region := ...) ------------------------------------------------- */
+/* .fai builder (src/seq_reader.c:676-750 -> fai_build3 -> fai_build_core, htslib faidx.c:132-349, a bgzf_getc loop; fai_save :352-377):
+ * the context holds the whole file (dhts_open_path / dhts_open_host + dhts_bgzf_index), uncompressed or BGZF.  The device finds the lines,
+ * their lengths, isgraph counts and classes, and reduces them per record; the host carries the open record from batch to batch and keeps
+ * the first of equal names.  Returns the number of .fai bytes ("name\tlen\toffset\tline_blen\tline_len\n" per sequence), or < 0 with
+ * htslib's wording and line number in dhts_error ("Different line length in sequence 'x' at line 7", "File truncated at line 9", ...).
+ * FASTQ (a first record that starts with '@') and plain gzip ("Cannot index files compressed with gzip, please use bgzip") are refused. */
+int64_t dhts_fasta_build_index(dhts_ctx *);
+int dhts_fasta_index_bytes(dhts_ctx *, void *dst, uint64_t n);
+/* the .gzi that goes with the .fai of a BGZF file (bgzf_index_dump_hfile, bgzf.c:2382-2408, as the single-threaded read path records it,
+ * :1225-1236): a u64 count, then (compressed, uncompressed) u64 offsets of every non-empty block behind the first.  n = 0 asks for the
+ * size; 0 bytes for uncompressed input. */
+int64_t dhts_fasta_gzi_bytes(dhts_ctx *, void *dst, uint64_t n);
+/* fai_read (faidx.c:380-446): the first of equal names stays; a line without four numbers is an error */
+int dhts_fasta_load_index(dhts_ctx *, const void *fai, uint64_t n);
+/* stages what the regions 'a:1-10,b' read, by the loaded .fai: of an uncompressed file only the byte windows of the regions (merged where
+ * they touch; dhts_resident_bytes says how much), of a BGZF file everything -- it is inflated whole on the first fetch, so no .gzi is needed */
+int dhts_fasta_open_regions(dhts_ctx *, const char *path, const char *regions);
+/* fai_fetch64 for every region of 'a:1-10,b' in one launch (fai_parse_region with flags 0; fai_get_val's clamping, faidx.c:798-827;
+ * fai_retrieve :716-796): regions are split at commas, blanks trimmed, empty pieces dropped (src/seq_reader.c:192-229), one row per region
+ * in the order given.  name = the region text up to its first ':' (seq_reader.c:443-446).  Columns are DEVICE pointers: offsets have
+ * n_rows + 1 entries.  beg >= len gives an empty string; an unknown name, line_blen 0 in the index and a source byte behind the end of the
+ * file are errors.  Works on resident bytes from dhts_fasta_open_regions, dhts_open_path or dhts_open_host. */
+typedef struct {
+    int64_t n_rows;
+    const uint64_t *name_off; const uint8_t *name_bytes; uint64_t name_nbytes;
+    const uint64_t *seq_off; const uint8_t *seq_bytes; uint64_t seq_nbytes;
+} dhts_fasta_batch;
+int dhts_fasta_fetch(dhts_ctx *, const char *regions, dhts_fasta_batch *out);
+/* read-back in the style of dhts_bam_batch_fetch: `out` = `b` with HOST pointers into dst */
+uint64_t dhts_fasta_batch_host_bytes(const dhts_fasta_batch *b);
+int dhts_fasta_batch_fetch(dhts_ctx *, const dhts_fasta_batch *b, void *dst, uint64_t cap, dhts_fasta_batch *out);
+
 /* ---- utilities ------------------------------------------------------------------------------ */
 int dhts_memcpy_d2h(dhts_ctx *, void *dst, const void *src_dev, uint64_t n);
 int dhts_sync(dhts_ctx *);

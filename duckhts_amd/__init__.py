@@ -284,6 +284,17 @@ class Context:
         self._chk(self.L.dhts_debug_fastq_records(self.h, buf.ctypes.data, size, C.byref(n)))
         return buf[:size].tobytes(), n.value
 
+    def debug_deflate_codes(self, counts, maxbits):
+        """the DEFLATE encoder's code builder on the device: counts[ncases, nsym] -> (lengths uint8[ncases, nsym], table words
+        uint32[ncases, nsym]: bit-reversed code | length << 16).  Only for count vectors the builder is known to end on."""
+        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert cnt.ndim == 2
+        lens, codes = np.zeros(cnt.shape, np.uint8), np.zeros(cnt.shape, np.uint32)
+        f = self.L.dhts_debug_deflate_codes
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
+        self._chk(f(self.h, cnt.ctypes.data, cnt.shape[1], maxbits, cnt.shape[0], lens.ctypes.data, codes.ctypes.data))
+        return lens, codes
+
     def header(self):
         h = BamHeader()
         self._chk(self.L.dhts_bam_header_get(self.h, C.byref(h)))

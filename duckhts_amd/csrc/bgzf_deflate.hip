@@ -106,6 +106,22 @@ __device__ void dfl_assign_codes(const uint8_t *len, uint32_t *tab, uint32_t n, 
     __syncthreads();
 }
 
+// test hook (dhts_debug_deflate_codes): the code builder alone, one wave per case.  counts: ncases rows of nsym words; the lengths and the
+// table words (reversed code | length << 16) of every case go out as they stand in LDS
+extern "C" __global__ void __launch_bounds__(64)
+bgzf_deflate_debug_codes(const uint32_t *__restrict__ counts, uint32_t nsym, uint32_t maxbits, int64_t ncases, uint8_t *__restrict__ lens_out, uint32_t *__restrict__ codes_out) {
+    __shared__ uint32_t cnt[288], ord[288], tab[288];
+    __shared__ uint8_t len[288];
+    const int lane = threadIdx.x;
+    const int64_t ci = blockIdx.x;
+    if (ci >= ncases || nsym > 288u) return;
+    for (uint32_t s = lane; s < nsym; s += 64) cnt[s] = counts[(uint64_t)ci * nsym + s];
+    __syncthreads();
+    dfl_build_lengths(cnt, len, nsym, maxbits, lane, ord);
+    dfl_assign_codes(len, tab, nsym, lane);
+    for (uint32_t s = lane; s < nsym; s += 64) { lens_out[(uint64_t)ci * nsym + s] = len[s]; codes_out[(uint64_t)ci * nsym + s] = tab[s]; }
+}
+
 extern "C" __global__ void __launch_bounds__(64)
 bgzf_deflate_blocks(const uint8_t *__restrict__ in, uint64_t n_in, int64_t nblk, int level, uint8_t *__restrict__ slots, uint32_t *__restrict__ sizes, uint32_t *__restrict__ tok_all) {
     extern __shared__ __attribute__((aligned(16))) uint8_t dsm[];

@@ -45,6 +45,29 @@ extern "C" int64_t dhts_bgzf_compress(dhts_ctx *c, const void *raw, uint64_t n, 
     memcpy((uint8_t *)out + at, BGZF_EOF_BLOCK, 28);
     return (int64_t)(at + 28);
 }
+// tests: dfl_build_lengths + dfl_assign_codes of the encoder on ncases count vectors of nsym symbols each (host arrays; one launch, one wave per
+// case).  The caller answers for count vectors the builder's loops end on (tests/deflate_code_ref.py carries each through first); what can
+// be refused here is: a total that does not fit 32 bits, more symbols than maxbits can code.
+extern "C" int dhts_debug_deflate_codes(dhts_ctx *c, const uint32_t *counts, uint32_t nsym, uint32_t maxbits, int64_t ncases, uint8_t *lens_out, uint32_t *codes_out) {
+    if (!c) return -1;
+    if (!counts || !lens_out || !codes_out || nsym < 2u || nsym > 288u || maxbits < 1u || maxbits > 15u || (uint64_t)nsym > (1ull << maxbits) || ncases < 0 || ncases > (1 << 20))
+        return fail(c, "debug_deflate_codes: arguments out of range");
+    if (ncases == 0) return 0;
+    for (int64_t k = 0; k < ncases; k++) {
+        uint64_t t = 0; for (uint32_t s = 0; s < nsym; s++) t += counts[(uint64_t)k * nsym + s];
+        if (t >> 32) return fail(c, "debug_deflate_codes: the counts of case %lld do not fit 32 bits", (long long)k);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nw = (size_t)ncases * nsym;
+    ENSURE(c, c->z_in, nw * 4 + 64); ENSURE(c, c->z_out, nw + 64); ENSURE(c, c->z_tok, nw * 4 + 64);
+    HIPCHK(c, hipMemcpyAsync(c->z_in.p, counts, nw * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(bgzf_deflate_debug_codes, dim3((unsigned)ncases), dim3(64), 0, c->stream, (const uint32_t *)c->z_in.p, nsym, maxbits, ncases, (uint8_t *)c->z_out.p, (uint32_t *)c->z_tok.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(lens_out, c->z_out.p, nw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(codes_out, c->z_tok.p, nw * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
 // bgzip(path): file -> BGZF file (bgzip.c:231-293).  Returns 0, -2 input cannot be opened, -3 output cannot be opened, -4 read error, -5 write error.
 extern "C" int dhts_bgzip_file(dhts_ctx *c, const char *in_path, const char *out_path, int level, int64_t *bytes_in, int64_t *bytes_out) {
     if (!c || !in_path || !out_path) return -1;

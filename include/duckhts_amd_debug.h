@@ -29,6 +29,10 @@ int dhts_debug_huff_run(dhts_ctx *, int64_t b0, int64_t nb, int kernel);
 /* tests: metadata, literal bytes and tokens phase A left for scratch slot s (the wave and the lane kernel must agree word for word) */
 int dhts_debug_scratch_get(dhts_ctx *, int64_t s, uint32_t *meta4, uint8_t *lit, uint32_t *tok);
 int dhts_debug_meta(dhts_ctx *, int64_t s, uint32_t *out4);
+/* tests: the DEFLATE encoder's code builder alone (bgzf_deflate.hip: dfl_build_lengths + dfl_assign_codes) on ncases count vectors of nsym
+ * symbols (host arrays, case after case); lens_out: ncases * nsym code lengths, codes_out: the table words (bit-reversed code | length << 16).
+ * Only for count vectors the builder's loops are known to end on (tests/deflate_code_ref.py). */
+int dhts_debug_deflate_codes(dhts_ctx *, const uint32_t *counts, uint32_t nsym, uint32_t maxbits, int64_t ncases, uint8_t *lens_out, uint32_t *codes_out);
 /* (diagnostic builds only: -DDHTS_DIAG dhts_debug_diag, -DHW_DIAG dhts_debug_hw_diag, -DTR_DIAG dhts_debug_tr_diag: per-phase cycle counters) */
 int dhts_debug_diag(dhts_ctx *, unsigned long long *out8);
 int dhts_debug_hw_diag(dhts_ctx *, unsigned long long *out16, int reset);

@@ -322,9 +322,16 @@ class Context:
         self._chk(self.L.dhts_bam_set_tag_columns(self.h, arr.ctypes.data, len(arr)))
         self._tag_ids = list(ids)
 
-    def build_index(self):
-        """BAI bytes for the open BAM (one whole-file scan; hts_idx_push / hts_idx_finish restated on the host)"""
-        n = self._chk(self.L.dhts_bam_build_index(self.h))
+    def build_index(self, min_shift=0):
+        """BAI bytes for the open BAM (one whole-file scan; hts_idx_push / hts_idx_finish restated on the host).  min_shift > 0: a CSI with
+        that min_shift and the depth the longest reference asks for (dhts_bam_build_index_csi); those bytes are the UNCOMPRESSED CSI, a
+        .csi file on disk is their BGZF wrapping (dhts_bgzf_wrap)."""
+        if min_shift > 0:
+            self.L.dhts_bam_build_index_csi.restype = C.c_int64
+            self.L.dhts_bam_build_index_csi.argtypes = [C.c_void_p, C.c_int]
+            n = self._chk(self.L.dhts_bam_build_index_csi(self.h, min_shift))
+        else:
+            n = self._chk(self.L.dhts_bam_build_index(self.h))
         out = np.empty(n, np.uint8)
         self._chk(self.L.dhts_bam_index_bytes(self.h, out.ctypes.data, n))
         return out.tobytes()

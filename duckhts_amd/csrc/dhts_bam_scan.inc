@@ -253,7 +253,7 @@ extern "C" int64_t dhts_tabix_build_index(dhts_ctx *c, int preset, int sc, int b
     if (rc) return fail(c, "tabix_index: %s", err.c_str());
     if (!inited) init_index();
     uint64_t fin = c->comp_len;
-    if (nb > 0 && c->h_isize[nb - 1] == 0) fin = c->h_coff[nb - 1];
+    for (int64_t k = nb; k > 0 && c->h_isize[k - 1] == 0; k--) fin = c->h_coff[k - 1];
     if (!ib.finish(fin << 16)) return fail(c, "tabix_index: %s", ib.err.c_str());
     {
         const uint32_t conf[6] = {(uint32_t)preset, (uint32_t)sc, (uint32_t)bc, (uint32_t)ec, (uint32_t)meta_char, (uint32_t)line_skip}; uint32_t l_nm = 0;

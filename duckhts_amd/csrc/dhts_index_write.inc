@@ -121,9 +121,11 @@ static int64_t bam_build_index_impl(dhts_ctx *c, int min_shift) {
     (void)rc; (void)t_loop;
     break;
   }
-    // where the reader stands after the failing read at EOF: the address of the last trailing empty block, else the file size
+    // where the reader stands after the failing read at EOF: behind the last block that holds data -- the address of the FIRST trailing
+    // empty block, else the file size (bgzf_read leaves block_address there, bgzf.c:1282-1285; bgzf_read_block skips the empty blocks
+    // with a local address and returns at the end of the file without storing it, 1145-1155)
     uint64_t fin = c->comp_len;
-    if (nb > 0 && c->h_isize[nb - 1] == 0) fin = c->h_coff[nb - 1];
+    for (int64_t k = nb; k > 0 && c->h_isize[k - 1] == 0; k--) fin = c->h_coff[k - 1];
     const double t_dl = now();
     if (!ib.finish(fin << 16)) return fail(c, "index build: %s", ib.err.c_str());
     ib.save(c->built_index);
@@ -250,7 +252,7 @@ int64_t dhts_bcf_build_index(dhts_ctx *c, int min_shift) {
     if (rc) return -1;
     if (!ok) return fail(c, "index build: %s", ib.err.c_str());
     uint64_t fin = c->comp_len;
-    if (nb > 0 && c->h_isize[nb - 1] == 0) fin = c->h_coff[nb - 1];
+    for (int64_t k = nb; k > 0 && c->h_isize[k - 1] == 0; k--) fin = c->h_coff[k - 1];
     lap(t2_scan);
     if (!ib.finish(fin << 16)) return fail(c, "index build: %s", ib.err.c_str());
     if (text) {                                                                      // tbx_set_meta: the VCF preset {TBX_VCF, 1, 2, 0, '#', 0}, l_nm, names

@@ -72,6 +72,13 @@ class FastaBatch(C.Structure):
                 ("seq_off", C.c_void_p), ("seq_bytes", C.c_void_p), ("seq_nbytes", C.c_uint64)]
 
 
+class BedBatch(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("status", C.c_int32), ("n_cols", C.c_int32), ("cols", C.POINTER(BcfCol))]
+
+
+BED_COLUMNS = ["chrom", "start", "end", "name", "score", "strand", "thick_start", "thick_end", "item_rgb", "block_count", "block_sizes", "block_starts", "extra"]
+BED_INT_COLUMNS = (1, 2, 6, 7, 9)
+
 # DUCKDB_TYPE_* element codes -> the canonical type tags of the test oracle's column blob
 _CANON_TYPE = {17: 1, 5: 2, 11: 3, 1: 4, 4: 5, 10: 6}
 ENC_PLAIN, ENC_CONTIG, ENC_DICT, ENC_SAMPLE, ENC_FLOAT_TEXT = 0, 1, 2, 3, 4
@@ -84,7 +91,8 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_bcf_rewind", "dhts_bcf_next_batch",
            "dhts_open_path_range", "dhts_open_path_shard", "dhts_bam_set_file_shard", "dhts_bam_header_bytes", "dhts_voffset",
            "dhts_host_alloc", "dhts_host_free", "dhts_release_pools", "dhts_device_mem_info", "dhts_shard_window", "dhts_bcf_build_index", "dhts_bgzf_wrap", "dhts_bgzf_compress", "dhts_bgzip_file", "dhts_bgunzip_file", "dhts_bcf_is_text", "dhts_bam_is_text", "dhts_bam_set_seq_packed", "dhts_bcf_header_bytes", "dhts_bcf_region_segments", "dhts_set_super_blocks", "dhts_bam_build_index_csi", "dhts_tabix_build_index", "dhts_bcf_batch_host_bytes", "dhts_bcf_batch_fetch", "dhts_resident_from_cache", "dhts_bam_region_segments", "dhts_open_path_segments", "dhts_open_path_async", "dhts_stage_wait", "dhts_bgzf_index_staged", "dhts_blocks_ahead", "dhts_bam_batch_host_bytes", "dhts_bam_batch_fetch", "dhts_bam_batch_fetch_begin", "dhts_bam_batch_fetch_wait", "dhts_bcf_batch_fetch_begin", "dhts_bcf_batch_fetch_wait", "dhts_device_numa_node", "dhts_bind_thread_to_node", "dhts_bind_thread_near_device", "dhts_bam_set_qual_packed",
-           "dhts_fasta_build_index", "dhts_fasta_index_bytes", "dhts_fasta_gzi_bytes", "dhts_fasta_load_index", "dhts_fasta_open_regions", "dhts_fasta_fetch", "dhts_fasta_batch_host_bytes", "dhts_fasta_batch_fetch"]
+           "dhts_fasta_build_index", "dhts_fasta_index_bytes", "dhts_fasta_gzi_bytes", "dhts_fasta_load_index", "dhts_fasta_open_regions", "dhts_fasta_fetch", "dhts_fasta_batch_host_bytes", "dhts_fasta_batch_fetch",
+           "dhts_bed_open", "dhts_bed_set_projection", "dhts_bed_set_region", "dhts_bed_load_index", "dhts_bed_region_segments", "dhts_bed_next_batch", "dhts_bed_batch_host_bytes", "dhts_bed_batch_fetch"]
 
 
 def lib():
@@ -156,6 +164,15 @@ def lib():
         L.dhts_fasta_batch_host_bytes.restype = C.c_uint64
         L.dhts_fasta_batch_host_bytes.argtypes = [C.POINTER(FastaBatch)]
         L.dhts_fasta_batch_fetch.argtypes = [C.c_void_p, C.POINTER(FastaBatch), C.c_void_p, C.c_uint64, C.POINTER(FastaBatch)]
+        L.dhts_bed_open.argtypes = [C.c_void_p]
+        L.dhts_bed_set_projection.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.dhts_bed_set_region.argtypes = [C.c_void_p, C.c_char_p]
+        L.dhts_bed_load_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.dhts_bed_region_segments.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.dhts_bed_next_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
+        L.dhts_bed_batch_host_bytes.restype = C.c_uint64
+        L.dhts_bed_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
+        L.dhts_bed_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
         _LIB = L
     return _LIB
 
@@ -682,6 +699,134 @@ class BcfScan:
                     c["cfixed"] = d2h(dc.child_fixed, cn, np.uint32).astype(np.uint64)
             cols.append(c)
         return {"n_rows": n, "status": int(b.status), "cols": cols}
+
+
+class BedIteratorError(DhtsError):
+    """the index does not know the region's sequence (the reference: "read_bed: failed to create region iterator")"""
+
+
+class BedScan:
+    """read_bed over one context (open + bgzf_index done): projection, region, batches as python columns."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        ctx._chk(ctx.L.dhts_bed_open(ctx.h))
+        self.projection = list(range(len(BED_COLUMNS)))
+        self.error = None
+
+    def set_projection(self, cols):
+        ids = [c if isinstance(c, int) else BED_COLUMNS.index(c) for c in cols]
+        arr = np.array(ids, np.int32)
+        self.ctx._chk(self.ctx.L.dhts_bed_set_projection(self.ctx.h, arr.ctypes.data, len(ids)))
+        self.projection = ids
+
+    def set_region(self, region):
+        self.ctx._chk(self.ctx.L.dhts_bed_set_region(self.ctx.h, region.encode() if region else None))
+
+    def load_index(self, index_bytes):
+        """False when the index does not know the region's sequence"""
+        buf = np.frombuffer(index_bytes, dtype=np.uint8)
+        return self.ctx._chk(self.ctx.L.dhts_bed_load_index(self.ctx.h, buf.ctypes.data, buf.nbytes)) == 0
+
+    def next_batch(self, max_blocks=0):
+        b = BedBatch()
+        self.ctx._chk(self.ctx.L.dhts_bed_next_batch(self.ctx.h, max_blocks, C.byref(b)))
+        if b.status < 0:
+            self.error = self.ctx.L.dhts_error(self.ctx.h).decode()
+        return b
+
+    def batch_columns(self, b):
+        """the projected columns of one batch through dhts_bed_batch_fetch: {name: int64 array + validity, or list of bytes / None}"""
+        n = int(b.n_rows)
+        need = int(self.ctx.L.dhts_bed_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        self.ctx._chk(self.ctx.L.dhts_bed_batch_fetch(self.ctx.h, C.byref(b), arena.ctypes.data, need, host))
+        base = arena.ctypes.data
+        out = {}
+        for i in range(b.n_cols):
+            hc = host[i]
+            name = BED_COLUMNS[hc.col]
+            if n == 0:
+                out[name] = []
+                continue
+            valid = arena[hc.valid - base: hc.valid - base + n]
+            if hc.col in BED_INT_COLUMNS:
+                vals = arena[hc.fixed - base: hc.fixed - base + 8 * n].view(np.int64)
+                out[name] = [int(vals[r]) if valid[r] else None for r in range(n)]
+            else:
+                off = arena[hc.off - base: hc.off - base + 4 * (n + 1)].view(np.uint32)
+                data = arena[hc.bytes - base: hc.bytes - base + int(hc.nbytes)].tobytes()
+                out[name] = [data[int(off[r]):int(off[r + 1])] if valid[r] else None for r in range(n)]
+        return out
+
+
+def _is_bgzf(path):
+    with open(path, "rb") as f:
+        h = f.read(18)
+    return len(h) == 18 and h[:4] == b"\x1f\x8b\x08\x04" and h[10:16] == b"\x06\x00BC\x02\x00"
+
+
+def read_bed(src, region=None, index_path=None, columns=None, device=0, max_blocks=0, stats=None):
+    """read_bed(path, region := ..., index_path := ...): {"n_rows", "status", "error", column: python list with None for NULL} for the
+    projected columns (default all 13, BED_COLUMNS).  src: a path (uncompressed, BGZF or plain gzip) or the file's bytes (no region).  A
+    region needs the tabix index (index_path, else src + ".tbi" / ".csi") and stages only the index windows; stats (a dict) receives
+    resident_bytes and n_batches.  A line with fewer than 3 fields ends the scan: the rows in front of it, status < 0 and the message in "error"."""
+    index = None
+    if region is not None:
+        if isinstance(src, (bytes, bytearray, memoryview, np.ndarray)):
+            raise DhtsError("read_bed: region queries require a tabix index")
+        cand = [index_path] if index_path else [os.fspath(src) + ".tbi", os.fspath(src) + ".csi"]
+        for p in cand:
+            if os.path.exists(p):
+                index = open(p, "rb").read()
+                break
+        if index is None:
+            raise DhtsError("read_bed: region queries require a tabix index")
+    ctx = Context(device)
+    try:
+        sparse = None
+        if index is not None and _is_bgzf(src):
+            ibuf = np.frombuffer(index, dtype=np.uint8)
+            beg, end, cnt = np.zeros(4096, np.uint64), np.zeros(4096, np.uint64), C.c_int64(0)
+            rc = ctx._chk(ctx.L.dhts_bed_region_segments(ctx.h, region.encode(), ibuf.ctypes.data, ibuf.nbytes, beg.ctypes.data, end.ctypes.data, 4096, C.byref(cnt)))
+            if rc == 1:
+                raise BedIteratorError("read_bed: failed to create region iterator")
+            if cnt.value >= 0:
+                sparse = (beg[:cnt.value].copy(), end[:cnt.value].copy())
+        if sparse is not None:
+            ctx.open_segments(src, 0, *sparse)
+        else:
+            ctx.open(src)
+        ctx.L.dhts_bgzf_index(ctx.h)                      # (fails on text that is not BGZF: dhts_bed_open reads that as text)
+        sc = BedScan(ctx)
+        if columns is not None:
+            sc.set_projection(columns)
+        if region is not None:
+            sc.set_region(region)
+            if not sc.load_index(index):
+                raise BedIteratorError("read_bed: failed to create region iterator")
+        names = [BED_COLUMNS[i] for i in sc.projection]
+        out = {"n_rows": 0, "status": 0, "error": None}
+        out.update({k: [] for k in names})
+        nb = 0
+        while True:
+            b = sc.next_batch(max_blocks)
+            nb += 1
+            if b.n_rows:
+                out["n_rows"] += int(b.n_rows)
+                for k, v in sc.batch_columns(b).items():
+                    out[k].extend(v)
+            out["status"] = int(b.status)
+            if b.status != 0:
+                break
+        out["error"] = sc.error
+        if stats is not None:
+            stats["resident_bytes"] = ctx.resident_bytes()
+            stats["n_batches"] = nb
+        return out
+    finally:
+        ctx.close()
 
 
 def c_strtof(tok: bytes):

@@ -9,6 +9,7 @@
 #include "bam_tile_rows.hip"
 #include "bcf_records.hip"
 #include "vcf_text.hip"
+#include "bed_text.hip"
 #include "sam_text.hip"
 #include "fastq_text.hip"
 #include "fasta_index.hip"
@@ -167,6 +168,14 @@ struct FastaState {
     DevBuf text; uint64_t text_len = 0; bool text_ready = false;
     DevBuf o_noff, o_soff, o_name, o_seq, rg;
 };
+// read_bed (bed_text.hip, dhts_bed_scan.inc): the projection, the region of a query, the delimiter table and the columns of the last batch
+struct BedState {
+    bool open = false; std::vector<int32_t> proj; std::vector<dhts_col> out;
+    int64_t lines_done = 0; int32_t status = 0;                   // lines in front of the next batch (the error's line number); the error the stream ended on
+    bool rg_active = false, rg_all = false, rg_pending = false; std::string rg_tok, rg_name; int64_t rg_beg = 0, rg_end = 0; TbxConf conf = {0, 0, 0, 0, 0, 0}; DevBuf rg_name_dev, tbx;
+    DevBuf cnt_nl, cnt_tab, base_nl, base_tab, line_off, tab_off, tab0, has_nul, lend, ntab, is_row, rank, row_line, ctr;
+    DevBuf ival[BED_N_INT], ivalid[BED_N_INT], slen[BED_N_STR], soff[BED_N_STR], svalid[BED_N_STR], sbytes[BED_N_STR];
+};
 struct dhts_ctx;
 static void stop_stager(dhts_ctx *c);
 struct dhts_ctx {
@@ -199,6 +208,8 @@ struct dhts_ctx {
     int64_t s_last_nrec = 0; uint64_t s_last_len = 0;     // records / bytes of the last SAM batch (dhts_debug_sam_records)
     int fastq = 0;                    // read_bam on raw reads (fastq_text.hip; sam_text is set as well): 1 FASTQ, 2 FASTA
     FastaState fa;
+    BedState bed;
+    bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
     DevBuf f_len, f_flag, f_psum, f_rank, f_mark, f_next, f_plus, f_exit, f_entry, f_stop, f_isstart, f_recrank, f_recline;
     DevBuf v_pos_hi;                   // VCF text: the high words of the batch's 0-based positions (BcfStream::pos_hi)
     DevBuf v_keep, v_endsv; uint64_t proj_gen = 1, keep_gen = 0; int32_t keep_none = 0, fmt_none = 0; bool keep_all = true, fmt_keep_all = true; DevBuf v_fkeep;   // VCF text: the INFO keys the projection reads (VcfArgs::info_keep)
@@ -302,6 +313,8 @@ static int fail(dhts_ctx *c, const char *fmt, ...) {
 }
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(c, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
 #define ENSURE(c, buf, n) do { if ((buf).ensure(n) != 0) return fail(c, "hipMalloc of %zu bytes failed", (size_t)(n)); } while (0)
+// shards and index building have no meaning on a context that dhts_bed_open prepared
+#define BED_REFUSE(c, what) do { if ((c) && (c)->bed.open) return fail(c, "%s is not supported on a BED context (read_bed scans BED text in file order)", what); } while (0)
 
 // ---- kernel timing with HIP events on the context's stream --------------------------------
 static hipEvent_t ev_get(dhts_ctx *c) {
@@ -419,7 +432,7 @@ static void stop_stager(dhts_ctx *c) {
 }
 static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
-    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false;
+    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->text_any = false; c->bed.open = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
@@ -471,6 +484,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_fastq_scan.inc"
 #include "dhts_fasta_index.inc"
 #include "dhts_bcf_scan.inc"
+#include "dhts_bed_scan.inc"
 #include "dhts_fetch.inc"
 
 }  // extern "C"

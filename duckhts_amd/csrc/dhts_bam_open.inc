@@ -221,6 +221,7 @@ int dhts_shard_cut(const uint64_t *coff, int64_t n_blocks, uint64_t comp_len, in
 }
 
 int dhts_bam_set_block_range(dhts_ctx *c, int64_t b0, int64_t b1, int speculative_start) {
+    BED_REFUSE(c, "a block range");
     if (!c || b0 < 0 || b1 < b0 || b1 > c->n_blocks) return -1;
     if (c->fastq && (b0 != 0 || b1 != c->n_blocks || speculative_start)) return fail(c, "read_bam: shards of FASTQ/FASTA text are not supported (%s)", FASTQ_SEQ_ONLY);
     if (c->sam_text && (b0 != 0 || b1 != c->n_blocks || speculative_start)) return fail(c, "read_bam: shards of SAM text are not supported (%s)", SAM_SEQ_ONLY);
@@ -366,6 +367,7 @@ uint64_t dhts_voffset(const dhts_ctx *c, uint64_t uoff) {
 
 int dhts_bam_set_shard(dhts_ctx *c, int rank, int world) {
     if (!c) return -1;
+    BED_REFUSE(c, "a shard");
     if (c->fastq && world > 1) return fail(c, "read_bam: shards of FASTQ/FASTA text are not supported (%s)", FASTQ_SEQ_ONLY);
     if (c->sam_text && world > 1) return fail(c, "read_bam: shards of SAM text are not supported (%s)", SAM_SEQ_ONLY);
     int64_t b0, b1;

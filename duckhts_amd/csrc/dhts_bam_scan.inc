@@ -149,6 +149,7 @@ static int batch_end(dhts_ctx *c, const Batch &B, uint64_t carry_start, bool rec
 // appearance and feeds hts_idx_push.  min_shift <= 0: TBI.  The context needs dhts_open_path + dhts_bgzf_index only.
 extern "C" int64_t dhts_tabix_build_index(dhts_ctx *c, int preset, int sc, int bc, int ec, int meta_char, int line_skip, int min_shift) {
     if (!c) return -1;
+    BED_REFUSE(c, "tabix_index");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n_blocks <= 0 || c->plain_text) return fail(c, "tabix_index: the file is not BGZF");
     if ((preset & 0xffff) == 2) return fail(c, "tabix_index: the vcf preset goes through dhts_bcf_build_index");

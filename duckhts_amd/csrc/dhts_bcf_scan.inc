@@ -185,6 +185,7 @@ int dhts_bcf_set_region(dhts_ctx *c, const char *region) {
 }
 
 int dhts_bcf_set_block_range(dhts_ctx *c, int64_t b0, int64_t b1, int speculative_start) {
+    BED_REFUSE(c, "a block range");
     if (!c || !c->bcf_open) return -1;
     if (b0 < 0 || b1 > c->n_blocks || b0 > b1) return fail(c, "bad block range");
     c->shard_b0 = b0; c->shard_b1 = b1; c->shard_rank = speculative_start ? 1 : 0; c->shard_world = 2;

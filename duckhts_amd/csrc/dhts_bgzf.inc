@@ -193,11 +193,11 @@ static int64_t index_impl(dhts_ctx *c, bool extend) {
             memset(head, 0, sizeof(head));
             nhead = text_len < sizeof(head) ? (size_t)text_len : sizeof(head);
             if (nhead) HIPCHK(c, hipMemcpy(head, c->gz_out.p, nhead, hipMemcpyDeviceToHost));
-            if (memcmp(head, "##fileformat=VCF", 16) != 0 && !sam_text_detect(head, nhead) && !fastq_text_detect(head, nhead) && !c->gz_any) return fail(c, "read_bcf: a plain-gzip file is read when it holds VCF text; this one does not (BAM / BCF inside plain gzip is not read by this build)");
+            if (memcmp(head, "##fileformat=VCF", 16) != 0 && !sam_text_detect(head, nhead) && !fastq_text_detect(head, nhead) && !c->gz_any && !c->text_any) return fail(c, "read_bcf: a plain-gzip file is read when it holds VCF text; this one does not (BAM / BCF inside plain gzip is not read by this build)");
         }
         // VCF text, SAM text (hts_detect_format: an @HD / @SQ / @RG / @PG / @CO line, or a first line whose columns look like SAM), FASTQ / FASTA
         const bool text_fmt = memcmp(head, "##fileformat=VCF", 16) == 0 || sam_text_detect(head, nhead) || fastq_text_detect(head, nhead);
-        if ((c->gz_plain && c->gz_any) || ((c->gz_plain || !(head[0] == 0x1f && head[1] == 0x8b)) && text_fmt)) {      // (gz_any: bgunzip wants the bytes, whatever they are)
+        if ((c->gz_plain && (c->gz_any || c->text_any)) || ((c->gz_plain || !(head[0] == 0x1f && head[1] == 0x8b)) && (text_fmt || c->text_any))) {      // (gz_any: bgunzip wants the bytes, whatever they are)
             const uint64_t P = 65280; const int64_t nb = (int64_t)((text_len + P - 1) / P);
             c->h_coff.resize(nb); c->h_clen.resize(nb); c->h_isize.resize(nb); c->h_uoff.resize(nb + 1);
             for (int64_t i = 0; i < nb; i++) { c->h_coff[i] = (uint64_t)i * P; c->h_uoff[i] = (uint64_t)i * P; const uint64_t l = text_len - (uint64_t)i * P < P ? text_len - (uint64_t)i * P : P; c->h_clen[i] = (uint32_t)l; c->h_isize[i] = (uint32_t)l; }

@@ -14,6 +14,7 @@ int64_t dhts_bam_build_index(dhts_ctx *c) { if (c && c->fastq) return fail(c, "b
 extern "C" int64_t dhts_bam_build_index_csi(dhts_ctx *c, int min_shift) { if (c && c->fastq) return fail(c, "bam_index: FASTQ/FASTA text cannot be indexed (%s)", FASTQ_SEQ_ONLY); if (c && c->sam_text) return fail(c, "bam_index: SAM text cannot be indexed here (%s)", SAM_SEQ_ONLY); return bam_build_index_impl(c, min_shift); }
 static int64_t bam_build_index_impl(dhts_ctx *c, int min_shift) {
     if (!c) return -1;
+    BED_REFUSE(c, "bam_index");
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->bam_open) return fail(c, "dhts_bam_open not called");
     if (c->rg_active || c->shard_b0 != 0 || c->shard_b1 != c->n_blocks || c->ov_active) return fail(c, "index build needs a whole-file scan (no region, shard or join)");
@@ -146,6 +147,7 @@ int dhts_bam_index_bytes(dhts_ctx *c, uint8_t *out, uint64_t cap) {
 // UNCOMPRESSED index; dhts_bgzf_wrap makes the .csi file of them.
 int64_t dhts_bcf_build_index(dhts_ctx *c, int min_shift) {
     if (!c) return -1;
+    BED_REFUSE(c, "bcf_index");
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->bcf_open) return fail(c, "dhts_bcf_open not called");
     if (c->vcf_text && c->plain_text) return fail(c, "index build: an uncompressed VCF cannot be indexed (tabix needs BGZF)");

@@ -1511,6 +1511,180 @@ extern "C" __attribute__((visibility("default"))) void register_read_fasta_funct
     API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
 }
 
+// ---- read_bed (src/interval_udf.c:217-426, 838-852): one thread, file order, vector_size rows per chunk -------------------------------------
+// bind checks the path and, for a region, that a tabix index can be read (tbx_index_load3: index_path, else <path>.tbi, <path>.csi); init
+// stages the file -- for a region only the index windows -- and resolves the region; the scan fills chunks from device batches read back
+// by dhts_bed_batch_fetch.  A line with fewer than 3 fields replaces the chunk it would have been in by read_bed's error.
+static const char *const kBedCols[DHTS_BED_COL_COUNT] = {"chrom", "start", "end", "name", "score", "strand", "thick_start", "thick_end", "item_rgb", "block_count", "block_sizes", "block_starts", "extra"};
+static inline bool bed_is_bigint(idx_t c) { return c == DHTS_BED_START || c == DHTS_BED_END || c == DHTS_BED_THICK_START || c == DHTS_BED_THICK_END || c == DHTS_BED_BLOCK_COUNT; }
+struct BedBind { std::string path, region; bool has_region = false; std::string index; };
+struct BedScanState {
+    dhts_ctx *ctx = nullptr; void *arena = nullptr; uint64_t arena_cap = 0;
+    std::vector<idx_t> column_ids; std::vector<int> slot;       // output column -> position in the projection (-1: none)
+    std::vector<dhts_col> host; int64_t n = 0, pos = 0; int32_t status = 0; bool done = false;
+    ~BedScanState() { if (arena) dhts_host_free(arena); if (ctx) dhts_destroy(ctx); }
+};
+static void destroy_bed_bind(void *p) { delete (BedBind *)p; }
+static void destroy_bed_scan(void *p) { delete (BedScanState *)p; }
+static bool read_file(const std::string &path, std::string &out) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    char buf[65536]; size_t n; out.clear();
+    while ((n = fread(buf, 1, sizeof(buf), f)) > 0) out.append(buf, n);
+    fclose(f);
+    return true;
+}
+static void bed_read_bind(duckdb_bind_info info) {
+    auto set_error = API(void, duckdb_bind_set_error, duckdb_bind_info, const char *);
+    auto dfree = API(void, duckdb_free, void *);
+    duckdb_value pv = API(duckdb_value, duckdb_bind_get_parameter, duckdb_bind_info, idx_t)(info, 0);
+    char *file_path = API(char *, duckdb_get_varchar, duckdb_value)(pv);
+    API(void, duckdb_destroy_value, duckdb_value *)(&pv);
+    if (!file_path || file_path[0] == '\0') { set_error(info, "read_bed requires a file path"); if (file_path) dfree(file_path); return; }   // interval_udf.c:242-246
+    BedBind *b = new BedBind();
+    b->path = file_path; dfree(file_path);
+    std::string index_path;
+    if (char *r = get_named_varchar(info, "region")) { b->region = r; b->has_region = true; dfree(r); }
+    if (char *x = get_named_varchar(info, "index_path")) { index_path = x; dfree(x); }
+    char err[768];
+    if (!file_exists(b->path)) { snprintf(err, sizeof(err), "read_bed: failed to open file: %s", b->path.c_str()); set_error(info, err); delete b; return; }   // :262-271
+    if (b->has_region) {                                          // :274-283
+        bool have = index_path.empty() ? (read_file(b->path + ".tbi", b->index) || read_file(b->path + ".csi", b->index)) : read_file(index_path, b->index);
+        if (have && b->index.size() < 4) have = false;
+        if (!have) { set_error(info, "read_bed: region queries require a tabix index"); delete b; return; }
+    }
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto add = API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR), t_bigint = mk(DUCKDB_TYPE_BIGINT);
+    for (idx_t c = 0; c < DHTS_BED_COL_COUNT; c++) add(info, kBedCols[c], bed_is_bigint(c) ? t_bigint : t_varchar);                            // :217-235
+    rm(&t_varchar); rm(&t_bigint);
+    API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, b, destroy_bed_bind);
+}
+static void bed_read_init(duckdb_init_info info) {
+    BedBind *bind = (BedBind *)API(void *, duckdb_init_get_bind_data, duckdb_init_info)(info);
+    auto init_error = API(void, duckdb_init_set_error, duckdb_init_info, const char *);
+    BedScanState *g = new BedScanState();
+    g->ctx = dhts_create(device_list()[0]);
+    if (!g->ctx) { init_error(info, "read_bed: no MI355X (gfx950) device available; this build has no CPU fallback"); delete g; return; }
+    bool staged = false;
+    if (bind->has_region) {
+        // a BGZF file is staged by the index: nothing but the windows of the region (BED text has no header)
+        uint8_t h[18] = {0}; size_t got = 0;
+        if (FILE *f = fopen(bind->path.c_str(), "rb")) { got = fread(h, 1, 18, f); fclose(f); }
+        const bool bgzf = got == 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C';
+        if (bgzf) {
+            uint64_t beg[4096], end[4096]; int64_t cnt = -1;
+            const int rc = dhts_bed_region_segments(g->ctx, bind->region.c_str(), bind->index.data(), bind->index.size(), beg, end, 4096, &cnt);
+            if (rc == 1) { init_error(info, "read_bed: failed to create region iterator"); delete g; return; }                             // :314-319
+            if (rc < 0) { init_error(info, "read_bed: failed to load tabix index"); delete g; return; }                                   // :308-313
+            if (cnt >= 0) {
+                if (dhts_open_path_segments(g->ctx, bind->path.c_str(), 0, beg, end, cnt) != 0) { init_error(info, "read_bed: failed to open file during init"); delete g; return; }
+                staged = true;
+            }
+        }
+    }
+    if (!staged && dhts_open_path(g->ctx, bind->path.c_str()) != 0) { init_error(info, "read_bed: failed to open file during init"); delete g; return; }   // :300-305
+    (void)dhts_bgzf_index(g->ctx);                               // (text that is not BGZF fails here and is taken as text by dhts_bed_open)
+    if (dhts_bed_open(g->ctx) != 0) { init_error(info, "read_bed: failed to open file during init"); delete g; return; }
+    const idx_t n = API(idx_t, duckdb_init_get_column_count, duckdb_init_info)(info);
+    std::vector<int32_t> proj;
+    for (idx_t i = 0; i < n; i++) {
+        const idx_t id = API(idx_t, duckdb_init_get_column_index, duckdb_init_info, idx_t)(info, i);
+        g->column_ids.push_back(id);
+        int at = -1;
+        if (id < DHTS_BED_COL_COUNT) {
+            for (size_t k = 0; k < proj.size(); k++) if (proj[k] == (int32_t)id) at = (int)k;
+            if (at < 0) { at = (int)proj.size(); proj.push_back((int32_t)id); }
+        }
+        g->slot.push_back(at);
+    }
+    if (dhts_bed_set_projection(g->ctx, proj.data(), (int32_t)proj.size()) != 0) { init_error(info, dhts_error(g->ctx)); delete g; return; }
+    if (bind->has_region) {
+        if (dhts_bed_set_region(g->ctx, bind->region.c_str()) != 0) { const std::string m = dhts_error(g->ctx); init_error(info, m.c_str()); delete g; return; }
+        const int rc = dhts_bed_load_index(g->ctx, bind->index.data(), bind->index.size());
+        if (rc == 1) { init_error(info, "read_bed: failed to create region iterator"); delete g; return; }
+        if (rc < 0) { init_error(info, "read_bed: failed to load tabix index"); delete g; return; }
+    }
+    g->host.resize(proj.size() ? proj.size() : 1);
+    API(void, duckdb_init_set_max_threads, duckdb_init_info, idx_t)(info, 1);
+    API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, g, destroy_bed_scan);
+}
+// the next device batch, read back; false at the end of the stream (g->status says how it ended) or on a failure (err set)
+static bool bed_next(BedScanState *g, std::string &err) {
+    while (g->status == 0) {
+        dhts_bed_batch b;
+        if (dhts_bed_next_batch(g->ctx, 0, &b) != 0) { err = dhts_error(g->ctx); return false; }
+        g->status = b.status;
+        if (b.n_rows == 0) continue;
+        const uint64_t need = dhts_bed_batch_host_bytes(&b);
+        if (need > g->arena_cap) { if (g->arena) dhts_host_free(g->arena); g->arena_cap = need + need / 4 + 4096; g->arena = dhts_host_alloc(g->arena_cap); if (!g->arena) { g->arena_cap = 0; err = "read_bed: out of pinned host memory"; return false; } }
+        if (dhts_bed_batch_fetch(g->ctx, &b, g->arena, g->arena_cap, g->host.data()) != 0) { err = dhts_error(g->ctx); return false; }
+        g->n = b.n_rows; g->pos = 0;
+        return true;
+    }
+    return false;
+}
+static void bed_read_function(duckdb_function_info info, duckdb_data_chunk output) {
+    BedScanState *g = (BedScanState *)API(void *, duckdb_function_get_init_data, duckdb_function_info)(info);
+    auto set_size = API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t);
+    if (!g || g->done) { set_size(output, 0); return; }
+    const idx_t vector_size = API(idx_t, duckdb_vector_size, void)();
+    auto get_vec = API(duckdb_vector, duckdb_data_chunk_get_vector, duckdb_data_chunk, idx_t);
+    auto assign_len = API(void, duckdb_vector_assign_string_element_len, duckdb_vector, idx_t, const char *, idx_t);
+    auto get_data = API(void *, duckdb_vector_get_data, duckdb_vector);
+    auto fail_scan = [&](const char *msg) { API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, msg); g->done = true; set_size(output, 0); };
+    idx_t row_count = 0;
+    while (row_count < vector_size) {
+        if (g->pos >= g->n) {
+            std::string err;
+            if (!bed_next(g, err)) {
+                if (!err.empty()) { fail_scan(err.c_str()); return; }
+                g->done = true;
+                // the short line would have been a row of this chunk: the chunk is the error (interval_udf.c:358-365); any other end of the
+                // stream ends the scan as a failed hts_getline does (:334-337)
+                if (g->status < 0 && strstr(dhts_error(g->ctx), "fewer than 3 tab-delimited fields")) { fail_scan("read_bed: BED line has fewer than 3 tab-delimited fields"); return; }
+                break;
+            }
+        }
+        const idx_t take = (idx_t)(g->n - g->pos) < vector_size - row_count ? (idx_t)(g->n - g->pos) : vector_size - row_count;
+        for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
+            duckdb_vector vec = get_vec(output, ci);
+            if (g->slot[ci] < 0) { for (idx_t r = 0; r < take; r++) set_null(vec, row_count + r); continue; }
+            const dhts_col &hc = g->host[(size_t)g->slot[ci]];
+            if (bed_is_bigint(g->column_ids[ci])) {
+                int64_t *data = (int64_t *)get_data(vec); const int64_t *src = (const int64_t *)hc.fixed;
+                for (idx_t r = 0; r < take; r++) { if (hc.valid[g->pos + r]) data[row_count + r] = src[g->pos + r]; else set_null(vec, row_count + r); }
+            } else {
+                for (idx_t r = 0; r < take; r++) {
+                    const int64_t k = g->pos + (int64_t)r;
+                    if (hc.valid[k]) assign_len(vec, row_count + r, (const char *)hc.bytes + hc.off[k], hc.off[k + 1] - hc.off[k]); else set_null(vec, row_count + r);
+                }
+            }
+        }
+        g->pos += (int64_t)take; row_count += take;
+    }
+    set_size(output, row_count);
+}
+extern "C" __attribute__((visibility("default"))) void register_read_bed_function(duckdb_connection connection) {                      // interval_udf.c:838-852
+    duckdb_table_function tf = API(duckdb_table_function, duckdb_create_table_function, void)();
+    API(void, duckdb_table_function_set_name, duckdb_table_function, const char *)(tf, "read_bed");
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    auto named = API(void, duckdb_table_function_add_named_parameter, duckdb_table_function, const char *, duckdb_logical_type);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR);
+    API(void, duckdb_table_function_add_parameter, duckdb_table_function, duckdb_logical_type)(tf, t_varchar);
+    named(tf, "region", t_varchar);
+    named(tf, "index_path", t_varchar);
+    rm(&t_varchar);
+    API(void, duckdb_table_function_set_bind, duckdb_table_function, duckdb_table_function_bind_t)(tf, bed_read_bind);
+    API(void, duckdb_table_function_set_init, duckdb_table_function, duckdb_table_function_init_t)(tf, bed_read_init);
+    API(void, duckdb_table_function_set_function, duckdb_table_function, duckdb_table_function_t)(tf, bed_read_function);
+    API(void, duckdb_table_function_supports_projection_pushdown, duckdb_table_function, bool)(tf, true);
+    API(duckdb_state, duckdb_register_table_function, duckdb_connection, duckdb_table_function)(connection, tf);
+    API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
+}
+
 extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(duckdb_extension_info info, struct duckdb_extension_access *access) {
     // duckdb_extension.h:1151-1158,1182-1194: fetch the API table, connect, register, disconnect
     const void *api = access->get_api(info, DUCKHTS_API_VERSION);
@@ -1529,6 +1703,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     // read_fastq (src/duckhts.c registers it between the readers) is opt-in until the registered set is widened: DHTS_SEQ_FUNCTIONS=1
     // read_fasta and fasta_index are opt-in with it, in the reference's order (src/duckhts.c:56-58): read_fasta, read_fastq, fasta_index
     if (const char *e = getenv("DHTS_SEQ_FUNCTIONS")) if (atoi(e) == 1) { register_read_fasta_function(conn); register_read_fastq_function(conn); register_fasta_index_function(conn); }
+    // read_bed follows fasta_index (src/duckhts.c:59), opt-in as well: DHTS_INTERVAL_FUNCTIONS=1
+    if (const char *e = getenv("DHTS_INTERVAL_FUNCTIONS")) if (atoi(e) == 1) register_read_bed_function(conn);
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);
     return true;
 }

@@ -127,7 +127,9 @@ typedef struct {
     uint64_t first_rec_uoff;       /* inflated offset of the first alignment record              */
 } dhts_bam_header;
 
-/* kernel ids for dhts_kernel_time (a read_bam scan of SAM text times its encoder's measure / write passes as DHTS_K_BCF_MEASURE / _WRITE) */
+/* kernel ids for dhts_kernel_time (a read_bam scan of SAM text times its encoder's measure / write passes as DHTS_K_BCF_MEASURE / _WRITE;
+ * read_bed: DHTS_K_TILES the delimiter table, _CORE the line classes, _SCAN the scans, _BCF_CHECK the BIGINT columns, _BCF_MEASURE / _WRITE
+ * the lengths and the bytes of the VARCHAR columns) */
 enum { DHTS_K_SIGSCAN = 0, DHTS_K_HUFF, DHTS_K_LZ, DHTS_K_TILES, DHTS_K_CORE, DHTS_K_SCAN, DHTS_K_STRINGS,
        DHTS_K_BCF_CHECK, DHTS_K_BCF_MEASURE, DHTS_K_BCF_WRITE, DHTS_K_COUNT };
 
@@ -408,6 +410,42 @@ int dhts_fasta_fetch(dhts_ctx *, const char *regions, dhts_fasta_batch *out);
 /* read-back in the style of dhts_bam_batch_fetch: `out` = `b` with HOST pointers into dst */
 uint64_t dhts_fasta_batch_host_bytes(const dhts_fasta_batch *b);
 int dhts_fasta_batch_fetch(dhts_ctx *, const dhts_fasta_batch *b, void *dst, uint64_t cap, dhts_fasta_batch *out);
+
+/* ---- read_bed --------------------------------------------------------------------------------
+ *   dhts_bed_open / dhts_bed_next_batch  <- read_bed_init / read_bed_scan over next_bed_line          src/interval_udf.c:295-426
+ *                                           (hts_getline or tbx_itr_next; is_meta_bed_line, count_tab_fields, get_field_span,
+ *                                           get_extra_span, parse_int64_span_local :127-195)
+ * The 13 columns of src/interval_udf.c:217-235, in that order.  BIGINT: start, end, thick_start, thick_end, block_count (strtoll over the
+ * whole field, else NULL); VARCHAR: the others, NULL when the field is absent or empty; extra = everything behind the 12th tab. */
+enum { DHTS_BED_CHROM = 0, DHTS_BED_START, DHTS_BED_END, DHTS_BED_NAME, DHTS_BED_SCORE, DHTS_BED_STRAND, DHTS_BED_THICK_START, DHTS_BED_THICK_END,
+       DHTS_BED_ITEM_RGB, DHTS_BED_BLOCK_COUNT, DHTS_BED_BLOCK_SIZES, DHTS_BED_BLOCK_STARTS, DHTS_BED_EXTRA, DHTS_BED_COL_COUNT };
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more data may follow, 1 = end of stream reached cleanly, <0 = the stream ended on an error after these rows
+                                (a line with fewer than 3 fields: dhts_error has read_bed's message and the line number)                   */
+    int32_t n_cols;          /* projected columns, in projection order                                                                     */
+    const dhts_col *cols;    /* host array of n_cols descriptors, DEVICE pointers inside: valid[n_rows]; BIGINT in fixed (8 bytes, 0 where
+                                NULL), VARCHAR in off[n_rows + 1] / bytes (one arena per column)                                           */
+} dhts_bed_batch;
+/* after dhts_open_path* / dhts_open_host and dhts_bgzf_index (whose result does not matter here): BGZF, plain gzip and uncompressed text
+ * are read, whatever the text looks like (hts_getline has no format).  Shards and index building fail on such a context. */
+int dhts_bed_open(dhts_ctx *);
+int dhts_bed_set_projection(dhts_ctx *, const int32_t *col_ids, int32_t n);   /* DHTS_BED_* ids, each once; default all 13; n = 0: only n_rows (count(*)) */
+/* ONE region as tbx_itr_querys takes it ("seq", "seq:1,000-2,000": commas are thousands separators, not a list; "." = every record; NULL /
+ * "" clears).  The name is one of the INDEX's sequences: dhts_bed_load_index (.tbi, or .csi with the tabix header) resolves it -- 0, 1 = the
+ * index does not know it (the reference: "failed to create region iterator"), <0 error -- and narrows the scan to the index windows.  Rows
+ * are kept by hts_itr_next's test on the interval tbx_parse1 gives the line under the index's OWN configuration (preset, columns), not by
+ * the BED columns.  Fails on uncompressed or plain-gzip text. */
+int dhts_bed_set_region(dhts_ctx *, const char *region);
+int dhts_bed_load_index(dhts_ctx *, const void *index_bytes, uint64_t n);
+/* what a region query stages instead of the file, for dhts_open_path_segments with header_bytes = 0 (BED has no header; conventions of
+ * dhts_bam_region_segments, *count = -1: the whole file).  Needs no open file.  Returns 1 when the index does not know the sequence. */
+int dhts_bed_region_segments(dhts_ctx *, const char *region, const void *index_bytes, uint64_t n, uint64_t *beg, uint64_t *end, int64_t cap, int64_t *count);
+/* next batch of rows (<= max_blocks BGZF blocks, or 65,280-byte pieces of text; 0 = default); lines open at the end are carried over */
+int dhts_bed_next_batch(dhts_ctx *, int64_t max_blocks, dhts_bed_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst */
+uint64_t dhts_bed_batch_host_bytes(const dhts_bed_batch *b);
+int dhts_bed_batch_fetch(dhts_ctx *, const dhts_bed_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
 /* ---- utilities ------------------------------------------------------------------------------ */
 int dhts_memcpy_d2h(dhts_ctx *, void *dst, const void *src_dev, uint64_t n);

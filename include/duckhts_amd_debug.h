@@ -22,6 +22,10 @@ int64_t dhts_debug_vcf_records(dhts_ctx *, uint8_t *dst, uint64_t cap, uint32_t 
 int64_t dhts_debug_sam_records(dhts_ctx *, uint8_t *dst, uint64_t cap, int64_t *nrec);
 /* tests: the same for the last FASTQ / FASTA batch (the encoders share the buffer); -1 when the context is not reading FASTQ / FASTA */
 int64_t dhts_debug_fastq_records(dhts_ctx *, uint8_t *dst, uint64_t cap, int64_t *nrec);
+/* tools/bench_bed.py: the lane-per-line walk read_bed's delimiter table is measured against, over the whole text of a BED context: device
+ * milliseconds of the line table (vcf_line_count / vcf_line_fill) and of bed_intervals (chrom / start / end by walking every line);
+ * returns the number of lines */
+int64_t dhts_debug_bed_walk(dhts_ctx *, double *ms_line_table, double *ms_walk);
 /* tools/dbg: phase A (kernel 0: lane per block, 1: wave per block) / phase B alone over blocks [b0, b0 + nb); ms per launch */
 double dhts_debug_time_huff(dhts_ctx *, int64_t b0, int64_t nb, int reps);
 double dhts_debug_time_lz(dhts_ctx *, int64_t b0, int64_t nb, int reps);

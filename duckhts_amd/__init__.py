@@ -76,6 +76,32 @@ class BedBatch(C.Structure):
     _fields_ = [("n_rows", C.c_int64), ("status", C.c_int32), ("n_cols", C.c_int32), ("cols", C.POINTER(BcfCol))]
 
 
+class TabixMap(C.Structure):
+    _fields_ = [("pair_off", C.c_void_p), ("valid", C.c_void_p), ("n_pairs", C.c_uint64), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p), ("key_nbytes", C.c_uint64),
+                ("val_off", C.c_void_p), ("val_bytes", C.c_void_p), ("val_nbytes", C.c_uint64)]
+
+
+class TabixBatch(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("status", C.c_int32), ("n_cols", C.c_int32), ("cols", C.POINTER(BcfCol)), ("col_types", C.POINTER(C.c_int32)),
+                ("has_map", C.c_int32), ("reserved", C.c_int32), ("map", TabixMap), ("n_double_fast", C.c_uint64), ("n_double_patched", C.c_uint64)]
+
+
+class TabixSniffed(C.Structure):
+    _fields_ = [("n_fields", C.c_int32), ("have_candidate", C.c_int32), ("candidate_from_skip", C.c_int32), ("reserved", C.c_int32),
+                ("candidate", C.c_void_p), ("candidate_len", C.c_uint64)]
+
+
+TABIX_MAX_COLS = 256
+
+
+class TabixSchema(C.Structure):
+    _fields_ = [("n_cols", C.c_int32), ("skip_header_line", C.c_int32), ("types", C.c_int32 * TABIX_MAX_COLS), ("names", C.c_char_p * TABIX_MAX_COLS)]
+
+
+TABIX_GENERIC, TABIX_GTF, TABIX_GFF = 0, 1, 2
+T_INTEGER, T_BIGINT, T_DOUBLE, T_VARCHAR = 4, 5, 11, 17
+GXF_COLUMNS = ["seqname", "source", "feature", "start", "end", "score", "strand", "frame", "attributes", "attributes_map"]
+GXF_TYPES = [T_VARCHAR, T_VARCHAR, T_VARCHAR, T_BIGINT, T_BIGINT, T_DOUBLE, T_VARCHAR, T_VARCHAR, T_VARCHAR]
 BED_COLUMNS = ["chrom", "start", "end", "name", "score", "strand", "thick_start", "thick_end", "item_rgb", "block_count", "block_sizes", "block_starts", "extra"]
 BED_INT_COLUMNS = (1, 2, 6, 7, 9)
 
@@ -92,7 +118,9 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_open_path_range", "dhts_open_path_shard", "dhts_bam_set_file_shard", "dhts_bam_header_bytes", "dhts_voffset",
            "dhts_host_alloc", "dhts_host_free", "dhts_release_pools", "dhts_device_mem_info", "dhts_shard_window", "dhts_bcf_build_index", "dhts_bgzf_wrap", "dhts_bgzf_compress", "dhts_bgzip_file", "dhts_bgunzip_file", "dhts_bcf_is_text", "dhts_bam_is_text", "dhts_bam_set_seq_packed", "dhts_bcf_header_bytes", "dhts_bcf_region_segments", "dhts_set_super_blocks", "dhts_bam_build_index_csi", "dhts_tabix_build_index", "dhts_bcf_batch_host_bytes", "dhts_bcf_batch_fetch", "dhts_resident_from_cache", "dhts_bam_region_segments", "dhts_open_path_segments", "dhts_open_path_async", "dhts_stage_wait", "dhts_bgzf_index_staged", "dhts_blocks_ahead", "dhts_bam_batch_host_bytes", "dhts_bam_batch_fetch", "dhts_bam_batch_fetch_begin", "dhts_bam_batch_fetch_wait", "dhts_bcf_batch_fetch_begin", "dhts_bcf_batch_fetch_wait", "dhts_device_numa_node", "dhts_bind_thread_to_node", "dhts_bind_thread_near_device", "dhts_bam_set_qual_packed",
            "dhts_fasta_build_index", "dhts_fasta_index_bytes", "dhts_fasta_gzi_bytes", "dhts_fasta_load_index", "dhts_fasta_open_regions", "dhts_fasta_fetch", "dhts_fasta_batch_host_bytes", "dhts_fasta_batch_fetch",
-           "dhts_bed_open", "dhts_bed_set_projection", "dhts_bed_set_region", "dhts_bed_load_index", "dhts_bed_region_segments", "dhts_bed_next_batch", "dhts_bed_batch_host_bytes", "dhts_bed_batch_fetch"]
+           "dhts_bed_open", "dhts_bed_set_projection", "dhts_bed_set_region", "dhts_bed_load_index", "dhts_bed_region_segments", "dhts_bed_next_batch", "dhts_bed_batch_host_bytes", "dhts_bed_batch_fetch",
+           "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
+           "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch"]
 
 
 def lib():
@@ -173,6 +201,21 @@ def lib():
         L.dhts_bed_batch_host_bytes.restype = C.c_uint64
         L.dhts_bed_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_bed_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_tabix_open.argtypes = [C.c_void_p, C.c_int]
+        L.dhts_tabix_set_conf.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.dhts_tabix_index_conf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.dhts_tabix_sniff.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(TabixSniffed)]
+        L.dhts_tabix_resolve_schema.argtypes = [C.POINTER(TabixSniffed), C.c_int, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int,
+                                                C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.POINTER(TabixSchema), C.c_char_p, C.c_uint64]
+        L.dhts_tabix_set_schema.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int]
+        L.dhts_tabix_set_projection.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.dhts_tabix_set_region.argtypes = [C.c_void_p, C.c_char_p]
+        L.dhts_tabix_load_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.dhts_tabix_region_segments.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.dhts_tabix_next_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(TabixBatch)]
+        L.dhts_tabix_batch_host_bytes.restype = C.c_uint64
+        L.dhts_tabix_batch_host_bytes.argtypes = [C.POINTER(TabixBatch)]
+        L.dhts_tabix_batch_fetch.argtypes = [C.c_void_p, C.POINTER(TabixBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol), C.POINTER(TabixMap)]
         _LIB = L
     return _LIB
 
@@ -827,6 +870,247 @@ def read_bed(src, region=None, index_path=None, columns=None, device=0, max_bloc
         return out
     finally:
         ctx.close()
+
+
+def tabix_parse_regions(region):
+    """parse_regions (src/tabix_reader.c:301-344): comma-separated, trimmed of blanks and tabs, empty tokens dropped"""
+    if not region:
+        return []
+    return [t.strip(" \t") for t in region.split(",") if t.strip(" \t")]
+
+
+def tabix_resolve_schema(sniffed, header=False, header_names=None, column_types=None, auto_detect=False, rows=None):
+    """dhts_tabix_resolve_schema (no device): {"n_cols", "names", "types", "skip_header_line", "need_rows"}.  sniffed: a TabixSniffed, or
+    (n_fields, candidate bytes or None, candidate_from_skip).  rows: for auto_detect, lists of n_cols cells (bytes or None)."""
+    L = lib()
+    if not isinstance(sniffed, TabixSniffed):
+        n_fields, cand, from_skip = sniffed
+        keep = C.create_string_buffer(cand, len(cand)) if cand is not None else None
+        sniffed = TabixSniffed(n_fields, 1 if cand is not None else 0, 1 if from_skip else 0, 0, C.addressof(keep) if keep is not None else None, len(cand) if cand is not None else 0)
+        sniffed._keep = keep
+
+    def strs(xs):
+        if not xs:
+            return None, 0
+        return (C.c_char_p * len(xs))(*[x.encode() if isinstance(x, str) else x for x in xs]), len(xs)
+    hn, n_hn = strs(header_names)
+    ct, n_ct = strs(column_types)
+    out, err = TabixSchema(), C.create_string_buffer(256)
+    cells = lens = None
+    n_rows = 0
+    if rows is not None:
+        flat = [c for r in rows for c in r]
+        bufs = [C.create_string_buffer(c, len(c)) if c is not None else None for c in flat]
+        cells = (C.c_char_p * max(len(flat), 1))(*[C.cast(b, C.c_char_p) if b is not None else None for b in bufs])
+        lens = np.array([len(c) if c is not None else 0 for c in flat] + [0], np.uint32)
+        n_rows = len(rows)
+    rc = L.dhts_tabix_resolve_schema(C.byref(sniffed), 1 if header else 0, hn, n_hn, ct, n_ct, 1 if auto_detect else 0,
+                                     cells, lens.ctypes.data if lens is not None else None, n_rows, C.byref(out), err, 256)
+    if rc < 0:
+        raise DhtsError(err.value.decode() or "dhts_tabix_resolve_schema failed")
+    n = out.n_cols
+    return {"n_cols": n, "names": [out.names[i].decode() for i in range(n)], "types": [int(out.types[i]) for i in range(n)],
+            "skip_header_line": bool(out.skip_header_line), "need_rows": rc == 1}
+
+
+class TabixScan:
+    """read_tabix / read_gtf / read_gff over one context (open + bgzf_index done): bind, projection, region, batches as python columns."""
+
+    def __init__(self, ctx, mode=TABIX_GENERIC):
+        self.ctx, self.mode = ctx, mode
+        ctx._chk(ctx.L.dhts_tabix_open(ctx.h, mode))
+        gxf = mode != TABIX_GENERIC
+        self.names = GXF_COLUMNS[:9] if gxf else ["column0"]
+        self.types = list(GXF_TYPES) if gxf else [T_VARCHAR]
+        self.projection = list(range(len(self.names)))
+        self.n_double_fast = self.n_double_patched = 0
+
+    def set_conf(self, meta_char, line_skip):
+        self.ctx._chk(self.ctx.L.dhts_tabix_set_conf(self.ctx.h, meta_char, line_skip))
+
+    def index_conf(self, index_bytes):
+        buf = np.frombuffer(index_bytes, dtype=np.uint8)
+        m, s = C.c_int32(0), C.c_int32(0)
+        self.ctx._chk(self.ctx.L.dhts_tabix_index_conf(self.ctx.h, buf.ctypes.data, buf.nbytes, C.byref(m), C.byref(s)))
+        return m.value, s.value
+
+    def sniff(self, header=False, have_header_names=False):
+        sn = TabixSniffed()
+        self.ctx._chk(self.ctx.L.dhts_tabix_sniff(self.ctx.h, 1 if header else 0, 1 if have_header_names else 0, C.byref(sn)))
+        cand = C.string_at(sn.candidate, sn.candidate_len) if sn.have_candidate else None
+        return sn.n_fields, cand, bool(sn.candidate_from_skip)
+
+    def set_schema(self, types, skip_header_line=False, names=None):
+        arr = np.array(types, np.int32)
+        self.ctx._chk(self.ctx.L.dhts_tabix_set_schema(self.ctx.h, len(types), arr.ctypes.data, 1 if skip_header_line else 0))
+        self.types = list(types)
+        self.names = list(names) if names else ["column%d" % i for i in range(len(types))]
+        self.projection = list(range(len(types)))
+
+    def bind(self, header=False, header_names=None, column_types=None, auto_detect=False, max_blocks=0):
+        """generic bind (src/tabix_reader.c:658-771): the peek, the schema rules and, for auto_detect, the first 100 rows; returns the schema"""
+        sn = self.sniff(header, bool(header_names))
+        sch = tabix_resolve_schema(sn, header, header_names, column_types, auto_detect)
+        if sch["need_rows"]:
+            self.set_schema(sch["types"], sch["skip_header_line"])
+            rows = []
+            while len(rows) < 100:
+                b = self.next_batch(max_blocks or 64)
+                cols = self.batch_columns(b) if b.n_rows else {}
+                for r in range(int(b.n_rows)):
+                    rows.append([cols["column%d" % i][r] for i in range(sch["n_cols"])])
+                if b.status != 0:
+                    break
+            self.set_region(None)                                            # rewinds
+            sch = tabix_resolve_schema(sn, header, header_names, column_types, auto_detect, rows[:100])
+        self.set_schema(sch["types"], sch["skip_header_line"], sch["names"])
+        return sch
+
+    def set_projection(self, cols):
+        allnames = GXF_COLUMNS if self.mode != TABIX_GENERIC else self.names
+        ids = [c if isinstance(c, int) else allnames.index(c) for c in cols]
+        arr = np.array(ids + [0], np.int32)
+        self.ctx._chk(self.ctx.L.dhts_tabix_set_projection(self.ctx.h, arr.ctypes.data, len(ids)))
+        self.projection = ids
+
+    def set_region(self, region):
+        self.ctx._chk(self.ctx.L.dhts_tabix_set_region(self.ctx.h, region.encode() if region else None))
+
+    def load_index(self, index_bytes):
+        """False when the index does not know the region's sequence"""
+        buf = np.frombuffer(index_bytes, dtype=np.uint8)
+        return self.ctx._chk(self.ctx.L.dhts_tabix_load_index(self.ctx.h, buf.ctypes.data, buf.nbytes)) == 0
+
+    def next_batch(self, max_blocks=0):
+        b = TabixBatch()
+        self.ctx._chk(self.ctx.L.dhts_tabix_next_batch(self.ctx.h, max_blocks, C.byref(b)))
+        self.n_double_fast += int(b.n_double_fast)
+        self.n_double_patched += int(b.n_double_patched)
+        return b
+
+    def col_name(self, cid):
+        return GXF_COLUMNS[cid] if self.mode != TABIX_GENERIC else self.names[cid]
+
+    def batch_columns(self, b):
+        """the projected columns of one batch through dhts_tabix_batch_fetch: {name: list of int / float (float64) / bytes / None; the map
+        column: list of [(key, value), ...] / None}"""
+        n = int(b.n_rows)
+        need = int(self.ctx.L.dhts_tabix_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        hmap = TabixMap()
+        self.ctx._chk(self.ctx.L.dhts_tabix_batch_fetch(self.ctx.h, C.byref(b), arena.ctypes.data, need, host, C.byref(hmap)))
+        base = arena.ctypes.data
+
+        def view(ptr, nbytes, dt=np.uint8):
+            return arena[ptr - base: ptr - base + nbytes].view(dt) if nbytes else np.zeros(0, dt)
+        out = {}
+        for i in range(b.n_cols):
+            hc, ty = host[i], int(b.col_types[i])
+            name = self.col_name(hc.col)
+            if n == 0:
+                out[name] = []
+            elif ty == 0:
+                po, valid = view(hmap.pair_off, 4 * (n + 1), np.uint32), view(hmap.valid, n)
+                npairs = int(hmap.n_pairs)
+                ko, vo = view(hmap.key_off, 4 * (npairs + 1), np.uint32), view(hmap.val_off, 4 * (npairs + 1), np.uint32)
+                kb, vb = view(hmap.key_bytes, int(hmap.key_nbytes)).tobytes(), view(hmap.val_bytes, int(hmap.val_nbytes)).tobytes()
+                out[name] = [[(kb[int(ko[p]):int(ko[p + 1])], vb[int(vo[p]):int(vo[p + 1])]) for p in range(int(po[r]), int(po[r + 1]))] if valid[r] else None for r in range(n)]
+            else:
+                valid = view(hc.valid, n)
+                if ty == T_VARCHAR:
+                    off = view(hc.off, 4 * (n + 1), np.uint32)
+                    data = view(hc.bytes, int(hc.nbytes)).tobytes()
+                    out[name] = [data[int(off[r]):int(off[r + 1])] if valid[r] else None for r in range(n)]
+                elif ty == T_DOUBLE:
+                    vals = view(hc.fixed, 8 * n, np.float64)
+                    out[name] = [vals[r] if valid[r] else None for r in range(n)]
+                else:
+                    vals = view(hc.fixed, 8 * n, np.int64)
+                    out[name] = [int(vals[r]) if valid[r] else None for r in range(n)]
+        return out
+
+
+def _read_tabix_mode(mode, who, src, region, index_path, header, header_names, column_types, auto_detect, columns, attributes_map, device, max_blocks, stats):
+    is_bytes = isinstance(src, (bytes, bytearray, memoryview, np.ndarray))
+    index = None
+    if not is_bytes:
+        for p in ([index_path] if index_path else [os.fspath(src) + ".tbi", os.fspath(src) + ".csi"]):   # tbx_index_load2
+            if os.path.exists(p):
+                index = open(p, "rb").read()
+                break
+    regions = tabix_parse_regions(region)
+    if regions and index is None:
+        raise DhtsError("Region query requested but no tabix index found for: %s" % ("<bytes>" if is_bytes else os.fspath(src)))
+    ctx = Context(device)
+    try:
+        sparse = None
+        if len(regions) == 1 and not is_bytes and _is_bgzf(src):                               # one region: only its index windows are staged
+            ibuf = np.frombuffer(index, dtype=np.uint8)
+            beg, end, cnt = np.zeros(4096, np.uint64), np.zeros(4096, np.uint64), C.c_int64(0)
+            rc = ctx._chk(ctx.L.dhts_tabix_region_segments(ctx.h, regions[0].encode(), ibuf.ctypes.data, ibuf.nbytes, beg.ctypes.data, end.ctypes.data, 4096, C.byref(cnt)))
+            if rc == 0 and cnt.value >= 0 and mode != TABIX_GENERIC:          # (generic bind peeks at the head of the file)
+                sparse = (beg[:cnt.value].copy(), end[:cnt.value].copy())
+        if sparse is not None:
+            ctx.open_segments(src, 0, *sparse)
+        else:
+            ctx.open(src)
+        ctx.L.dhts_bgzf_index(ctx.h)
+        sc = TabixScan(ctx, mode)
+        if mode == TABIX_GENERIC:
+            if index is not None:
+                meta, skip = sc.index_conf(index)
+                sc.set_conf(meta if meta else ord("#"), skip)
+            schema = sc.bind(header, header_names, column_types, auto_detect, max_blocks)
+            names, types = schema["names"], schema["types"]
+        else:
+            names, types = GXF_COLUMNS[:9] + (["attributes_map"] if attributes_map else []), GXF_TYPES + ([0] if attributes_map else [])
+            if attributes_map:
+                sc.set_projection(list(range(10)))
+        if columns is not None:
+            sc.set_projection(columns)
+        pnames = [sc.col_name(i) for i in sc.projection]
+        out = {"n_rows": 0, "status": 1, "names": names, "types": types}
+        out.update({k: [] for k in pnames})
+        nb = 0
+        for rg in (regions if regions else [None]):
+            if rg is not None:
+                sc.set_region(rg)
+                if not sc.load_index(index):
+                    continue                                                 # tabix_advance_region_iterator passes over a region without an iterator
+            while True:
+                b = sc.next_batch(max_blocks)
+                nb += 1
+                if b.n_rows:
+                    out["n_rows"] += int(b.n_rows)
+                    for k, v in sc.batch_columns(b).items():
+                        out[k].extend(v)
+                out["status"] = int(b.status)
+                if b.status != 0:
+                    break
+        if stats is not None:
+            stats.update(resident_bytes=ctx.resident_bytes(), n_batches=nb, n_double_fast=sc.n_double_fast, n_double_patched=sc.n_double_patched)
+        return out
+    finally:
+        ctx.close()
+
+
+def read_tabix(src, region=None, index_path=None, header=False, header_names=None, column_types=None, auto_detect=False, columns=None, device=0, max_blocks=0, stats=None):
+    """read_tabix(path, region := 'a,b', index_path, header, header_names, column_types, auto_detect): {"n_rows", "status", "names", "types"
+    (the resolved schema, DUCKDB_TYPE_* codes), column: python list with None for NULL} for the projected columns (default all).  src: a path
+    (uncompressed, BGZF or plain gzip) or the file's bytes.  The regions run one after another, each through its own index windows; one the
+    index cannot resolve is passed over.  meta character and line_skip come from the index (src + ".tbi" / ".csi", or index_path)."""
+    return _read_tabix_mode(TABIX_GENERIC, "read_tabix", src, region, index_path, header, header_names, column_types, auto_detect, columns, False, device, max_blocks, stats)
+
+
+def read_gff(src, region=None, index_path=None, columns=None, attributes_map=False, device=0, max_blocks=0, stats=None):
+    """read_gff: the nine GFF3 columns (GXF_COLUMNS) and, with attributes_map, the key=value pairs of column 9 as [(key, value), ...]"""
+    return _read_tabix_mode(TABIX_GFF, "read_gff", src, region, index_path, False, None, None, False, columns, attributes_map, device, max_blocks, stats)
+
+
+def read_gtf(src, region=None, index_path=None, columns=None, attributes_map=False, device=0, max_blocks=0, stats=None):
+    """read_gtf: as read_gff with GTF's attribute grammar (key "value"; ...)"""
+    return _read_tabix_mode(TABIX_GTF, "read_gtf", src, region, index_path, False, None, None, False, columns, attributes_map, device, max_blocks, stats)
 
 
 def c_strtof(tok: bytes):

@@ -10,6 +10,7 @@
 #include "bcf_records.hip"
 #include "vcf_text.hip"
 #include "bed_text.hip"
+#include "tabix_text.hip"
 #include "sam_text.hip"
 #include "fastq_text.hip"
 #include "fasta_index.hip"
@@ -176,6 +177,15 @@ struct BedState {
     DevBuf cnt_nl, cnt_tab, base_nl, base_tab, line_off, tab_off, tab0, has_nul, lend, ntab, is_row, rank, row_line, ctr;
     DevBuf ival[BED_N_INT], ivalid[BED_N_INT], slen[BED_N_STR], soff[BED_N_STR], svalid[BED_N_STR], sbytes[BED_N_STR];
 };
+// read_tabix / read_gtf / read_gff (tabix_text.hip, dhts_tabix_scan.inc): the configuration and schema of bind, what is left of line_skip and
+// the header line, and the columns of the last batch.  The line table and the region of a query live in BedState.
+struct TabixState {
+    bool open = false; int mode = 0; int32_t meta_char = '#', line_skip = 0; bool skip_header = false; int32_t skip_left = 0, hdr_left = 0;
+    int32_t n_cols = 0; std::vector<int32_t> types, proj, out_types; std::vector<dhts_col> out; std::vector<TabixCol> cols; int32_t status = 0;
+    bool want_skip_cand = false, have_cand = false; std::string cand;       // dhts_tabix_sniff
+    DevBuf ne, coldev, valid, fixed, len, off, bytes, patch, ctr, pval, pok, tok_off, tok_bytes;
+    DevBuf a_np, a_kb, a_vb, a_po, a_ko, a_vo, a_valid, a_keyoff, a_valoff, a_kbytes, a_vbytes;
+};
 struct dhts_ctx;
 static void stop_stager(dhts_ctx *c);
 struct dhts_ctx {
@@ -209,6 +219,7 @@ struct dhts_ctx {
     int fastq = 0;                    // read_bam on raw reads (fastq_text.hip; sam_text is set as well): 1 FASTQ, 2 FASTA
     FastaState fa;
     BedState bed;
+    TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
     DevBuf f_len, f_flag, f_psum, f_rank, f_mark, f_next, f_plus, f_exit, f_entry, f_stop, f_isstart, f_recrank, f_recline;
     DevBuf v_pos_hi;                   // VCF text: the high words of the batch's 0-based positions (BcfStream::pos_hi)
@@ -314,7 +325,8 @@ static int fail(dhts_ctx *c, const char *fmt, ...) {
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(c, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
 #define ENSURE(c, buf, n) do { if ((buf).ensure(n) != 0) return fail(c, "hipMalloc of %zu bytes failed", (size_t)(n)); } while (0)
 // shards and index building have no meaning on a context that dhts_bed_open prepared
-#define BED_REFUSE(c, what) do { if ((c) && (c)->bed.open) return fail(c, "%s is not supported on a BED context (read_bed scans BED text in file order)", what); } while (0)
+#define BED_REFUSE(c, what) do { if ((c) && (c)->bed.open) return fail(c, "%s is not supported on a BED context (read_bed scans BED text in file order)", what); \
+                                 if ((c) && (c)->tbx.open) return fail(c, "%s is not supported on a tabix text context (read_tabix / read_gtf / read_gff scan text in file order)", what); } while (0)
 
 // ---- kernel timing with HIP events on the context's stream --------------------------------
 static hipEvent_t ev_get(dhts_ctx *c) {
@@ -432,7 +444,7 @@ static void stop_stager(dhts_ctx *c) {
 }
 static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
-    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->text_any = false; c->bed.open = false;
+    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
@@ -485,6 +497,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_fasta_index.inc"
 #include "dhts_bcf_scan.inc"
 #include "dhts_bed_scan.inc"
+#include "dhts_tabix_scan.inc"
 #include "dhts_fetch.inc"
 
 }  // extern "C"

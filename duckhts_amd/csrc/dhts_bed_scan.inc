@@ -5,21 +5,27 @@
 // the rows by the interval tabix_intervals gives a line under the index's own configuration.
 static const char *bed_container(const dhts_ctx *c) { return c->gz_plain ? "plain (non-BGZF) gzip" : "uncompressed text"; }
 
-int dhts_bed_open(dhts_ctx *c) {
-    if (!c) return -1;
+// hts_open for a reader of lines (read_bed, read_tabix): BGZF stays BGZF, everything else is text
+static int text_open(dhts_ctx *c, const char *who) {
     HIPCHK(c, hipSetDevice(c->device));
-    BedState &S = c->bed;
-    S.open = false;
+    c->bed.open = false; c->tbx.open = false;
     if (c->comp_len > 0 && !c->plain_text) {
         // anything that is not BGZF is text, whatever it looks like (hts_getline reads every file): uncompressed, or the members of a plain gzip
         uint8_t head[18] = {0};
         HIPCHK(c, hipMemcpy(head, c->comp.p, c->comp_len < 18 ? (size_t)c->comp_len : 18, hipMemcpyDeviceToHost));
         const bool bgzf = c->comp_len >= 18 && head[0] == 0x1f && head[1] == 0x8b && head[2] == 8 && (head[3] & 4) && head[10] == 6 && head[11] == 0 && head[12] == 'B' && head[13] == 'C' && head[14] == 2 && head[15] == 0;
-        if (!bgzf) { c->text_any = true; if (index_impl(c, false) < 0) return -1; if (!c->plain_text) return fail(c, "read_bed: failed to open file"); }
-        else if (c->n_blocks <= 0) return fail(c, "read_bed: failed to open file (no BGZF block)");
+        if (!bgzf) { c->text_any = true; if (index_impl(c, false) < 0) return -1; if (!c->plain_text) return fail(c, "%s: failed to open file", who); }
+        else if (c->n_blocks <= 0) return fail(c, "%s: failed to open file (no BGZF block)", who);
     }
     c->bam_open = false; c->bcf_open = false; c->sam_text = false; c->vcf_text = false; c->fastq = 0;
     c->first_rec_uoff = 0;
+    return 0;
+}
+
+int dhts_bed_open(dhts_ctx *c) {
+    if (!c) return -1;
+    if (text_open(c, "read_bed")) return -1;
+    BedState &S = c->bed;
     S.proj.clear(); for (int i = 0; i < BED_N_COLS; i++) S.proj.push_back(i);
     S.open = true;
     return dhts_bed_set_region(c, nullptr);
@@ -37,42 +43,47 @@ int dhts_bed_set_projection(dhts_ctx *c, const int32_t *col_ids, int32_t n) {
     return 0;
 }
 
-static int bed_rewind(dhts_ctx *c) { c->bed.lines_done = 0; c->bed.status = 0; return dhts_bam_rewind(c); }
+// (the scan position of a text context: read_bed's line count and error, read_tabix's remaining line_skip / header line)
+static int bed_rewind(dhts_ctx *c) { c->bed.lines_done = 0; c->bed.status = 0; c->tbx.skip_left = c->tbx.line_skip; c->tbx.hdr_left = c->tbx.skip_header ? 1 : 0; return dhts_bam_rewind(c); }
 
 // ONE region, as tbx_itr_querys takes it (commas are thousands separators of its numbers); "." = every record; NULL / "" clears.  The name is
 // one of the INDEX's sequences, so it is resolved by dhts_bed_load_index, which has to follow (except for ".").
-int dhts_bed_set_region(dhts_ctx *c, const char *region) {
-    if (!c || !c->bed.open) return c ? fail(c, "dhts_bed_open not called") : -1;
+// The three region entries are shared with read_tabix (dhts_tabix_scan.inc): `who` names the table function in the messages, the region
+// state lives in c->bed for both.
+static int text_set_region(dhts_ctx *c, const char *who, const char *region) {
     BedState &S = c->bed;
     S.rg_active = S.rg_all = S.rg_pending = false; c->rg_empty_window = false;
     c->wins.clear(); c->win_cur = 0; c->scan_end_uoff = ~0ull;
     c->shard_b0 = 0; c->shard_b1 = c->n_blocks; c->shard_rank = 0; c->shard_world = 1; c->scan_first_uoff = 0;
     if (!region || !*region) return bed_rewind(c);
-    if (c->plain_text) return fail(c, "read_bed: region queries need a BGZF file with a tabix index; this file is %s", bed_container(c));
+    if (c->plain_text) return fail(c, "%s: region queries need a BGZF file with a tabix index; this file is %s", who, bed_container(c));
     S.rg_active = true; S.rg_tok = region;
     if (S.rg_tok == ".") S.rg_all = true; else S.rg_pending = true;
     return bed_rewind(c);
 }
+int dhts_bed_set_region(dhts_ctx *c, const char *region) {
+    if (!c || !c->bed.open) return c ? fail(c, "dhts_bed_open not called") : -1;
+    return text_set_region(c, "read_bed", region);
+}
 
 // the region of `tok` among the sequences of the index `d` (already plain): 0, 1 = no iterator (unknown sequence, malformed region)
-static int bed_resolve(dhts_ctx *c, const uint8_t *d, uint64_t n, const std::string &tok, TbxConf &cf, std::string &name, int &tid, int64_t &b, int64_t &e) {
+static int bed_resolve(dhts_ctx *c, const char *who, const uint8_t *d, uint64_t n, const std::string &tok, TbxConf &cf, std::string &name, int &tid, int64_t &b, int64_t &e) {
     int32_t preset = 0; std::vector<std::string> names;
     const int rc = tabix_header(c, d, n, preset, names);
     if (rc < 0) return -1;
-    if (rc == 1) return fail(c, "read_bed: the index has no tabix header");
+    if (rc == 1) return fail(c, "%s: the index has no tabix header", who);
     const uint8_t *m = memcmp(d, "TBI\1", 4) == 0 ? d + 8 : d + 16;
     cf.preset = (int32_t)hle32(m); cf.sc = (int32_t)hle32(m + 4); cf.bc = (int32_t)hle32(m + 8); cf.ec = (int32_t)hle32(m + 12); cf.meta = (int32_t)hle32(m + 16); cf.skip = (int32_t)hle32(m + 20);
-    if ((cf.preset & 0xffff) > 1) return fail(c, "read_bed: the tabix index was built with the VCF preset");
+    if ((cf.preset & 0xffff) > 1) return fail(c, "%s: the tabix index was built with the VCF preset", who);
     if (!parse_region_token(names, tok, tid, b, e)) return 1;
     name = names[(size_t)tid];
     return 0;
 }
 
 // .tbi, or .csi with the tabix header.  0, 1 = the index does not know the region's sequence ("failed to create region iterator"), < 0 error.
-int dhts_bed_load_index(dhts_ctx *c, const void *bytes, uint64_t n) {
-    if (!c || !c->bed.open) return c ? fail(c, "dhts_bed_open not called") : -1;
+static int text_load_index(dhts_ctx *c, const char *who, const void *bytes, uint64_t n) {
     BedState &S = c->bed;
-    if (c->plain_text) return fail(c, "read_bed: %s has no index", bed_container(c));
+    if (c->plain_text) return fail(c, "%s: %s has no index", who, bed_container(c));
     if (!S.rg_active) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     const uint8_t *d = (const uint8_t *)bytes; std::vector<uint8_t> inflated;
@@ -80,7 +91,7 @@ int dhts_bed_load_index(dhts_ctx *c, const void *bytes, uint64_t n) {
     std::vector<QIv> q;
     if (!S.rg_all) {
         int tid = -1; int64_t b = 0, e = 0;
-        const int rc = bed_resolve(c, d, n, S.rg_tok, S.conf, S.rg_name, tid, b, e);
+        const int rc = bed_resolve(c, who, d, n, S.rg_tok, S.conf, S.rg_name, tid, b, e);
         if (rc < 0) return -1;
         if (rc == 1) { S.rg_pending = false; c->rg_empty_window = true; (void)bed_rewind(c); return 1; }
         S.rg_pending = false; S.rg_beg = b; S.rg_end = e;
@@ -93,10 +104,14 @@ int dhts_bed_load_index(dhts_ctx *c, const void *bytes, uint64_t n) {
     if (apply_window(c, w, S.rg_all, false, true)) return -1;
     return bed_rewind(c);
 }
+int dhts_bed_load_index(dhts_ctx *c, const void *bytes, uint64_t n) {
+    if (!c || !c->bed.open) return c ? fail(c, "dhts_bed_open not called") : -1;
+    return text_load_index(c, "read_bed", bytes, n);
+}
 
 // The file ranges a region query stages instead of the file (conventions of dhts_bam_region_segments; *count = -1: the whole file).  BED text
 // has no header and the names are the index's, so the context need not hold the file.  Returns 1 when the index does not know the sequence.
-int dhts_bed_region_segments(dhts_ctx *c, const char *region, const void *index_bytes, uint64_t n, uint64_t *beg, uint64_t *end, int64_t cap, int64_t *count) {
+static int text_region_segments(dhts_ctx *c, const char *who, const char *region, const void *index_bytes, uint64_t n, uint64_t *beg, uint64_t *end, int64_t cap, int64_t *count) {
     if (!c || !count || !region) return -1;
     *count = -1;
     if (!*region || !strcmp(region, ".")) return 0;
@@ -104,7 +119,7 @@ int dhts_bed_region_segments(dhts_ctx *c, const char *region, const void *index_
     const uint8_t *d = (const uint8_t *)index_bytes; std::vector<uint8_t> inflated;
     if (index_plain(c, d, n, inflated)) return -1;
     TbxConf cf; std::string name; int tid = -1; int64_t b = 0, e = 0;
-    const int rc = bed_resolve(c, d, n, region, cf, name, tid, b, e);
+    const int rc = bed_resolve(c, who, d, n, region, cf, name, tid, b, e);
     if (rc) { if (rc == 1) *count = 0; return rc; }
     std::vector<QIv> q; q.push_back({tid, b, e});
     IdxWindow w;
@@ -115,20 +130,15 @@ int dhts_bed_region_segments(dhts_ctx *c, const char *region, const void *index_
     for (size_t k = 0; k < mg.size(); k++) { beg[k] = mg[k].first >> 16; end[k] = mg[k].second >> 16; }
     return 0;
 }
+int dhts_bed_region_segments(dhts_ctx *c, const char *region, const void *index_bytes, uint64_t n, uint64_t *beg, uint64_t *end, int64_t cap, int64_t *count) {
+    return text_region_segments(c, "read_bed", region, index_bytes, n, beg, end, cap, count);
+}
 
-static int bed_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *out) {
-    memset(out, 0, sizeof(*out));
+// The delimiter table of a batch (bed_text.hip) in c->bed's buffers, for read_bed and read_tabix: the lines that belong to this batch's scan
+// range (a window of a region query ends inside a block), where the carry begins, whether the range ends here.
+struct LineTab { uint64_t carry_start = 0; int64_t nlines = 0; int last_open = 0; bool finished = false; };
+static int text_line_table(dhts_ctx *c, const Batch &B, LineTab &T) {
     BedState &S = c->bed;
-    if (!S.open) return fail(c, "dhts_bed_open not called");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int ncols = (int)S.proj.size();
-    S.out.assign((size_t)ncols, dhts_col());
-    for (int i = 0; i < ncols; i++) { memset(&S.out[(size_t)i], 0, sizeof(dhts_col)); S.out[(size_t)i].col = S.proj[(size_t)i]; }
-    out->n_cols = ncols; out->cols = S.out.data();
-    if (c->stream_done || c->n_blocks <= 0) { out->status = S.status ? S.status : 1; return 0; }
-    if (S.rg_pending) return fail(c, "read_bed: a region query needs the tabix index (dhts_bed_load_index) before the scan");
-    Batch B;
-    if (batch_begin(c, max_blocks, B)) return -1;
     const uint8_t *u = B.u; const uint64_t ulen = B.ulen, out_base = B.out_base;
     uint64_t t0 = 0;
     if (c->first_batch) { if (c->scan_first_uoff < out_base) return fail(c, "internal: window start in front of its first batch"); t0 = c->scan_first_uoff - out_base; }
@@ -136,7 +146,7 @@ static int bed_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *o
     uint64_t end_abs = B.sharded_tail ? c->h_uoff[c->shard_b1] : ~0ull;
     if (c->scan_end_uoff < end_abs) end_abs = c->scan_end_uoff;
     const uint64_t lim = (end_abs != ~0ull && out_base + ulen > end_abs) ? end_abs - out_base : ~0ull;
-    bool finished = false, rec_err = false; uint64_t carry_start = t0 < ulen ? t0 : ulen; int64_t nlines = 0, nrows = 0; int last_open = 0;
+    bool finished = false; uint64_t carry_start = t0 < ulen ? t0 : ulen; int64_t nlines = 0; int last_open = 0;
     if (c->first_batch && out_base + t0 >= end_abs) finished = true;
     if (!finished && t0 < ulen) {
         const uint64_t a0 = t0 & ~(uint64_t)15;
@@ -176,6 +186,27 @@ static int bed_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *o
             else if (carry_start >= lim) finished = true;
         }
     }
+    T.carry_start = carry_start; T.nlines = nlines; T.last_open = last_open; T.finished = finished;
+    return 0;
+}
+
+static int bed_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *out) {
+    memset(out, 0, sizeof(*out));
+    BedState &S = c->bed;
+    if (!S.open) return fail(c, "dhts_bed_open not called");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int ncols = (int)S.proj.size();
+    S.out.assign((size_t)ncols, dhts_col());
+    for (int i = 0; i < ncols; i++) { memset(&S.out[(size_t)i], 0, sizeof(dhts_col)); S.out[(size_t)i].col = S.proj[(size_t)i]; }
+    out->n_cols = ncols; out->cols = S.out.data();
+    if (c->stream_done || c->n_blocks <= 0) { out->status = S.status ? S.status : 1; return 0; }
+    if (S.rg_pending) return fail(c, "read_bed: a region query needs the tabix index (dhts_bed_load_index) before the scan");
+    Batch B;
+    if (batch_begin(c, max_blocks, B)) return -1;
+    const uint8_t *u = B.u; const uint64_t ulen = B.ulen;
+    LineTab T;
+    if (text_line_table(c, B, T)) return -1;
+    bool finished = T.finished, rec_err = false; uint64_t carry_start = T.carry_start; int64_t nlines = T.nlines, nrows = 0; int last_open = T.last_open;
     BedRows R; memset(&R, 0, sizeof(R));
     if (nlines > 0) {
         const size_t ln = (size_t)(nlines + 2) * 4 + 64;

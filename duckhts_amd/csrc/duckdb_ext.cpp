@@ -1685,6 +1685,327 @@ extern "C" __attribute__((visibility("default"))) void register_read_bed_functio
     API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
 }
 
+// ---- read_tabix / read_gtf / read_gff (src/tabix_reader.c): one thread, file order, vector_size rows per chunk ------------------------------
+// Generic bind is the reference's peek at the file (:636-771) on the device: dhts_tabix_sniff + dhts_tabix_resolve_schema, with the meta
+// character and line_skip of the index when there is one; GTF / GFF have their fixed schema.  Init stages the file -- for a single region
+// only its index windows -- and the scan chains the regions of region := 'a,b' (tabix_advance_region_iterator :346-360).
+static const char *const kTabixFn[3] = {"read_tabix", "read_gtf", "read_gff"};
+static const char *const kGxfCols[9] = {"seqname", "source", "feature", "start", "end", "score", "strand", "frame", "attributes"};
+struct TabixBind {
+    int mode = DHTS_TABIX_GENERIC; std::string path, index_path, index; bool has_index = false, attr_map = false;
+    std::vector<std::string> regions;
+    int32_t meta = '#', skip = 0, n_cols = 9; std::vector<int32_t> types; bool skip_header = false;
+};
+struct TabixScanState {
+    dhts_ctx *ctx = nullptr; void *arena = nullptr; uint64_t arena_cap = 0;
+    std::vector<idx_t> column_ids; std::vector<int> slot; std::vector<int32_t> slot_type;     // output column -> position in the projection (-1: none)
+    std::vector<dhts_col> host; dhts_tabix_map hmap; int64_t n = 0, pos = 0; int32_t status = 0; bool done = false;
+    size_t next_region = 0;
+    ~TabixScanState() { if (arena) dhts_host_free(arena); if (ctx) dhts_destroy(ctx); }
+};
+static void destroy_tabix_bind(void *p) { delete (TabixBind *)p; }
+static void destroy_tabix_scan(void *p) { delete (TabixScanState *)p; }
+// parse_regions :301-344
+static std::vector<std::string> tabix_split_regions(const std::string &s) {
+    std::vector<std::string> out; size_t b = 0;
+    while (b <= s.size()) {
+        size_t e = s.find(',', b); if (e == std::string::npos) e = s.size();
+        size_t s0 = b, s1 = e;
+        while (s0 < s1 && (s[s0] == ' ' || s[s0] == '\t')) s0++;
+        while (s1 > s0 && (s[s1 - 1] == ' ' || s[s1 - 1] == '\t')) s1--;
+        if (s1 > s0) out.push_back(s.substr(s0, s1 - s0));
+        b = e + 1;
+    }
+    return out;
+}
+// a LIST(VARCHAR) named parameter.  The two getters are touched only when the parameter is present and not NULL.
+static bool get_named_list(duckdb_bind_info info, const char *name, std::vector<std::string> &out) {
+    duckdb_value v = API(duckdb_value, duckdb_bind_get_named_parameter, duckdb_bind_info, const char *)(info, name);
+    if (!v) return false;
+    bool have = false;
+    if (!API(bool, duckdb_is_null_value, duckdb_value)(v)) {
+        const idx_t n = API(idx_t, duckdb_get_list_size, duckdb_value)(v);
+        for (idx_t i = 0; i < n; i++) {
+            duckdb_value e = API(duckdb_value, duckdb_get_list_child, duckdb_value, idx_t)(v, i);
+            char *t = API(char *, duckdb_get_varchar, duckdb_value)(e);
+            out.push_back(t ? t : ""); if (t) API(void, duckdb_free, void *)(t);
+            API(void, duckdb_destroy_value, duckdb_value *)(&e);
+        }
+        have = n > 0;
+    }
+    API(void, duckdb_destroy_value, duckdb_value *)(&v);
+    return have;
+}
+// the first 100 data rows under the provisional all-VARCHAR schema, for auto_detect (:713-743)
+static bool tabix_first_rows(dhts_ctx *c, int32_t n_cols, std::vector<std::string> &text, std::vector<char> &have, int32_t &n_rows) {
+    n_rows = 0;
+    std::vector<dhts_col> host((size_t)n_cols); std::vector<uint8_t> arena;
+    for (int32_t st = 0; st == 0 && n_rows < 100;) {
+        dhts_tabix_batch b;
+        if (dhts_tabix_next_batch(c, 64, &b) != 0) return false;
+        st = b.status;
+        if (b.n_rows == 0) continue;
+        arena.resize(dhts_tabix_batch_host_bytes(&b) + 8);
+        if (dhts_tabix_batch_fetch(c, &b, arena.data(), arena.size(), host.data(), nullptr) != 0) return false;
+        for (int64_t r = 0; r < b.n_rows && n_rows < 100; r++, n_rows++) for (int32_t k = 0; k < n_cols; k++) {
+            const dhts_col &h = host[(size_t)k];
+            have.push_back(h.valid[r] ? 1 : 0);
+            text.push_back(h.valid[r] ? std::string((const char *)h.bytes + h.off[r], h.off[r + 1] - h.off[r]) : std::string());
+        }
+    }
+    return dhts_tabix_set_region(c, nullptr) == 0;                             // rewinds
+}
+static void tabix_bind(duckdb_bind_info info, int mode) {
+    auto set_error = API(void, duckdb_bind_set_error, duckdb_bind_info, const char *);
+    auto dfree = API(void, duckdb_free, void *);
+    duckdb_value pv = API(duckdb_value, duckdb_bind_get_parameter, duckdb_bind_info, idx_t)(info, 0);
+    char *file_path = API(char *, duckdb_get_varchar, duckdb_value)(pv);
+    API(void, duckdb_destroy_value, duckdb_value *)(&pv);
+    char err[768];
+    if (!file_path || file_path[0] == '\0') { snprintf(err, sizeof(err), "%s requires a file path", kTabixFn[mode]); set_error(info, err); if (file_path) dfree(file_path); return; }   // :520-527
+    TabixBind *b = new TabixBind();
+    b->mode = mode; b->path = file_path; dfree(file_path);
+    if (char *r = get_named_varchar(info, "region")) { b->regions = tabix_split_regions(r); dfree(r); }
+    if (char *x = get_named_varchar(info, "index_path")) { b->index_path = x; dfree(x); }
+    // tbx_index_load2: index_path, else <path>.tbi, else <path>.csi; a file without a readable index is scanned without one
+    b->has_index = b->index_path.empty() ? (read_file(b->path + ".tbi", b->index) || read_file(b->path + ".csi", b->index)) : read_file(b->index_path, b->index);
+    if (b->has_index && b->index.size() < 4) b->has_index = false;
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto add = API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR), t_bigint = mk(DUCKDB_TYPE_BIGINT), t_double = mk(DUCKDB_TYPE_DOUBLE), t_integer = mk(DUCKDB_TYPE_INTEGER);
+    auto type_of = [&](int32_t t) { return t == DHTS_T_BIGINT ? t_bigint : t == DHTS_T_DOUBLE ? t_double : t == DHTS_T_INTEGER ? t_integer : t_varchar; };
+    auto done_types = [&]() { rm(&t_varchar); rm(&t_bigint); rm(&t_double); rm(&t_integer); };
+    if (mode != DHTS_TABIX_GENERIC) {                                          // :555-587
+        static const int32_t gxf[9] = {DHTS_T_VARCHAR, DHTS_T_VARCHAR, DHTS_T_VARCHAR, DHTS_T_BIGINT, DHTS_T_BIGINT, DHTS_T_DOUBLE, DHTS_T_VARCHAR, DHTS_T_VARCHAR, DHTS_T_VARCHAR};
+        b->attr_map = get_named_bool(info, "attributes_map") != 0;
+        b->n_cols = 9; b->types.assign(gxf, gxf + 9);
+        for (int i = 0; i < 9; i++) add(info, kGxfCols[i], type_of(gxf[i]));
+        if (b->attr_map) {
+            duckdb_logical_type t_map = API(duckdb_logical_type, duckdb_create_map_type, duckdb_logical_type, duckdb_logical_type)(t_varchar, t_varchar);
+            add(info, "attributes_map", t_map); rm(&t_map);
+        }
+    } else {
+        const bool header = get_named_bool(info, "header") != 0, auto_detect = get_named_bool(info, "auto_detect") != 0;
+        std::vector<std::string> hn, ct;
+        const bool have_hn = get_named_list(info, "header_names", hn), have_ct = get_named_list(info, "column_types", ct);
+        if (!file_exists(b->path)) { set_error(info, "Cannot open file"); done_types(); delete b; return; }               // :636-641
+        dhts_ctx *c = dhts_create(device_list()[0]);
+        if (!c) { set_error(info, "read_tabix: no MI355X (gfx950) device available; this build has no CPU fallback"); done_types(); delete b; return; }
+        auto bail = [&](const char *msg) { const std::string m = msg; set_error(info, m.c_str()); dhts_destroy(c); done_types(); delete b; };
+        if (dhts_open_path(c, b->path.c_str()) != 0) { bail("Cannot open file"); return; }
+        (void)dhts_bgzf_index(c);
+        if (dhts_tabix_open(c, DHTS_TABIX_GENERIC) != 0) { bail("Cannot open file"); return; }
+        if (b->has_index) {                                                    // :649-656
+            int32_t m = 0, sk = 0;
+            if (dhts_tabix_index_conf(c, b->index.data(), b->index.size(), &m, &sk) == 0) { b->meta = m ? m : '#'; b->skip = sk; } else b->has_index = false;
+        }
+        if (dhts_tabix_set_conf(c, b->meta, b->skip) != 0) { bail(dhts_error(c)); return; }
+        dhts_tabix_sniffed sn;
+        if (dhts_tabix_sniff(c, header, have_hn, &sn) != 0) { bail(dhts_error(c)); return; }
+        std::vector<const char *> hn_p, ct_p;
+        for (auto &x : hn) hn_p.push_back(x.c_str());
+        for (auto &x : ct) ct_p.push_back(x.c_str());
+        dhts_tabix_schema *sch = new dhts_tabix_schema();
+        char emsg[256];
+        int rc = dhts_tabix_resolve_schema(&sn, header, have_hn ? hn_p.data() : nullptr, (int32_t)hn_p.size(), have_ct ? ct_p.data() : nullptr, (int32_t)ct_p.size(), auto_detect,
+                                           nullptr, nullptr, 0, sch, emsg, sizeof(emsg));
+        if (rc == 1) {
+            std::vector<std::string> text; std::vector<char> have; int32_t n_rows = 0;
+            if (dhts_tabix_set_schema(c, sch->n_cols, sch->types, sch->skip_header_line) != 0 || !tabix_first_rows(c, sch->n_cols, text, have, n_rows)) { delete sch; bail(dhts_error(c)); return; }
+            std::vector<const char *> cells(text.size() + 1, nullptr); std::vector<uint32_t> lens(text.size() + 1, 0);
+            for (size_t i = 0; i < text.size(); i++) if (have[i]) { cells[i] = text[i].data(); lens[i] = (uint32_t)text[i].size(); }
+            rc = dhts_tabix_resolve_schema(&sn, header, have_hn ? hn_p.data() : nullptr, (int32_t)hn_p.size(), nullptr, 0, auto_detect, cells.data(), lens.data(), n_rows, sch, emsg, sizeof(emsg));
+        }
+        if (rc < 0) { delete sch; bail(emsg); return; }                        // "column_types length does not match detected column count" :698-702
+        b->n_cols = sch->n_cols; b->types.assign(sch->types, sch->types + sch->n_cols); b->skip_header = sch->skip_header_line != 0;
+        for (int32_t i = 0; i < sch->n_cols; i++) add(info, sch->names[i], type_of(sch->types[i]));
+        delete sch;
+        dhts_destroy(c);
+    }
+    done_types();
+    API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, b, destroy_tabix_bind);
+}
+static void tabix_read_bind(duckdb_bind_info info) { tabix_bind(info, DHTS_TABIX_GENERIC); }
+static void gtf_read_bind(duckdb_bind_info info) { tabix_bind(info, DHTS_TABIX_GTF); }
+static void gff_read_bind(duckdb_bind_info info) { tabix_bind(info, DHTS_TABIX_GFF); }
+// the next region the index resolves becomes the scan (tabix_advance_region_iterator): 1 positioned, 0 none left, -1 error (err set)
+static int tabix_advance(const TabixBind *bind, TabixScanState *g, std::string &err) {
+    while (g->next_region < bind->regions.size()) {
+        const std::string &r = bind->regions[g->next_region++];
+        if (dhts_tabix_set_region(g->ctx, r.c_str()) != 0) { err = dhts_error(g->ctx); return -1; }
+        const int rc = dhts_tabix_load_index(g->ctx, bind->index.data(), bind->index.size());
+        if (rc < 0) { err = dhts_error(g->ctx); return -1; }
+        if (rc == 0) { g->status = 0; return 1; }
+    }
+    return 0;
+}
+static void tabix_read_init(duckdb_init_info info) {
+    TabixBind *bind = (TabixBind *)API(void *, duckdb_init_get_bind_data, duckdb_init_info)(info);
+    auto init_error = API(void, duckdb_init_set_error, duckdb_init_info, const char *);
+    char msg[768];
+    if (!file_exists(bind->path)) { snprintf(msg, sizeof(msg), "Cannot open file: %s", bind->path.c_str()); init_error(info, msg); return; }                                  // :794-801
+    if (!bind->regions.empty() && !bind->has_index) { snprintf(msg, sizeof(msg), "Region query requested but no tabix index found for: %s", bind->path.c_str()); init_error(info, msg); return; }   // :806-816
+    TabixScanState *g = new TabixScanState();
+    memset(&g->hmap, 0, sizeof(g->hmap));
+    g->ctx = dhts_create(device_list()[0]);
+    if (!g->ctx) { snprintf(msg, sizeof(msg), "%s: no MI355X (gfx950) device available; this build has no CPU fallback", kTabixFn[bind->mode]); init_error(info, msg); delete g; return; }
+    auto bail = [&](const char *m) { const std::string t = m; init_error(info, t.c_str()); delete g; };
+    snprintf(msg, sizeof(msg), "Cannot open file: %s", bind->path.c_str());
+    bool staged = false;
+    if (bind->regions.size() == 1) {
+        // one region of a BGZF file: nothing but its index windows is staged
+        uint8_t h[18] = {0}; size_t got = 0;
+        if (FILE *f = fopen(bind->path.c_str(), "rb")) { got = fread(h, 1, 18, f); fclose(f); }
+        const bool bgzf = got == 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C';
+        if (bgzf) {
+            uint64_t beg[4096], end[4096]; int64_t cnt = -1;
+            const int rc = dhts_tabix_region_segments(g->ctx, bind->regions[0].c_str(), bind->index.data(), bind->index.size(), beg, end, 4096, &cnt);
+            if (rc < 0) { bail(dhts_error(g->ctx)); return; }
+            if (rc == 0 && cnt > 0) {
+                if (dhts_open_path_segments(g->ctx, bind->path.c_str(), 0, beg, end, cnt) != 0) { bail(msg); return; }
+                staged = true;
+            }
+        }
+    }
+    if (!staged && dhts_open_path(g->ctx, bind->path.c_str()) != 0) { bail(msg); return; }
+    (void)dhts_bgzf_index(g->ctx);                               // (text that is not BGZF fails here and is taken as text by dhts_tabix_open)
+    if (dhts_tabix_open(g->ctx, bind->mode) != 0) { bail(msg); return; }
+    if (bind->mode == DHTS_TABIX_GENERIC) {
+        if (dhts_tabix_set_conf(g->ctx, bind->meta, bind->skip) != 0 || dhts_tabix_set_schema(g->ctx, bind->n_cols, bind->types.data(), bind->skip_header ? 1 : 0) != 0) { bail(dhts_error(g->ctx)); return; }
+    }
+    const idx_t n = API(idx_t, duckdb_init_get_column_count, duckdb_init_info)(info);
+    const idx_t lim = bind->mode == DHTS_TABIX_GENERIC ? (idx_t)bind->n_cols : (idx_t)(bind->attr_map ? 10 : 9);
+    std::vector<int32_t> proj, proj_type;
+    for (idx_t i = 0; i < n; i++) {
+        const idx_t id = API(idx_t, duckdb_init_get_column_index, duckdb_init_info, idx_t)(info, i);
+        g->column_ids.push_back(id);
+        int at = -1;
+        if (id < lim) {
+            for (size_t k = 0; k < proj.size(); k++) if (proj[k] == (int32_t)id) at = (int)k;
+            if (at < 0) { at = (int)proj.size(); proj.push_back((int32_t)id); proj_type.push_back(id < (idx_t)bind->n_cols ? bind->types[id] : 0); }
+        }
+        g->slot.push_back(at); g->slot_type.push_back(at >= 0 ? proj_type[(size_t)at] : 0);
+    }
+    if (dhts_tabix_set_projection(g->ctx, proj.data(), (int32_t)proj.size()) != 0) { bail(dhts_error(g->ctx)); return; }
+    if (!bind->regions.empty()) {
+        std::string err;
+        const int rc = tabix_advance(bind, g, err);
+        if (rc < 0) { bail(err.c_str()); return; }
+        if (rc == 0) g->done = true;                             // no region matches a sequence of the index: an empty result (:821-824)
+    }
+    g->host.resize(proj.size() ? proj.size() : 1);
+    API(void, duckdb_init_set_max_threads, duckdb_init_info, idx_t)(info, 1);
+    API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, g, destroy_tabix_scan);
+}
+// the next device batch, read back; false at the end of the scan or on a failure (err set)
+static bool tabix_next(const TabixBind *bind, TabixScanState *g, std::string &err) {
+    for (;;) {
+        while (g->status == 0) {
+            dhts_tabix_batch b;
+            if (dhts_tabix_next_batch(g->ctx, 0, &b) != 0) { err = dhts_error(g->ctx); return false; }
+            g->status = b.status;
+            if (b.n_rows == 0) continue;
+            const uint64_t need = dhts_tabix_batch_host_bytes(&b);
+            if (need > g->arena_cap) { if (g->arena) dhts_host_free(g->arena); g->arena_cap = need + need / 4 + 4096; g->arena = dhts_host_alloc(g->arena_cap); if (!g->arena) { g->arena_cap = 0; err = "read_tabix: out of pinned host memory"; return false; } }
+            if (dhts_tabix_batch_fetch(g->ctx, &b, g->arena, g->arena_cap, g->host.data(), &g->hmap) != 0) { err = dhts_error(g->ctx); return false; }
+            g->n = b.n_rows; g->pos = 0;
+            return true;
+        }
+        if (bind->regions.empty() || g->status < 0) return false;
+        const int rc = tabix_advance(bind, g, err);                            // the iterator is exhausted: the next region (:888-894)
+        if (rc <= 0) return false;
+    }
+}
+static void tabix_read_function(duckdb_function_info info, duckdb_data_chunk output) {
+    TabixScanState *g = (TabixScanState *)API(void *, duckdb_function_get_init_data, duckdb_function_info)(info);
+    const TabixBind *bind = (const TabixBind *)API(void *, duckdb_function_get_bind_data, duckdb_function_info)(info);
+    auto set_size = API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t);
+    if (!g || g->done) { set_size(output, 0); return; }
+    const idx_t vector_size = API(idx_t, duckdb_vector_size, void)();
+    auto get_vec = API(duckdb_vector, duckdb_data_chunk_get_vector, duckdb_data_chunk, idx_t);
+    auto assign_len = API(void, duckdb_vector_assign_string_element_len, duckdb_vector, idx_t, const char *, idx_t);
+    auto get_data = API(void *, duckdb_vector_get_data, duckdb_vector);
+    idx_t row_count = 0;
+    while (row_count < vector_size) {
+        if (g->pos >= g->n) {
+            std::string err;
+            if (!tabix_next(bind, g, err)) {
+                g->done = true;
+                if (!err.empty()) { API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, err.c_str()); set_size(output, 0); return; }
+                break;
+            }
+        }
+        const idx_t take = (idx_t)(g->n - g->pos) < vector_size - row_count ? (idx_t)(g->n - g->pos) : vector_size - row_count;
+        for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
+            duckdb_vector vec = get_vec(output, ci);
+            if (g->slot[ci] < 0) { for (idx_t r = 0; r < take; r++) set_null(vec, row_count + r); continue; }
+            const dhts_col &hc = g->host[(size_t)g->slot[ci]];
+            const int32_t ty = g->slot_type[ci];
+            const int64_t s = g->pos;
+            if (ty == 0) {                                                     // attributes_map, filled like the auxiliary-tag map of read_bam
+                const dhts_tabix_map &m = g->hmap;
+                duckdb_list_entry *le = (duckdb_list_entry *)get_data(vec);
+                const idx_t base = API(idx_t, duckdb_list_vector_get_size, duckdb_vector)(vec);
+                const uint32_t c0 = m.pair_off[s], c1 = m.pair_off[s + (int64_t)take];
+                if (c1 > c0) { API(duckdb_state, duckdb_list_vector_reserve, duckdb_vector, idx_t)(vec, base + (c1 - c0)); API(duckdb_state, duckdb_list_vector_set_size, duckdb_vector, idx_t)(vec, base + (c1 - c0)); }
+                duckdb_vector child = API(duckdb_vector, duckdb_list_vector_get_child, duckdb_vector)(vec);
+                duckdb_vector kvec = API(duckdb_vector, duckdb_struct_vector_get_child, duckdb_vector, idx_t)(child, 0);
+                duckdb_vector vvec = API(duckdb_vector, duckdb_struct_vector_get_child, duckdb_vector, idx_t)(child, 1);
+                for (idx_t r = 0; r < take; r++) {
+                    le[row_count + r].offset = base + (m.pair_off[s + r] - c0); le[row_count + r].length = m.pair_off[s + r + 1] - m.pair_off[s + r];
+                    if (!m.valid[s + r]) set_null(vec, row_count + r);
+                }
+                for (uint32_t k = c0; k < c1; k++) {
+                    assign_len(kvec, base + (k - c0), (const char *)m.key_bytes + m.key_off[k], m.key_off[k + 1] - m.key_off[k]);
+                    assign_len(vvec, base + (k - c0), (const char *)m.val_bytes + m.val_off[k], m.val_off[k + 1] - m.val_off[k]);
+                }
+            } else if (ty == DHTS_T_VARCHAR) {
+                for (idx_t r = 0; r < take; r++) {
+                    const int64_t k = s + (int64_t)r;
+                    if (hc.valid[k]) assign_len(vec, row_count + r, (const char *)hc.bytes + hc.off[k], hc.off[k + 1] - hc.off[k]); else set_null(vec, row_count + r);
+                }
+            } else if (ty == DHTS_T_INTEGER) {
+                // the reference declares INTEGER and stores 8-byte values into the 4-byte vector (:1004-1008); here a value that fits is stored, another is NULL
+                int32_t *data = (int32_t *)get_data(vec); const int64_t *src = (const int64_t *)hc.fixed;
+                for (idx_t r = 0; r < take; r++) { const int64_t v = src[s + r]; if (hc.valid[s + r] && v >= INT32_MIN && v <= INT32_MAX) data[row_count + r] = (int32_t)v; else set_null(vec, row_count + r); }
+            } else {                                                           // BIGINT and DOUBLE: 8 bytes as they are
+                int64_t *data = (int64_t *)get_data(vec); const int64_t *src = (const int64_t *)hc.fixed;
+                for (idx_t r = 0; r < take; r++) { if (hc.valid[s + r]) data[row_count + r] = src[s + r]; else set_null(vec, row_count + r); }
+            }
+        }
+        g->pos += (int64_t)take; row_count += take;
+    }
+    set_size(output, row_count);
+}
+static void register_tabix_tf(duckdb_connection connection, const char *name, duckdb_table_function_bind_t bind) {          // create_tabix_tf :1038-1079
+    duckdb_table_function tf = API(duckdb_table_function, duckdb_create_table_function, void)();
+    API(void, duckdb_table_function_set_name, duckdb_table_function, const char *)(tf, name);
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    auto named = API(void, duckdb_table_function_add_named_parameter, duckdb_table_function, const char *, duckdb_logical_type);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR), t_bool = mk(DUCKDB_TYPE_BOOLEAN);
+    duckdb_logical_type t_list = API(duckdb_logical_type, duckdb_create_list_type, duckdb_logical_type)(t_varchar);
+    API(void, duckdb_table_function_add_parameter, duckdb_table_function, duckdb_logical_type)(tf, t_varchar);
+    named(tf, "region", t_varchar);
+    named(tf, "index_path", t_varchar);
+    named(tf, "attributes_map", t_bool);
+    named(tf, "header", t_bool);
+    named(tf, "header_names", t_list);
+    named(tf, "auto_detect", t_bool);
+    named(tf, "column_types", t_list);
+    rm(&t_list); rm(&t_bool); rm(&t_varchar);
+    API(void, duckdb_table_function_set_bind, duckdb_table_function, duckdb_table_function_bind_t)(tf, bind);
+    API(void, duckdb_table_function_set_init, duckdb_table_function, duckdb_table_function_init_t)(tf, tabix_read_init);
+    API(void, duckdb_table_function_set_function, duckdb_table_function, duckdb_table_function_t)(tf, tabix_read_function);
+    API(void, duckdb_table_function_supports_projection_pushdown, duckdb_table_function, bool)(tf, true);
+    API(duckdb_state, duckdb_register_table_function, duckdb_connection, duckdb_table_function)(connection, tf);
+    API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
+}
+extern "C" __attribute__((visibility("default"))) void register_read_tabix_function(duckdb_connection connection) { register_tabix_tf(connection, "read_tabix", tabix_read_bind); }   // :1081-1085
+extern "C" __attribute__((visibility("default"))) void register_read_gtf_function(duckdb_connection connection) { register_tabix_tf(connection, "read_gtf", gtf_read_bind); }
+extern "C" __attribute__((visibility("default"))) void register_read_gff_function(duckdb_connection connection) { register_tabix_tf(connection, "read_gff", gff_read_bind); }
+
 extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(duckdb_extension_info info, struct duckdb_extension_access *access) {
     // duckdb_extension.h:1151-1158,1182-1194: fetch the API table, connect, register, disconnect
     const void *api = access->get_api(info, DUCKHTS_API_VERSION);
@@ -1705,6 +2026,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     if (const char *e = getenv("DHTS_SEQ_FUNCTIONS")) if (atoi(e) == 1) { register_read_fasta_function(conn); register_read_fastq_function(conn); register_fasta_index_function(conn); }
     // read_bed follows fasta_index (src/duckhts.c:59), opt-in as well: DHTS_INTERVAL_FUNCTIONS=1
     if (const char *e = getenv("DHTS_INTERVAL_FUNCTIONS")) if (atoi(e) == 1) register_read_bed_function(conn);
+    // read_tabix, read_gtf, read_gff close the list (src/duckhts.c:67-69), opt-in: DHTS_TABIX_FUNCTIONS=1
+    if (const char *e = getenv("DHTS_TABIX_FUNCTIONS")) if (atoi(e) == 1) { register_read_tabix_function(conn); register_read_gtf_function(conn); register_read_gff_function(conn); }
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);
     return true;
 }

@@ -447,6 +447,74 @@ int dhts_bed_next_batch(dhts_ctx *, int64_t max_blocks, dhts_bed_batch *out);
 uint64_t dhts_bed_batch_host_bytes(const dhts_bed_batch *b);
 int dhts_bed_batch_fetch(dhts_ctx *, const dhts_bed_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
+ * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and
+ * uncompressed text are read.  Bind is dhts_tabix_set_conf + dhts_tabix_sniff + dhts_tabix_resolve_schema + dhts_tabix_set_schema;
+ * GTF / GFF have the fixed schema of :564-587 and need none of them. */
+enum { DHTS_TABIX_GENERIC = 0, DHTS_TABIX_GTF = 1, DHTS_TABIX_GFF = 2 };
+enum { DHTS_TABIX_MAX_COLS = 256,       /* TABIX_MAX_GENERIC_COLS                                                    */
+       DHTS_GXF_ATTRIBUTES_MAP = 9 };   /* projection id of attributes_map in GTF / GFF mode (ids 0..8: seqname .. attributes) */
+/* hts_open + tabix_init :786-846 for `mode`; positions the scan at the first line.  Shards, block ranges other than the whole file and index
+ * building fail on such a context. */
+int dhts_tabix_open(dhts_ctx *, int mode);
+/* what bind takes from the index, tbx->conf :649-656: the meta character (0: none) and line_skip.  '#' / 0 after dhts_tabix_open; GTF / GFF
+ * keep '#' / 0 whatever an index says (their bind never loads it) and refuse this call. */
+int dhts_tabix_set_conf(dhts_ctx *, int meta_char, int line_skip);
+/* the peek of bind :658-679 on the device's line table of the first batch(es); only the bytes of the header candidate are fetched.
+ * n_fields = count_fields of the first data line (0: there is none); candidate = the line `header := true` takes its names from when no
+ * header_names are given (have_candidate; owned by the context, valid until the next call on it): the last line of the line_skip prefix
+ * (candidate_from_skip) or else the first line that is neither empty nor meta.  The scan is rewound afterwards. */
+typedef struct { int32_t n_fields, have_candidate, candidate_from_skip, reserved; const char *candidate; uint64_t candidate_len; } dhts_tabix_sniffed;
+int dhts_tabix_sniff(dhts_ctx *, int header, int have_header_names, dhts_tabix_sniffed *out);
+/* the rest of bind :684-771, host only (no context): names, types (DHTS_T_INTEGER / _BIGINT / _DOUBLE / _VARCHAR, parse_type_name :218-230)
+ * and skip_header_line.  header_names / column_types: NULL or n = 0 when the parameter is absent.  auto_detect :709-755 looks at up to 100
+ * data rows: cells[r * n_cols + k] / cell_len[...] are the fields of row r under the returned n_cols (NULL = the line has no such field);
+ * when it needs them and cells is NULL the call fills `out` with the all-VARCHAR schema and returns 1: scan 100 rows under it (after
+ * dhts_tabix_set_schema), rewind, and call again.  names[k] point into memory of the library that stays valid until the calling thread's
+ * next dhts_tabix_resolve_schema.  < 0: the message is in err. */
+typedef struct {
+    int32_t n_cols, skip_header_line;
+    int32_t types[DHTS_TABIX_MAX_COLS]; const char *names[DHTS_TABIX_MAX_COLS];
+} dhts_tabix_schema;
+int dhts_tabix_resolve_schema(const dhts_tabix_sniffed *sniffed, int header, const char *const *header_names, int32_t n_header_names,
+                              const char *const *column_types, int32_t n_column_types, int auto_detect,
+                              const char *const *cells, const uint32_t *cell_len, int32_t n_cell_rows, dhts_tabix_schema *out, char *err, uint64_t err_cap);
+/* generic mode: the schema bind resolved (INTEGER is parsed as BIGINT: the consumer narrows); the projection becomes every column */
+int dhts_tabix_set_schema(dhts_ctx *, int32_t n_cols, const int32_t *types, int skip_header_line);
+/* column ids, each once (init :834-843); n = 0: only n_rows.  GTF / GFF: 0..8 and DHTS_GXF_ATTRIBUTES_MAP; default 0..8 */
+int dhts_tabix_set_projection(dhts_ctx *, const int32_t *col_ids, int32_t n);
+/* ONE region at a time, with dhts_bed_set_region / _load_index / _region_segments' conventions (tbx_itr_querys; the caller splits
+ * region := 'a,b' by parse_regions :301-344 and chains the scans, tabix_advance_region_iterator :346-360).  Inside a region query line_skip
+ * and the header line are not applied (:898, 903 test !id->itr). */
+int dhts_tabix_set_region(dhts_ctx *, const char *region);
+int dhts_tabix_load_index(dhts_ctx *, const void *index_bytes, uint64_t n);
+int dhts_tabix_region_segments(dhts_ctx *, const char *region, const void *index_bytes, uint64_t n, uint64_t *beg, uint64_t *end, int64_t cap, int64_t *count);
+/* what an index says for dhts_tabix_set_conf (.tbi, or .csi with the tabix header; BGZF or already inflated): 0, < 0 not a tabix index */
+int dhts_tabix_index_conf(dhts_ctx *, const void *index_bytes, uint64_t n, int32_t *meta_char, int32_t *line_skip);
+/* attributes_map (fill_attr_map :412-494): row r owns pairs pair_off[r] .. pair_off[r + 1] - 1; pair p has the key key_bytes[key_off[p],
+ * key_off[p + 1]) and the value val_bytes[val_off[p], val_off[p + 1]).  valid[r] = 0: NULL map (field 8 missing, empty or "."). */
+typedef struct {
+    const uint32_t *pair_off; const uint8_t *valid; uint64_t n_pairs;
+    const uint32_t *key_off; const uint8_t *key_bytes; uint64_t key_nbytes;
+    const uint32_t *val_off; const uint8_t *val_bytes; uint64_t val_nbytes;
+} dhts_tabix_map;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more data may follow, 1 = end of stream reached cleanly, < 0 = the stream ended on an error            */
+    int32_t n_cols;          /* projected columns, in projection order                                                                     */
+    const dhts_col *cols;    /* as dhts_bed_batch.cols: BIGINT and DOUBLE in fixed (8 bytes), VARCHAR in off / bytes.  The descriptor of
+                                attributes_map is empty: `map` holds it                                                                    */
+    const int32_t *col_types;/* host array: DHTS_T_* of every projected column (attributes_map: 0)                                          */
+    int32_t has_map, reserved;
+    dhts_tabix_map map;
+    uint64_t n_double_fast, n_double_patched;   /* DOUBLE tokens of this batch converted on the device / by strtod on the host (the columns
+                                                   are complete on the device either way)                                                  */
+} dhts_tabix_batch;
+int dhts_tabix_next_batch(dhts_ctx *, int64_t max_blocks, dhts_tabix_batch *out);     /* the loop body of tabix_scan :880-1028 */
+/* read-back: out_cols[b->n_cols] = b->cols and *out_map = b->map with HOST pointers into dst (out_map may be NULL without a map) */
+uint64_t dhts_tabix_batch_host_bytes(const dhts_tabix_batch *b);
+int dhts_tabix_batch_fetch(dhts_ctx *, const dhts_tabix_batch *b, void *dst, uint64_t cap, dhts_col *out_cols, dhts_tabix_map *out_map);
+
 /* ---- utilities ------------------------------------------------------------------------------ */
 int dhts_memcpy_d2h(dhts_ctx *, void *dst, const void *src_dev, uint64_t n);
 int dhts_sync(dhts_ctx *);

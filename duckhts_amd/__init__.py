@@ -104,6 +104,9 @@ GXF_COLUMNS = ["seqname", "source", "feature", "start", "end", "score", "strand"
 GXF_TYPES = [T_VARCHAR, T_VARCHAR, T_VARCHAR, T_BIGINT, T_BIGINT, T_DOUBLE, T_VARCHAR, T_VARCHAR, T_VARCHAR]
 BED_COLUMNS = ["chrom", "start", "end", "name", "score", "strand", "thick_start", "thick_end", "item_rgb", "block_count", "block_sizes", "block_starts", "extra"]
 BED_INT_COLUMNS = (1, 2, 6, 7, 9)
+NUC_COLUMNS = ["chrom", "start", "end", "pct_at", "pct_gc", "num_a", "num_c", "num_g", "num_t", "num_n", "num_other", "seq_len", "seq"]
+NUC_DOUBLE_COLUMNS = (3, 4)
+NUC_STR_COLUMNS = (0, 12)
 
 # DUCKDB_TYPE_* element codes -> the canonical type tags of the test oracle's column blob
 _CANON_TYPE = {17: 1, 5: 2, 11: 3, 1: 4, 4: 5, 10: 6}
@@ -119,6 +122,7 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_host_alloc", "dhts_host_free", "dhts_release_pools", "dhts_device_mem_info", "dhts_shard_window", "dhts_bcf_build_index", "dhts_bgzf_wrap", "dhts_bgzf_compress", "dhts_bgzip_file", "dhts_bgunzip_file", "dhts_bcf_is_text", "dhts_bam_is_text", "dhts_bam_set_seq_packed", "dhts_bcf_header_bytes", "dhts_bcf_region_segments", "dhts_set_super_blocks", "dhts_bam_build_index_csi", "dhts_tabix_build_index", "dhts_bcf_batch_host_bytes", "dhts_bcf_batch_fetch", "dhts_resident_from_cache", "dhts_bam_region_segments", "dhts_open_path_segments", "dhts_open_path_async", "dhts_stage_wait", "dhts_bgzf_index_staged", "dhts_blocks_ahead", "dhts_bam_batch_host_bytes", "dhts_bam_batch_fetch", "dhts_bam_batch_fetch_begin", "dhts_bam_batch_fetch_wait", "dhts_bcf_batch_fetch_begin", "dhts_bcf_batch_fetch_wait", "dhts_device_numa_node", "dhts_bind_thread_to_node", "dhts_bind_thread_near_device", "dhts_bam_set_qual_packed",
            "dhts_fasta_build_index", "dhts_fasta_index_bytes", "dhts_fasta_gzi_bytes", "dhts_fasta_load_index", "dhts_fasta_open_regions", "dhts_fasta_fetch", "dhts_fasta_batch_host_bytes", "dhts_fasta_batch_fetch",
            "dhts_bed_open", "dhts_bed_set_projection", "dhts_bed_set_region", "dhts_bed_load_index", "dhts_bed_region_segments", "dhts_bed_next_batch", "dhts_bed_batch_host_bytes", "dhts_bed_batch_fetch",
+           "dhts_nuc_open_region", "dhts_nuc_open", "dhts_nuc_set_region", "dhts_nuc_set_projection", "dhts_nuc_next_bins", "dhts_nuc_next_bed", "dhts_nuc_intervals", "dhts_nuc_batch_host_bytes", "dhts_nuc_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch"]
 
@@ -201,6 +205,16 @@ def lib():
         L.dhts_bed_batch_host_bytes.restype = C.c_uint64
         L.dhts_bed_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_bed_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_nuc_open_region.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int]
+        L.dhts_nuc_open.argtypes = [C.c_void_p, C.c_int]
+        L.dhts_nuc_set_region.argtypes = [C.c_void_p, C.c_char_p]
+        L.dhts_nuc_set_projection.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.dhts_nuc_next_bins.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BedBatch)]
+        L.dhts_nuc_next_bed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
+        L.dhts_nuc_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
+        L.dhts_nuc_batch_host_bytes.restype = C.c_uint64
+        L.dhts_nuc_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
+        L.dhts_nuc_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
         L.dhts_tabix_open.argtypes = [C.c_void_p, C.c_int]
         L.dhts_tabix_set_conf.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dhts_tabix_index_conf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -557,6 +571,68 @@ class Context:
         sb = arena[hb.seq_bytes - base: hb.seq_bytes - base + hb.seq_nbytes].tobytes()
         return [(nb[int(noff[i]):int(noff[i + 1])], sb[int(soff[i]):int(soff[i + 1])]) for i in range(n)]
 
+    # ---- fasta_nuc (the batch has dhts_bed_batch's layout) ----
+    def nuc_open(self, include_seq=False):
+        self._chk(self.L.dhts_nuc_open(self.h, int(bool(include_seq))))
+        self.nuc_projection = list(range(len(NUC_COLUMNS) - (0 if include_seq else 1)))
+        return self
+
+    def nuc_set_region(self, region):
+        """False for a region the reference calls invalid ("fasta_nuc: invalid FASTA region")"""
+        r = region.encode() if isinstance(region, str) else region
+        return self._chk(self.L.dhts_nuc_set_region(self.h, r)) == 0
+
+    def nuc_set_projection(self, cols):
+        ids = [c if isinstance(c, int) else NUC_COLUMNS.index(c) for c in cols]
+        arr = np.array(ids, np.int32)
+        self._chk(self.L.dhts_nuc_set_projection(self.h, arr.ctypes.data, len(ids)))
+        self.nuc_projection = ids
+
+    def nuc_next_bins(self, bin_width, max_rows=0):
+        b = BedBatch()
+        self._chk(self.L.dhts_nuc_next_bins(self.h, bin_width, max_rows, C.byref(b)))
+        return b
+
+    def nuc_next_bed(self, bed_ctx, max_blocks=0):
+        b = BedBatch()
+        self._chk(self.L.dhts_nuc_next_bed(self.h, bed_ctx.h, max_blocks, C.byref(b)))
+        return b
+
+    def nuc_batch_columns(self, b):
+        """the projected columns of one batch through dhts_nuc_batch_fetch: {"n_rows", name: python list, None for NULL}; the two
+        fractions come back as float64 values whose bits are the device's"""
+        n = int(b.n_rows)
+        need = int(self.L.dhts_nuc_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        self._chk(self.L.dhts_nuc_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
+        base = arena.ctypes.data
+        out = {"n_rows": n}
+        for i in range(b.n_cols):
+            hc = host[i]
+            name = NUC_COLUMNS[hc.col]
+            if n == 0:
+                out[name] = []
+                continue
+            valid = arena[hc.valid - base: hc.valid - base + n]
+            if hc.col in NUC_STR_COLUMNS:
+                off = arena[hc.off - base: hc.off - base + 4 * (n + 1)].view(np.uint32)
+                data = arena[hc.bytes - base: hc.bytes - base + int(hc.nbytes)].tobytes()
+                out[name] = [data[int(off[r]):int(off[r + 1])] if valid[r] else None for r in range(n)]
+            else:
+                vals = arena[hc.fixed - base: hc.fixed - base + 8 * n].view(np.float64 if hc.col in NUC_DOUBLE_COLUMNS else np.int64)
+                out[name] = vals.tolist()
+        return out
+
+    def nuc_intervals(self, tid, start, end):
+        """fasta_nuc's rows for already-resolved intervals (tid = index of the sequence in the loaded .fai, < 0: unknown); nuc_open first"""
+        t, s, e = np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64)
+        if not (len(t) == len(s) == len(e)):
+            raise ValueError("tid, start and end have to be of one length")
+        b = BedBatch()
+        self._chk(self.L.dhts_nuc_intervals(self.h, t.ctypes.data, s.ctypes.data, e.ctypes.data, len(t), C.byref(b)))
+        return self.nuc_batch_columns(b)
+
     def next_batch(self, max_blocks=0, colmask=0x1FFF):
         b = BamBatch()
         self._chk(self.L.dhts_bam_next_batch(self.h, max_blocks, colmask, C.byref(b)))
@@ -802,6 +878,100 @@ class BedScan:
                 data = arena[hc.bytes - base: hc.bytes - base + int(hc.nbytes)].tobytes()
                 out[name] = [data[int(off[r]):int(off[r + 1])] if valid[r] else None for r in range(n)]
         return out
+
+
+class NucRegionError(DhtsError):
+    """the reference's "fasta_nuc: invalid FASTA region" """
+
+
+def fasta_nuc(fasta, bed=None, bin_width=None, region=None, fai=None, bed_index=None, include_seq=False, columns=None, device=0, max_rows=0, stats=None):
+    """fasta_nuc(fasta, bed_path := / bin_width :=, region :=, index_path :=, bed_index_path :=, include_seq :=): {"n_rows", column: python
+    list with None for NULL} for the projected columns (default all of NUC_COLUMNS; seq only with include_seq).  fasta: a path
+    (uncompressed or BGZF) or, with fai given as bytes, the file's bytes; fai: the .fai's path (default fasta + ".fai"; it is never built here) or its bytes.  bed: a path (uncompressed,
+    BGZF or plain gzip) or the BED's bytes; bed_index: the tabix index of a BGZF BED, used with a region (default bed + ".tbi" / ".csi"; without
+    one the whole BED is read and filtered).  max_rows: rows per batch in bins mode, BED blocks per batch in BED mode.  stats (a dict)
+    receives resident_bytes (of the FASTA) and n_batches."""
+    fasta_is_bytes = isinstance(fasta, (bytes, bytearray, memoryview, np.ndarray))
+    if not fasta_is_bytes and not fasta:
+        raise DhtsError("fasta_nuc requires a FASTA path")
+    if (bed is None) == (bin_width is None):
+        raise DhtsError("fasta_nuc requires exactly one of bed_path or bin_width")
+    if bin_width is not None and bin_width <= 0:
+        raise DhtsError("fasta_nuc bin_width must be > 0")
+    if isinstance(fai, (bytes, bytearray)):
+        fai_bytes = bytes(fai)
+    else:
+        fp = fai or (None if fasta_is_bytes else os.fspath(fasta) + ".fai")
+        if fp is None or not os.path.exists(fp):
+            raise DhtsError("fasta_nuc: failed to open FASTA index")
+        fai_bytes = open(fp, "rb").read()
+    ctx, bctx = Context(device), None
+    try:
+        ctx.fasta_load_index(fai_bytes)
+        if region and not fasta_is_bytes and not _is_bgzf(fasta):
+            # only what the region reads is staged: its own window for bins, the whole sequence for BED rows (they may reach past the region)
+            ctx._chk(ctx.L.dhts_nuc_open_region(ctx.h, os.fsencode(fasta), region.encode() if isinstance(region, str) else region, int(bed is not None)))
+        else:
+            ctx.open(fasta)
+            ctx.L.dhts_bgzf_index(ctx.h)
+        ctx.nuc_open(include_seq)
+        if region and not ctx.nuc_set_region(region):
+            raise NucRegionError("fasta_nuc: invalid FASTA region")
+        if columns is not None:
+            ctx.nuc_set_projection(columns)
+        names = [NUC_COLUMNS[i] for i in ctx.nuc_projection]
+        out = {"n_rows": 0}
+        out.update({k: [] for k in names})
+        if bed is not None:
+            is_path = not isinstance(bed, (bytes, bytearray, memoryview, np.ndarray))
+            if is_path and not os.path.exists(bed):
+                raise DhtsError("fasta_nuc: failed to open BED file")
+            index = None
+            if region and is_path and _is_bgzf(bed):                          # HTS_IDX_SILENT_FAIL: no index, no iterator
+                for p in ([bed_index] if bed_index else [os.fspath(bed) + ".tbi", os.fspath(bed) + ".csi"]):
+                    if os.path.exists(p):
+                        index = open(p, "rb").read()
+                        break
+            bctx = Context(device)
+            sparse = None
+            if index is not None:
+                ibuf = np.frombuffer(index, dtype=np.uint8)
+                beg, end, cnt = np.zeros(4096, np.uint64), np.zeros(4096, np.uint64), C.c_int64(0)
+                rb = region.encode() if isinstance(region, str) else region
+                rc = bctx._chk(bctx.L.dhts_bed_region_segments(bctx.h, rb, ibuf.ctypes.data, ibuf.nbytes, beg.ctypes.data, end.ctypes.data, 4096, C.byref(cnt)))
+                if rc == 1:
+                    raise BedIteratorError("fasta_nuc: failed to create BED region iterator")
+                if cnt.value >= 0:
+                    sparse = (beg[:cnt.value].copy(), end[:cnt.value].copy())
+            if sparse is not None:
+                bctx.open_segments(bed, 0, *sparse)
+            else:
+                bctx.open(bed)
+            bctx.L.dhts_bgzf_index(bctx.h)
+            sc = BedScan(bctx)
+            if index is not None:
+                sc.set_region(region if isinstance(region, str) else region.decode())
+                if not sc.load_index(index):
+                    raise BedIteratorError("fasta_nuc: failed to create BED region iterator")
+        nb = 0
+        while True:
+            b = ctx.nuc_next_bed(bctx, max_rows) if bed is not None else ctx.nuc_next_bins(bin_width, max_rows)
+            nb += 1
+            if b.n_rows:
+                out["n_rows"] += int(b.n_rows)
+                for k, v in ctx.nuc_batch_columns(b).items():
+                    if k != "n_rows":
+                        out[k].extend(v)
+            if b.status != 0:
+                break
+        if stats is not None:
+            stats["resident_bytes"] = ctx.resident_bytes()
+            stats["n_batches"] = nb
+        return out
+    finally:
+        if bctx is not None:
+            bctx.close()
+        ctx.close()
 
 
 def _is_bgzf(path):

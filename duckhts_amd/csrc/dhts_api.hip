@@ -14,6 +14,7 @@
 #include "sam_text.hip"
 #include "fastq_text.hip"
 #include "fasta_index.hip"
+#include "fasta_nuc.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -186,6 +187,16 @@ struct TabixState {
     DevBuf ne, coldev, valid, fixed, len, off, bytes, patch, ctr, pval, pok, tok_off, tok_bytes;
     DevBuf a_np, a_kb, a_vb, a_po, a_ko, a_vo, a_valid, a_keyoff, a_valoff, a_kbytes, a_vbytes;
 };
+// fasta_nuc (fasta_nuc.hip, dhts_fasta_nuc.inc): the index on the device (entries, names, the hash table of the names), the region, the
+// position of a bins scan, the interval table and the columns of the last batch
+struct NucState {
+    bool open = false, include_seq = false; std::vector<int32_t> proj; std::vector<dhts_col> out;
+    bool has_region = false; int32_t rg_tid = -1; int64_t rg_beg = 0, rg_end = 0;
+    const uint8_t *text = nullptr; uint64_t text_len = 0; uint32_t nseq = 0, hmask = 0;
+    int64_t bins_bw = 0; uint64_t bins_next = 0, bins_total = 0;
+    DevBuf ents, names, table, cum, in_tid, in_start, in_end, tmp, keep, rank, src, rows, err, npieces, piece_off, counts;
+    DevBuf name_len, name_off, name_bytes, name_valid, seq_len, seq_off32, seq_off64, seq_valid, ones, fixed[NUC_N_COLS];
+};
 struct dhts_ctx;
 static void stop_stager(dhts_ctx *c);
 struct dhts_ctx {
@@ -219,6 +230,7 @@ struct dhts_ctx {
     int fastq = 0;                    // read_bam on raw reads (fastq_text.hip; sam_text is set as well): 1 FASTQ, 2 FASTA
     FastaState fa;
     BedState bed;
+    NucState nuc;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
     DevBuf f_len, f_flag, f_psum, f_rank, f_mark, f_next, f_plus, f_exit, f_entry, f_stop, f_isstart, f_recrank, f_recline;
@@ -444,7 +456,7 @@ static void stop_stager(dhts_ctx *c) {
 }
 static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
-    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
+    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
@@ -498,6 +510,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bcf_scan.inc"
 #include "dhts_bed_scan.inc"
 #include "dhts_tabix_scan.inc"
+#include "dhts_fasta_nuc.inc"
 #include "dhts_fetch.inc"
 
 }  // extern "C"

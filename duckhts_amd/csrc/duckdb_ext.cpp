@@ -1685,6 +1685,202 @@ extern "C" __attribute__((visibility("default"))) void register_read_bed_functio
     API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
 }
 
+// ---- fasta_nuc (src/interval_udf.c:451-836, 854-876): one thread, BED file order or bin order, vector_size rows per chunk --------------------
+// bind checks the arguments and reads the .fai (index_path, else <fasta>.fai; unlike fai_load3_format a missing one is never built: it is
+// the bind error); init stages the FASTA -- with a region of an uncompressed file only what the region reads -- puts the index on the
+// device, resolves the region and prepares the BED context (with a region and a tabix index: the index windows only); the scan fills
+// chunks from device batches read back by dhts_nuc_batch_fetch.  The BED lines' columns never visit the host.
+static const char *const kNucCols[DHTS_NUC_COL_COUNT] = {"chrom", "start", "end", "pct_at", "pct_gc", "num_a", "num_c", "num_g", "num_t", "num_n", "num_other", "seq_len", "seq"};
+static inline bool nuc_is_varchar(idx_t c) { return c == DHTS_NUC_CHROM || c == DHTS_NUC_SEQ; }
+struct NucBind { std::string fasta, bed, region, bed_index_path, fai; bool has_bed = false, has_region = false, include_seq = false; int64_t bin_width = 0; };
+struct NucScanState {
+    dhts_ctx *ctx = nullptr, *bed = nullptr; void *arena = nullptr; uint64_t arena_cap = 0; int64_t bin_width = 0;
+    std::vector<idx_t> column_ids; std::vector<int> slot;
+    std::vector<dhts_col> host; int64_t n = 0, pos = 0; int32_t status = 0; bool done = false;
+    ~NucScanState() { if (arena) dhts_host_free(arena); if (bed) dhts_destroy(bed); if (ctx) dhts_destroy(ctx); }
+};
+static void destroy_nuc_bind(void *p) { delete (NucBind *)p; }
+static void destroy_nuc_scan(void *p) { delete (NucScanState *)p; }
+static bool file_is_bgzf(const std::string &path) {
+    uint8_t h[18] = {0}; size_t got = 0;
+    if (FILE *f = fopen(path.c_str(), "rb")) { got = fread(h, 1, 18, f); fclose(f); }
+    return got == 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C';
+}
+static void fasta_nuc_bind(duckdb_bind_info info) {
+    auto set_error = API(void, duckdb_bind_set_error, duckdb_bind_info, const char *);
+    auto dfree = API(void, duckdb_free, void *);
+    duckdb_value pv = API(duckdb_value, duckdb_bind_get_parameter, duckdb_bind_info, idx_t)(info, 0);
+    char *fasta_path = API(char *, duckdb_get_varchar, duckdb_value)(pv);
+    API(void, duckdb_destroy_value, duckdb_value *)(&pv);
+    if (!fasta_path || fasta_path[0] == '\0') { set_error(info, "fasta_nuc requires a FASTA path"); if (fasta_path) dfree(fasta_path); return; }   // interval_udf.c:479-483
+    NucBind *b = new NucBind();
+    b->fasta = fasta_path; dfree(fasta_path);
+    if (char *x = get_named_varchar(info, "bed_path")) { b->bed = x; b->has_bed = true; dfree(x); }
+    bool has_bin_width = false;
+    {
+        duckdb_value v = API(duckdb_value, duckdb_bind_get_named_parameter, duckdb_bind_info, const char *)(info, "bin_width");
+        if (v && !API(bool, duckdb_is_null_value, duckdb_value)(v)) { b->bin_width = API(int64_t, duckdb_get_int64, duckdb_value)(v); has_bin_width = true; }
+        if (v) API(void, duckdb_destroy_value, duckdb_value *)(&v);
+    }
+    if (b->has_bed == has_bin_width) { set_error(info, "fasta_nuc requires exactly one of bed_path or bin_width"); delete b; return; }        // :499-504
+    if (has_bin_width && b->bin_width <= 0) { set_error(info, "fasta_nuc bin_width must be > 0"); delete b; return; }                          // :505-510
+    std::string index_path;
+    if (char *x = get_named_varchar(info, "region")) { b->region = x; b->has_region = x[0] != '\0'; dfree(x); }
+    if (char *x = get_named_varchar(info, "index_path")) { index_path = x; dfree(x); }
+    if (char *x = get_named_varchar(info, "bed_index_path")) { b->bed_index_path = x; dfree(x); }
+    b->include_seq = get_named_bool(info, "include_seq") != 0;
+    // fai_load3_format (:532) opens the FASTA and its index; it would BUILD a missing index, this project never does
+    if (!file_exists(b->fasta) || !read_file(index_path.empty() ? b->fasta + ".fai" : index_path, b->fai)) { set_error(info, "fasta_nuc: failed to open FASTA index"); delete b; return; }
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto add = API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR), t_bigint = mk(DUCKDB_TYPE_BIGINT), t_double = mk(DUCKDB_TYPE_DOUBLE);
+    for (idx_t c = 0; c < (idx_t)(b->include_seq ? DHTS_NUC_COL_COUNT : DHTS_NUC_SEQ); c++)                                                  // :451-473
+        add(info, kNucCols[c], nuc_is_varchar(c) ? t_varchar : (c == DHTS_NUC_PCT_AT || c == DHTS_NUC_PCT_GC) ? t_double : t_bigint);
+    rm(&t_varchar); rm(&t_bigint); rm(&t_double);
+    API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, b, destroy_nuc_bind);
+}
+static void fasta_nuc_init(duckdb_init_info info) {
+    NucBind *bind = (NucBind *)API(void *, duckdb_init_get_bind_data, duckdb_init_info)(info);
+    auto init_error = API(void, duckdb_init_set_error, duckdb_init_info, const char *);
+    NucScanState *g = new NucScanState();
+    g->bin_width = bind->bin_width;
+    g->ctx = dhts_create(device_list()[0]);
+    if (!g->ctx) { init_error(info, "fasta_nuc: no MI355X (gfx950) device available; this build has no CPU fallback"); delete g; return; }
+    auto fail_ctx = [&]() { const std::string m = std::string("fasta_nuc: ") + dhts_error(g->ctx); init_error(info, m.c_str()); delete g; };
+    if (dhts_fasta_load_index(g->ctx, bind->fai.data(), bind->fai.size()) != 0) { init_error(info, "fasta_nuc: failed to load FASTA index"); delete g; return; }   // :578-583
+    if (bind->has_region && !file_is_bgzf(bind->fasta)) {
+        // an uncompressed file: only what the region reads -- its own window for bins, its whole sequence for BED rows, which may reach past it
+        if (dhts_nuc_open_region(g->ctx, bind->fasta.c_str(), bind->region.c_str(), bind->has_bed ? 1 : 0) != 0) { init_error(info, "fasta_nuc: failed to load FASTA index"); delete g; return; }
+    } else {
+        if (dhts_open_path(g->ctx, bind->fasta.c_str()) != 0) { init_error(info, "fasta_nuc: failed to load FASTA index"); delete g; return; }
+        (void)dhts_bgzf_index(g->ctx);
+    }
+    if (dhts_nuc_open(g->ctx, bind->include_seq ? 1 : 0) != 0) { fail_ctx(); return; }
+    if (bind->has_region) {
+        const int rc = dhts_nuc_set_region(g->ctx, bind->region.c_str());
+        if (rc != 0) { init_error(info, "fasta_nuc: invalid FASTA region"); delete g; return; }                                                // :584-588
+    }
+    if (bind->has_bed) {
+        if (!file_exists(bind->bed)) { init_error(info, "fasta_nuc: failed to open BED file"); delete g; return; }                              // :591-596
+        g->bed = dhts_create(device_list()[0]);
+        if (!g->bed) { init_error(info, "fasta_nuc: no MI355X (gfx950) device available; this build has no CPU fallback"); delete g; return; }
+        // tbx_index_load3 with HTS_IDX_SILENT_FAIL (:598): without an index there is no iterator, the whole BED is read and filtered
+        std::string index; bool have = false, staged = false;
+        if (bind->has_region && file_is_bgzf(bind->bed)) {
+            have = bind->bed_index_path.empty() ? (read_file(bind->bed + ".tbi", index) || read_file(bind->bed + ".csi", index)) : read_file(bind->bed_index_path, index);
+            if (have && index.size() < 4) have = false;
+        }
+        if (have) {
+            uint64_t beg[4096], end[4096]; int64_t cnt = -1;
+            const int rc = dhts_bed_region_segments(g->bed, bind->region.c_str(), index.data(), index.size(), beg, end, 4096, &cnt);
+            if (rc != 0) { init_error(info, "fasta_nuc: failed to create BED region iterator"); delete g; return; }                          // :600-605
+            if (cnt >= 0) {
+                if (dhts_open_path_segments(g->bed, bind->bed.c_str(), 0, beg, end, cnt) != 0) { init_error(info, "fasta_nuc: failed to open BED file"); delete g; return; }
+                staged = true;
+            }
+        }
+        if (!staged && dhts_open_path(g->bed, bind->bed.c_str()) != 0) { init_error(info, "fasta_nuc: failed to open BED file"); delete g; return; }
+        (void)dhts_bgzf_index(g->bed);
+        if (dhts_bed_open(g->bed) != 0) { init_error(info, "fasta_nuc: failed to open BED file"); delete g; return; }
+        if (have) {
+            if (dhts_bed_set_region(g->bed, bind->region.c_str()) != 0 || dhts_bed_load_index(g->bed, index.data(), index.size()) != 0) { init_error(info, "fasta_nuc: failed to create BED region iterator"); delete g; return; }
+        }
+    }
+    const idx_t n = API(idx_t, duckdb_init_get_column_count, duckdb_init_info)(info);
+    std::vector<int32_t> proj;
+    const idx_t ncols = bind->include_seq ? DHTS_NUC_COL_COUNT : DHTS_NUC_SEQ;
+    for (idx_t i = 0; i < n; i++) {
+        const idx_t id = API(idx_t, duckdb_init_get_column_index, duckdb_init_info, idx_t)(info, i);
+        g->column_ids.push_back(id);
+        int at = -1;
+        if (id < ncols) {
+            for (size_t k = 0; k < proj.size(); k++) if (proj[k] == (int32_t)id) at = (int)k;
+            if (at < 0) { at = (int)proj.size(); proj.push_back((int32_t)id); }
+        }
+        g->slot.push_back(at);
+    }
+    if (dhts_nuc_set_projection(g->ctx, proj.data(), (int32_t)proj.size()) != 0) { fail_ctx(); return; }
+    g->host.resize(proj.size() ? proj.size() : 1);
+    API(void, duckdb_init_set_max_threads, duckdb_init_info, idx_t)(info, 1);
+    API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, g, destroy_nuc_scan);
+}
+// the next device batch, read back; false at the end (or on a failure: err set)
+static bool nuc_next(NucScanState *g, std::string &err) {
+    while (g->status == 0) {
+        dhts_nuc_batch b;
+        const int rc = g->bed ? dhts_nuc_next_bed(g->ctx, g->bed, 0, &b) : dhts_nuc_next_bins(g->ctx, g->bin_width, 0, &b);
+        if (rc != 0) { err = dhts_error(g->ctx); return false; }
+        g->status = b.status;
+        if (b.n_rows == 0) continue;
+        const uint64_t need = dhts_nuc_batch_host_bytes(&b);
+        if (need > g->arena_cap) { if (g->arena) dhts_host_free(g->arena); g->arena_cap = need + need / 4 + 4096; g->arena = dhts_host_alloc(g->arena_cap); if (!g->arena) { g->arena_cap = 0; err = "fasta_nuc: out of pinned host memory"; return false; } }
+        if (dhts_nuc_batch_fetch(g->ctx, &b, g->arena, g->arena_cap, g->host.data()) != 0) { err = dhts_error(g->ctx); return false; }
+        g->n = b.n_rows; g->pos = 0;
+        return true;
+    }
+    return false;
+}
+static void fasta_nuc_function(duckdb_function_info info, duckdb_data_chunk output) {
+    NucScanState *g = (NucScanState *)API(void *, duckdb_function_get_init_data, duckdb_function_info)(info);
+    auto set_size = API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t);
+    if (!g || g->done) { set_size(output, 0); return; }
+    const idx_t vector_size = API(idx_t, duckdb_vector_size, void)();
+    auto get_vec = API(duckdb_vector, duckdb_data_chunk_get_vector, duckdb_data_chunk, idx_t);
+    auto assign_len = API(void, duckdb_vector_assign_string_element_len, duckdb_vector, idx_t, const char *, idx_t);
+    auto get_data = API(void *, duckdb_vector_get_data, duckdb_vector);
+    idx_t row_count = 0;
+    while (row_count < vector_size) {
+        if (g->pos >= g->n) {
+            std::string err;
+            if (!nuc_next(g, err)) {
+                g->done = true;
+                if (!err.empty()) { API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, err.c_str()); set_size(output, 0); return; }
+                break;
+            }
+        }
+        const idx_t take = (idx_t)(g->n - g->pos) < vector_size - row_count ? (idx_t)(g->n - g->pos) : vector_size - row_count;
+        for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
+            duckdb_vector vec = get_vec(output, ci);
+            if (g->slot[ci] < 0) { for (idx_t r = 0; r < take; r++) set_null(vec, row_count + r); continue; }
+            const dhts_col &hc = g->host[(size_t)g->slot[ci]];
+            if (!nuc_is_varchar(g->column_ids[ci])) {                                  // BIGINT and DOUBLE: eight bytes either way, never NULL
+                uint64_t *data = (uint64_t *)get_data(vec); const uint64_t *src = (const uint64_t *)hc.fixed;
+                for (idx_t r = 0; r < take; r++) data[row_count + r] = src[g->pos + r];
+            } else {
+                for (idx_t r = 0; r < take; r++) {
+                    const int64_t k = g->pos + (int64_t)r;
+                    if (hc.valid[k]) assign_len(vec, row_count + r, (const char *)hc.bytes + hc.off[k], hc.off[k + 1] - hc.off[k]); else set_null(vec, row_count + r);
+                }
+            }
+        }
+        g->pos += (int64_t)take; row_count += take;
+    }
+    set_size(output, row_count);
+}
+extern "C" __attribute__((visibility("default"))) void register_fasta_nuc_function(duckdb_connection connection) {                     // interval_udf.c:854-876
+    duckdb_table_function tf = API(duckdb_table_function, duckdb_create_table_function, void)();
+    API(void, duckdb_table_function_set_name, duckdb_table_function, const char *)(tf, "fasta_nuc");
+    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
+    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
+    auto named = API(void, duckdb_table_function_add_named_parameter, duckdb_table_function, const char *, duckdb_logical_type);
+    duckdb_logical_type t_varchar = mk(DUCKDB_TYPE_VARCHAR), t_bigint = mk(DUCKDB_TYPE_BIGINT), t_bool = mk(DUCKDB_TYPE_BOOLEAN);
+    API(void, duckdb_table_function_add_parameter, duckdb_table_function, duckdb_logical_type)(tf, t_varchar);
+    named(tf, "bed_path", t_varchar);
+    named(tf, "bin_width", t_bigint);
+    named(tf, "region", t_varchar);
+    named(tf, "index_path", t_varchar);
+    named(tf, "bed_index_path", t_varchar);
+    named(tf, "include_seq", t_bool);
+    rm(&t_varchar); rm(&t_bigint); rm(&t_bool);
+    API(void, duckdb_table_function_set_bind, duckdb_table_function, duckdb_table_function_bind_t)(tf, fasta_nuc_bind);
+    API(void, duckdb_table_function_set_init, duckdb_table_function, duckdb_table_function_init_t)(tf, fasta_nuc_init);
+    API(void, duckdb_table_function_set_function, duckdb_table_function, duckdb_table_function_t)(tf, fasta_nuc_function);
+    API(void, duckdb_table_function_supports_projection_pushdown, duckdb_table_function, bool)(tf, true);
+    API(duckdb_state, duckdb_register_table_function, duckdb_connection, duckdb_table_function)(connection, tf);
+    API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
+}
+
 // ---- read_tabix / read_gtf / read_gff (src/tabix_reader.c): one thread, file order, vector_size rows per chunk ------------------------------
 // Generic bind is the reference's peek at the file (:636-771) on the device: dhts_tabix_sniff + dhts_tabix_resolve_schema, with the meta
 // character and line_skip of the index when there is one; GTF / GFF have their fixed schema.  Init stages the file -- for a single region
@@ -2026,6 +2222,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     if (const char *e = getenv("DHTS_SEQ_FUNCTIONS")) if (atoi(e) == 1) { register_read_fasta_function(conn); register_read_fastq_function(conn); register_fasta_index_function(conn); }
     // read_bed follows fasta_index (src/duckhts.c:59), opt-in as well: DHTS_INTERVAL_FUNCTIONS=1
     if (const char *e = getenv("DHTS_INTERVAL_FUNCTIONS")) if (atoi(e) == 1) register_read_bed_function(conn);
+    // fasta_nuc follows read_bed (src/duckhts.c:59-60), behind a variable of its own: DHTS_NUC_FUNCTIONS=1
+    if (const char *e = getenv("DHTS_NUC_FUNCTIONS")) if (atoi(e) == 1) register_fasta_nuc_function(conn);
     // read_tabix, read_gtf, read_gff close the list (src/duckhts.c:67-69), opt-in: DHTS_TABIX_FUNCTIONS=1
     if (const char *e = getenv("DHTS_TABIX_FUNCTIONS")) if (atoi(e) == 1) { register_read_tabix_function(conn); register_read_gtf_function(conn); register_read_gff_function(conn); }
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);

@@ -447,6 +447,51 @@ int dhts_bed_next_batch(dhts_ctx *, int64_t max_blocks, dhts_bed_batch *out);
 uint64_t dhts_bed_batch_host_bytes(const dhts_bed_batch *b);
 int dhts_bed_batch_fetch(dhts_ctx *, const dhts_bed_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- fasta_nuc -------------------------------------------------------------------------------
+ *   dhts_nuc_open / _set_region        <- fasta_nuc_init, init_fasta_region                           src/interval_udf.c:558-627
+ *   dhts_nuc_next_bins                 <- next_fasta_nuc_bin_interval                                 :684-726
+ *   dhts_nuc_next_bed                  <- next_fasta_nuc_bed_interval, bed_overlap_region             :645-682
+ *   every row                          <- fasta_nuc_scan :728-836: faidx_fetch_seq64(start, end - 1) (htslib faidx.c:914-983),
+ *                                         count_nucleotides :629-643, pct_at / pct_gc :765-768
+ * The 13 columns of add_fasta_nuc_columns (:451-473), in that order.  VARCHAR: chrom, seq; DOUBLE: pct_at, pct_gc; BIGINT: the others.
+ * Rows: end - start <= 0 gives a row without any fetch (counts 0, seq_len = end - start, seq NULL, unknown chrom included); otherwise a
+ * chrom the .fai does not know, line_blen 0 and bases behind the end of the file drop the row, and seq_len is what
+ * faidx_adjust_position(end_adjust = 1) leaves of (start, end - 1).  start and end are always the caller's / the BED's own numbers. */
+enum { DHTS_NUC_CHROM = 0, DHTS_NUC_START, DHTS_NUC_END, DHTS_NUC_PCT_AT, DHTS_NUC_PCT_GC, DHTS_NUC_NUM_A, DHTS_NUC_NUM_C, DHTS_NUC_NUM_G, DHTS_NUC_NUM_T,
+       DHTS_NUC_NUM_N, DHTS_NUC_NUM_OTHER, DHTS_NUC_SEQ_LEN, DHTS_NUC_SEQ, DHTS_NUC_COL_COUNT };
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows may follow, 1 = the last batch                                                               */
+    int32_t n_cols;          /* projected columns, in projection order                                                                     */
+    const dhts_col *cols;    /* host array of n_cols descriptors, DEVICE pointers inside: valid[n_rows]; BIGINT and DOUBLE in fixed
+                                (8 bytes), VARCHAR in off[n_rows + 1] / bytes                                                              */
+} dhts_nuc_batch;
+/* stages what a query with `region` reads of the FASTA at `path`, by the loaded .fai (dhts_fasta_load_index first): of an uncompressed file
+ * the byte window of the region's bases -- with whole_sequence, for BED mode, of the whole sequence the region names, since a BED row
+ * that overlaps the region may reach past it -- of a BGZF file everything.  ONE region: commas are thousands separators, not a list. */
+int dhts_nuc_open_region(dhts_ctx *fasta, const char *path, const char *region, int whole_sequence);
+/* after the FASTA is resident (dhts_open_path / dhts_open_host / dhts_nuc_open_region) and dhts_fasta_load_index: the index goes to
+ * the device.  Fails with a message that names the FASTA index when none is loaded.  include_seq adds the 13th column. */
+int dhts_nuc_open(dhts_ctx *fasta, int include_seq);
+/* ONE region as init_fasta_region reads it: fai_parse_region with flags 0, then fai_adjust_region.  Returns 1 for a region the reference
+ * calls invalid (unknown name, malformed, or one fai_adjust_region had to move: a start behind the sequence, an explicit end behind it).
+ * NULL / "" clears.  Bins mode walks the region; BED mode keeps the rows that pass bed_overlap_region. */
+int dhts_nuc_set_region(dhts_ctx *fasta, const char *region);
+/* DHTS_NUC_* ids, each once (DHTS_NUC_SEQ only with include_seq); default all; n = 0: only n_rows (count(*)).  With none of pct_at ..
+ * num_other projected the bases are not read. */
+int dhts_nuc_set_projection(dhts_ctx *fasta, const int32_t *col_ids, int32_t n);
+/* the next <= max_rows bins (0 = default) of the region or of every sequence, in order; built on the device from the bin number */
+int dhts_nuc_next_bins(dhts_ctx *fasta, int64_t bin_width, int64_t max_rows, dhts_nuc_batch *out);
+/* the rows of the next batch of `bed`, a second context on the same device prepared as for read_bed (dhts_bed_open; with a region and a
+ * tabix index also dhts_bed_set_region + dhts_bed_load_index).  Lines are read by fasta_nuc's rules: fewer than three fields, or a start
+ * or end that is not a whole number, skip the line.  chrom is resolved against the .fai on the device. */
+int dhts_nuc_next_bed(dhts_ctx *fasta, dhts_ctx *bed, int64_t max_blocks, dhts_nuc_batch *out);
+/* rows for n intervals in host arrays, tid = index of the sequence in the .fai (< 0: a chrom it does not know) */
+int dhts_nuc_intervals(dhts_ctx *fasta, const int32_t *tid, const int64_t *start, const int64_t *end, int64_t n, dhts_nuc_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst */
+uint64_t dhts_nuc_batch_host_bytes(const dhts_nuc_batch *b);
+int dhts_nuc_batch_fetch(dhts_ctx *fasta, const dhts_nuc_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
 /* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
  * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and
  * uncompressed text are read.  Bind is dhts_tabix_set_conf + dhts_tabix_sniff + dhts_tabix_resolve_schema + dhts_tabix_set_schema;

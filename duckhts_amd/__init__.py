@@ -98,6 +98,27 @@ class TabixSchema(C.Structure):
     _fields_ = [("n_cols", C.c_int32), ("skip_header_line", C.c_int32), ("types", C.c_int32 * TABIX_MAX_COLS), ("names", C.c_char_p * TABIX_MAX_COLS)]
 
 
+class UdfArg(C.Structure):
+    _fields_ = [("off", C.c_void_p), ("len", C.c_void_p), ("bytes", C.c_void_p), ("nbytes", C.c_uint64), ("valid", C.c_void_p), ("child_valid", C.c_void_p),
+                ("fixed", C.c_void_p), ("width", C.c_int32), ("is_const", C.c_int32)]
+
+
+class UdfResult(C.Structure):
+    _fields_ = [("op", C.c_int32), ("type", C.c_int32), ("is_list", C.c_int32), ("n_fields", C.c_int32), ("n_rows", C.c_int64), ("col", BcfCol), ("len", C.c_void_p)]
+
+
+class UdfKmers(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("status", C.c_int32), ("k", C.c_int32), ("next", C.c_uint64), ("total", C.c_uint64), ("row", C.c_void_p), ("pos", C.c_void_p),
+                ("kmer", BcfCol), ("hash", C.c_void_p), ("hash_valid", C.c_void_p)]
+
+
+# the scalar functions of the reference's k-mer family in registration order (src/kmer_udf.c:1223-1254 without the table function): index = DHTS_UDF_* id
+UDF_OPS = ["seq_revcomp", "seq_canonical", "seq_hash_2bit", "seq_encode_4bit", "seq_decode_4bit", "seq_gc_content",
+           "cigar_has_soft_clip", "cigar_has_hard_clip", "cigar_left_soft_clip", "cigar_right_soft_clip", "cigar_query_length", "cigar_aligned_query_length",
+           "cigar_reference_length", "cigar_has_op", "sam_flag_bits", "sam_flag_has", "is_forward_aligned",
+           "is_paired", "is_proper_pair", "is_unmapped", "is_next_segment_unmapped", "is_reverse_complemented", "is_next_segment_reverse_complemented",
+           "is_first_segment", "is_last_segment", "is_secondary", "is_qc_fail", "is_duplicate", "is_supplementary"]
+_UDF_TEXT_OPS = 14           # the ids below take a VARCHAR (or list) first argument, the others an integer column
 TABIX_GENERIC, TABIX_GTF, TABIX_GFF = 0, 1, 2
 T_INTEGER, T_BIGINT, T_DOUBLE, T_VARCHAR = 4, 5, 11, 17
 GXF_COLUMNS = ["seqname", "source", "feature", "start", "end", "score", "strand", "frame", "attributes", "attributes_map"]
@@ -124,7 +145,8 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_bed_open", "dhts_bed_set_projection", "dhts_bed_set_region", "dhts_bed_load_index", "dhts_bed_region_segments", "dhts_bed_next_batch", "dhts_bed_batch_host_bytes", "dhts_bed_batch_fetch",
            "dhts_nuc_open_region", "dhts_nuc_open", "dhts_nuc_set_region", "dhts_nuc_set_projection", "dhts_nuc_next_bins", "dhts_nuc_next_bed", "dhts_nuc_intervals", "dhts_nuc_batch_host_bytes", "dhts_nuc_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
-           "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch"]
+           "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
+           "dhts_udf_upload", "dhts_udf_apply", "dhts_udf_result_host_bytes", "dhts_udf_fetch", "dhts_udf_seq_kmers", "dhts_udf_kmers_host_bytes", "dhts_udf_kmers_fetch"]
 
 
 def lib():
@@ -230,6 +252,15 @@ def lib():
         L.dhts_tabix_batch_host_bytes.restype = C.c_uint64
         L.dhts_tabix_batch_host_bytes.argtypes = [C.POINTER(TabixBatch)]
         L.dhts_tabix_batch_fetch.argtypes = [C.c_void_p, C.POINTER(TabixBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol), C.POINTER(TabixMap)]
+        L.dhts_udf_upload.argtypes = [C.c_void_p, C.c_int, C.POINTER(UdfArg), C.c_int64, C.POINTER(UdfArg)]
+        L.dhts_udf_apply.argtypes = [C.c_void_p, C.c_int, C.POINTER(UdfArg), C.POINTER(UdfArg), C.c_int64, C.POINTER(UdfResult)]
+        L.dhts_udf_result_host_bytes.restype = C.c_uint64
+        L.dhts_udf_result_host_bytes.argtypes = [C.POINTER(UdfResult)]
+        L.dhts_udf_fetch.argtypes = [C.c_void_p, C.POINTER(UdfResult), C.c_void_p, C.c_uint64, C.POINTER(UdfResult)]
+        L.dhts_udf_seq_kmers.argtypes = [C.c_void_p, C.POINTER(UdfArg), C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint64, C.POINTER(UdfKmers)]
+        L.dhts_udf_kmers_host_bytes.restype = C.c_uint64
+        L.dhts_udf_kmers_host_bytes.argtypes = [C.POINTER(UdfKmers)]
+        L.dhts_udf_kmers_fetch.argtypes = [C.c_void_p, C.POINTER(UdfKmers), C.c_void_p, C.c_uint64, C.POINTER(UdfKmers)]
         _LIB = L
     return _LIB
 
@@ -632,6 +663,153 @@ class Context:
         b = BedBatch()
         self._chk(self.L.dhts_nuc_intervals(self.h, t.ctypes.data, s.ctypes.data, e.ctypes.data, len(t), C.byref(b)))
         return self.nuc_batch_columns(b)
+
+    # ---- seq_* / cigar_* / SAM flag functions on device columns (dhts_udf_*) ----
+    def udf_upload(self, values, slot=0, kind="str", const=False, reserve=0):
+        """host values -> a device argument column (UdfArg).  kind "str": bytes / str / None per row (reserve = extra reserved bytes behind
+        every row, the layout of a batch column); "list": a list of 4-bit codes per row (None = NULL row, None inside = NULL child); "int":
+        integers / None (BIGINT).  const: `values` is ONE value that stands for every row."""
+        vals = [values] if const else list(values)
+        n = len(vals)
+        h = UdfArg()
+        h.is_const = int(const)
+        valid = np.array([v is not None for v in vals], np.uint8)
+        keep = [valid]
+        if not valid.all():
+            h.valid = valid.ctypes.data
+        if kind == "int":
+            fixed = np.array([0 if v is None else v for v in vals], np.int64)
+            keep.append(fixed)
+            h.fixed, h.width = fixed.ctypes.data, -8
+        else:
+            rows, cvalid = [], []
+            for v in vals:
+                if kind == "list":
+                    v = [] if v is None else list(v)
+                    cvalid.append(bytes(x is not None for x in v))
+                    rows.append(bytes(0 if x is None else x for x in v))
+                else:
+                    rows.append(b"" if v is None else (v.encode() if isinstance(v, str) else bytes(v)))
+            ln = np.array([len(r) for r in rows], np.uint32)
+            off = np.zeros(n + 1, np.uint32)
+            off[1:] = np.cumsum(ln.astype(np.uint64) + np.uint64(reserve))
+            pad = b"\xee" * reserve
+            data = np.frombuffer(b"".join(r + pad for r in rows) + b"\0", np.uint8)
+            keep += [ln, off, data]
+            h.off, h.bytes, h.nbytes = off.ctypes.data, data.ctypes.data, len(data) - 1
+            if reserve:
+                h.len = ln.ctypes.data
+            if kind == "list" and not all(all(c) for c in cvalid):
+                cv = np.frombuffer(b"".join(c + b"\1" * reserve for c in cvalid) + b"\0", np.uint8)
+                keep.append(cv)
+                h.child_valid = cv.ctypes.data
+        d = UdfArg()
+        self._chk(self.L.dhts_udf_upload(self.h, slot, C.byref(h), 0 if const else n, C.byref(d)))
+        d._n = n
+        return d
+
+    def _udf_arg(self, col, slot, width):
+        if isinstance(col, UdfArg):
+            return col
+        a = UdfArg()
+        if isinstance(col, StrCol):                       # a batch's own column: the four pointers as they are
+            a.off, a.len, a.bytes, a.nbytes = col.off, col.len, col.bytes, col.nbytes
+            return a
+        if isinstance(col, int) and width:               # a device pointer to integers of |width| bytes (a batch's flag: width = 2)
+            a.fixed, a.width = col, width
+            return a
+        return self.udf_upload(col, slot, kind="int" if isinstance(col, int) else "str", const=True)
+
+    def udf(self, op, col, arg=None, n_rows=None, width=0, fetch=True):
+        """op(col[, arg]) on the device.  col: a batch's seq / cigar / qname column (StrCol) or its flag pointer (width = 2), with n_rows =
+        the batch's; or an uploaded UdfArg.  arg, for cigar_has_op and sam_flag_has: a UdfArg / batch column, or one str / int for every row.
+        Returns python values (None = NULL), or with fetch = False the UdfResult whose device pointers live until the next udf call."""
+        opid = UDF_OPS.index(op) if isinstance(op, str) else int(op)
+        a0 = self._udf_arg(col, 0, width)
+        n = getattr(a0, "_n", None) if n_rows is None else n_rows
+        if n is None:
+            raise ValueError("udf on a batch column needs n_rows")
+        a1 = None if arg is None else self._udf_arg(arg, 1, 0)
+        r = UdfResult()
+        self._chk(self.L.dhts_udf_apply(self.h, opid, C.byref(a0), None if a1 is None else C.byref(a1), int(n), C.byref(r)))
+        return self.udf_fetch(r) if fetch else r
+
+    def udf_as_arg(self, r):
+        """a LIST / VARCHAR result as the argument of the next call (seq_decode_4bit(seq_encode_4bit(x)))"""
+        a = UdfArg()
+        a.off, a.len, a.bytes, a.nbytes, a.valid = r.col.off, r.len, r.col.bytes, r.col.nbytes, r.col.valid
+        a._n = int(r.n_rows)
+        return a
+
+    def udf_fetch(self, r, raw=False):
+        """one result column as python values through dhts_udf_fetch: bytes, int, float (its bits are the device's), bool, a list of codes,
+        12 bools for sam_flag_bits; None = NULL.  raw: the dict of numpy arrays instead (valid, off, len, bytes / fixed)."""
+        n = int(r.n_rows)
+        need = int(self.L.dhts_udf_result_host_bytes(C.byref(r)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        h = UdfResult()
+        self._chk(self.L.dhts_udf_fetch(self.h, C.byref(r), arena.ctypes.data, need, C.byref(h)))
+        if n == 0:
+            return {"n_rows": 0} if raw else []
+        base = arena.ctypes.data
+        valid = arena[h.col.valid - base: h.col.valid - base + n]
+        if h.is_list or h.type == T_VARCHAR:
+            off = arena[h.col.off - base: h.col.off - base + 4 * (n + 1)].view(np.uint32)
+            data = arena[h.col.bytes - base: h.col.bytes - base + int(h.col.nbytes)]
+            ln = (off[1:] - off[:-1]) if h.is_list else arena[h.len - base: h.len - base + 4 * n].view(np.uint32)
+            if raw:
+                return {"n_rows": n, "valid": valid, "off": off, "len": ln, "bytes": data}
+            blob = data.tobytes()
+            if h.is_list:
+                return [list(blob[int(off[i]):int(off[i]) + int(ln[i])]) if valid[i] else None for i in range(n)]
+            return [blob[int(off[i]):int(off[i]) + int(ln[i])] if valid[i] else None for i in range(n)]
+        if h.type == 1:                                   # BOOLEAN
+            nf = max(int(h.n_fields), 1)
+            b = arena[h.col.fixed - base: h.col.fixed - base + n * nf].reshape(nf, n)
+            if raw:
+                return {"n_rows": n, "valid": valid, "fixed": b}
+            if nf > 1:
+                return [[bool(b[k, i]) for k in range(nf)] if valid[i] else None for i in range(n)]
+            return [bool(b[0, i]) if valid[i] else None for i in range(n)]
+        vals = arena[h.col.fixed - base: h.col.fixed - base + 8 * n].view({5: np.int64, 9: np.uint64, 11: np.float64}[int(h.type)])
+        if raw:
+            return {"n_rows": n, "valid": valid, "fixed": vals}
+        return [v if valid[i] else None for i, v in enumerate(vals.tolist())]
+
+    def udf_seq_kmers(self, col, k, canonical=False, text=True, hash=False, max_rows=0, n_rows=None):
+        """every k-mer of the column, max_rows per call of dhts_udf_seq_kmers until the end: {"row", "pos"[, "kmer"][, "hash"]: lists}"""
+        a = self._udf_arg(col, 0, 0)
+        n = getattr(a, "_n", None) if n_rows is None else n_rows
+        out = {"row": [], "pos": []}
+        if text:
+            out["kmer"] = []
+        if hash:
+            out["hash"] = []
+        nxt = 0
+        while True:
+            b = UdfKmers()
+            self._chk(self.L.dhts_udf_seq_kmers(self.h, C.byref(a), int(n), int(k), int(canonical), int(text), int(hash), int(max_rows), nxt, C.byref(b)))
+            m = int(b.n_rows)
+            if m:
+                need = int(self.L.dhts_udf_kmers_host_bytes(C.byref(b)))
+                arena = np.zeros(max(need, 8), np.uint8)
+                h = UdfKmers()
+                self._chk(self.L.dhts_udf_kmers_fetch(self.h, C.byref(b), arena.ctypes.data, need, C.byref(h)))
+                base = arena.ctypes.data
+                out["row"] += arena[h.row - base: h.row - base + 8 * m].view(np.int64).tolist()
+                out["pos"] += arena[h.pos - base: h.pos - base + 8 * m].view(np.int64).tolist()
+                if text:
+                    v = arena[h.kmer.valid - base: h.kmer.valid - base + m]
+                    off = arena[h.kmer.off - base: h.kmer.off - base + 4 * (m + 1)].view(np.uint32)
+                    blob = arena[h.kmer.bytes - base: h.kmer.bytes - base + int(h.kmer.nbytes)].tobytes()
+                    out["kmer"] += [blob[int(off[i]):int(off[i + 1])] if v[i] else None for i in range(m)]
+                if hash:
+                    hv = arena[h.hash_valid - base: h.hash_valid - base + m]
+                    hs = arena[h.hash - base: h.hash - base + 8 * m].view(np.uint64).tolist()
+                    out["hash"] += [x if hv[i] else None for i, x in enumerate(hs)]
+            if b.status != 0 or (m == 0 and b.next == nxt):
+                return out
+            nxt = int(b.next)
 
     def next_batch(self, max_blocks=0, colmask=0x1FFF):
         b = BamBatch()
@@ -1472,6 +1650,46 @@ def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, s
             else:
                 out[k] = [x for v in vals for x in v]
         return out
+    finally:
+        ctx.close()
+
+
+def _udf_call(op, values, arg=None, device=0):
+    ctx = Context(device)
+    try:
+        kind = "list" if op == "seq_decode_4bit" else "int" if UDF_OPS.index(op) >= _UDF_TEXT_OPS else "str"
+        a0 = ctx.udf_upload(values, 0, kind=kind)
+        if arg is not None and not isinstance(arg, (str, bytes, int)):
+            arg = ctx.udf_upload(arg, 1, kind="int" if op == "sam_flag_has" else "str")
+        return ctx.udf(op, a0, arg)
+    finally:
+        ctx.close()
+
+
+def _udf_function(op, two):
+    if two:
+        def f(values, arg, device=0):
+            return _udf_call(op, values, arg, device)
+    else:
+        def f(values, device=0):
+            return _udf_call(op, values, None, device)
+    f.__name__ = f.__qualname__ = op
+    f.__doc__ = (f"{op} of the reference (src/kmer_udf.c) for a list of values, evaluated on the device: upload, one kernel, fetch.  None is NULL."
+                 + ("  The second argument is one value for every row, or a list." if two else ""))
+    return f
+
+
+for _op in UDF_OPS:
+    globals()[_op] = _udf_function(_op, _op in ("cigar_has_op", "sam_flag_has"))
+del _op
+
+
+def seq_kmers(strings, k, canonical=False, hash=False, text=True, max_rows=0, device=0):
+    """seq_kmers over a list of sequences: {"row": index of the sequence, "pos": 1-based, "kmer": bytes (None: a canonical k-mer with a byte
+    outside ACGTN), "hash": seq_hash_2bit(kmer) with hash = True (k <= 32)}"""
+    ctx = Context(device)
+    try:
+        return ctx.udf_seq_kmers(ctx.udf_upload(strings, 0), k, canonical=canonical, text=text, hash=hash, max_rows=max_rows)
     finally:
         ctx.close()
 

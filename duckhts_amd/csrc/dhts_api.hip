@@ -15,6 +15,7 @@
 #include "fastq_text.hip"
 #include "fasta_index.hip"
 #include "fasta_nuc.hip"
+#include "seq_udf.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -197,6 +198,13 @@ struct NucState {
     DevBuf ents, names, table, cum, in_tid, in_start, in_end, tmp, keep, rank, src, rows, err, npieces, piece_off, counts;
     DevBuf name_len, name_off, name_bytes, name_valid, seq_len, seq_off32, seq_off64, seq_valid, ones, fixed[NUC_N_COLS];
 };
+// seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
+// turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
+struct UdfState {
+    DevBuf up[2][6];                                               // off, len, bytes, valid, child_valid, fixed
+    struct Res { DevBuf valid, fixed, len, off, bytes; } res[2]; int cur = 0;
+    DevBuf clen, cnt, cum, k_row, k_pos, k_off, k_bytes, k_valid, k_hash, k_hvalid;
+};
 struct dhts_ctx;
 static void stop_stager(dhts_ctx *c);
 struct dhts_ctx {
@@ -231,6 +239,7 @@ struct dhts_ctx {
     FastaState fa;
     BedState bed;
     NucState nuc;
+    UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
     DevBuf f_len, f_flag, f_psum, f_rank, f_mark, f_next, f_plus, f_exit, f_entry, f_stop, f_isstart, f_recrank, f_recline;
@@ -511,6 +520,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bed_scan.inc"
 #include "dhts_tabix_scan.inc"
 #include "dhts_fasta_nuc.inc"
+#include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 
 }  // extern "C"

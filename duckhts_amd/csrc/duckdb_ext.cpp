@@ -2202,6 +2202,8 @@ extern "C" __attribute__((visibility("default"))) void register_read_tabix_funct
 extern "C" __attribute__((visibility("default"))) void register_read_gtf_function(duckdb_connection connection) { register_tabix_tf(connection, "read_gtf", gtf_read_bind); }
 extern "C" __attribute__((visibility("default"))) void register_read_gff_function(duckdb_connection connection) { register_tabix_tf(connection, "read_gff", gff_read_bind); }
 
+#include "duckdb_udf.inc"
+
 extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(duckdb_extension_info info, struct duckdb_extension_access *access) {
     // duckdb_extension.h:1151-1158,1182-1194: fetch the API table, connect, register, disconnect
     const void *api = access->get_api(info, DUCKHTS_API_VERSION);
@@ -2224,6 +2226,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     if (const char *e = getenv("DHTS_INTERVAL_FUNCTIONS")) if (atoi(e) == 1) register_read_bed_function(conn);
     // fasta_nuc follows read_bed (src/duckhts.c:59-60), behind a variable of its own: DHTS_NUC_FUNCTIONS=1
     if (const char *e = getenv("DHTS_NUC_FUNCTIONS")) if (atoi(e) == 1) register_fasta_nuc_function(conn);
+    // the k-mer family follows tabix_index and precedes read_tabix (src/duckhts.c:66), behind a variable of its own: DHTS_KMER_FUNCTIONS=1
+    if (const char *e = getenv("DHTS_KMER_FUNCTIONS")) if (atoi(e) == 1) register_kmer_udf_functions(conn);
     // read_tabix, read_gtf, read_gff close the list (src/duckhts.c:67-69), opt-in: DHTS_TABIX_FUNCTIONS=1
     if (const char *e = getenv("DHTS_TABIX_FUNCTIONS")) if (atoi(e) == 1) { register_read_tabix_function(conn); register_read_gtf_function(conn); register_read_gff_function(conn); }
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);

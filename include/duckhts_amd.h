@@ -560,6 +560,81 @@ int dhts_tabix_next_batch(dhts_ctx *, int64_t max_blocks, dhts_tabix_batch *out)
 uint64_t dhts_tabix_batch_host_bytes(const dhts_tabix_batch *b);
 int dhts_tabix_batch_fetch(dhts_ctx *, const dhts_tabix_batch *b, void *dst, uint64_t cap, dhts_col *out_cols, dhts_tabix_map *out_map);
 
+/* ---- seq_* / cigar_* / SAM flag functions on device columns --------------------------------------
+ * register_kmer_udf_functions (src/kmer_udf.c:1223-1254) evaluated where a batch lives: the arguments are DEVICE columns -- the seq, cigar
+ * and flag of a dhts_bam_batch as they are, or host values brought over by dhts_udf_upload -- and so are the results.
+ *   DHTS_UDF_SEQ_REVCOMP               <- seq_revcomp_scalar :297-336, dna_complement :88-97
+ *   DHTS_UDF_SEQ_CANONICAL             <- seq_canonical_scalar :338-388
+ *   DHTS_UDF_SEQ_HASH_2BIT             <- seq_hash_2bit_scalar :390-427, dna_to_2bit :99-107
+ *   DHTS_UDF_SEQ_ENCODE_4BIT / _DECODE <- seq_encode_4bit_scalar :429-480, iupac_to_4bit :109-128 / seq_decode_4bit_scalar :482-528, :130-149
+ *   DHTS_UDF_SEQ_GC_CONTENT            <- seq_gc_content_scalar :530-581
+ *   DHTS_UDF_CIGAR_HAS_SOFT_CLIP .. _REFERENCE_LENGTH <- cigar_metric_scalar :695-742 over parse_cigar_metrics :197-269
+ *   DHTS_UDF_CIGAR_HAS_OP              <- cigar_has_op_scalar :744-790 over cigar_has_operator_text :271-295
+ *   DHTS_UDF_SAM_FLAG_BITS / _HAS / DHTS_UDF_IS_FORWARD_ALIGNED / DHTS_UDF_IS_PAIRED .. _IS_SUPPLEMENTARY <- :583-693
+ *   dhts_udf_seq_kmers                 <- seq_kmers_bind / seq_kmers_function :820-974, over a whole column
+ * The ids follow the registration order of :1223-1254 (seq_kmers, a table function, has its own entry). */
+enum { DHTS_UDF_SEQ_REVCOMP = 0, DHTS_UDF_SEQ_CANONICAL, DHTS_UDF_SEQ_HASH_2BIT, DHTS_UDF_SEQ_ENCODE_4BIT, DHTS_UDF_SEQ_DECODE_4BIT, DHTS_UDF_SEQ_GC_CONTENT,
+       DHTS_UDF_CIGAR_HAS_SOFT_CLIP, DHTS_UDF_CIGAR_HAS_HARD_CLIP, DHTS_UDF_CIGAR_LEFT_SOFT_CLIP, DHTS_UDF_CIGAR_RIGHT_SOFT_CLIP, DHTS_UDF_CIGAR_QUERY_LENGTH,
+       DHTS_UDF_CIGAR_ALIGNED_QUERY_LENGTH, DHTS_UDF_CIGAR_REFERENCE_LENGTH, DHTS_UDF_CIGAR_HAS_OP,
+       DHTS_UDF_SAM_FLAG_BITS, DHTS_UDF_SAM_FLAG_HAS, DHTS_UDF_IS_FORWARD_ALIGNED,
+       DHTS_UDF_IS_PAIRED, DHTS_UDF_IS_PROPER_PAIR, DHTS_UDF_IS_UNMAPPED, DHTS_UDF_IS_NEXT_SEGMENT_UNMAPPED, DHTS_UDF_IS_REVERSE_COMPLEMENTED,
+       DHTS_UDF_IS_NEXT_SEGMENT_REVERSE_COMPLEMENTED, DHTS_UDF_IS_FIRST_SEGMENT, DHTS_UDF_IS_LAST_SEGMENT, DHTS_UDF_IS_SECONDARY, DHTS_UDF_IS_QC_FAIL,
+       DHTS_UDF_IS_DUPLICATE, DHTS_UDF_IS_SUPPLEMENTARY, DHTS_UDF_OP_COUNT };
+enum { DHTS_T_UTINYINT = 6, DHTS_T_UBIGINT = 9 };      /* DUCKDB_TYPE_* values the results add to DHTS_T_* */
+/* One argument column.  VARCHAR: the first four members are a dhts_strcol (a batch column is copied in as it is, reserved widths and all;
+ * len = NULL: row i is bytes[off[i], off[i + 1])).  LIST(UTINYINT) (seq_decode_4bit): the same shape with one byte per child, child_valid
+ * beside bytes.  Integers (FLAG, a mask): fixed[n] of |width| bytes, width < 0 = signed.  is_const: the column has ONE row that stands for
+ * every row (the 'S' of cigar_has_op(CIGAR, 'S'), the mask of sam_flag_has). */
+typedef struct {
+    const uint32_t *off; const uint32_t *len; const uint8_t *bytes; uint64_t nbytes;
+    const uint8_t *valid;        /* n bytes, 1 = valid; NULL = every row is valid */
+    const uint8_t *child_valid;  /* nbytes bytes; NULL = every child is valid */
+    const void *fixed; int32_t width;
+    int32_t is_const;
+} dhts_udf_arg;
+/* A result column: DEVICE pointers owned by the context, valid until the next dhts_udf_* call on it -- which may still take them as an
+ * argument (seq_decode_4bit of the list seq_encode_4bit just made).  A dhts_udf_* call leaves the context's current dhts_bam_batch alone.
+ *   BOOLEAN                 col.fixed[n_rows] bytes; sam_flag_bits: n_fields = 12 arrays of n_rows bytes behind each other (:21-49's order)
+ *   BIGINT, UBIGINT, DOUBLE col.fixed[n_rows] 8-byte values
+ *   VARCHAR                 row i = col.bytes[col.off[i], col.off[i] + len[i]); off is the ARGUMENT's (same-length results keep its layout:
+ *                           a NULL row keeps its reserved bytes, content unspecified), col.nbytes its arena size
+ *   LIST(UTINYINT)          col.off[n_rows + 1] child offsets, the codes in col.bytes[col.child_n]; a NULL row has no children */
+typedef struct {
+    int32_t op, type;            /* DHTS_T_* of the value (of the child when is_list) */
+    int32_t is_list, n_fields;
+    int64_t n_rows;
+    dhts_col col;
+    const uint32_t *len;
+} dhts_udf_result;
+/* Host values -> device, into one of two argument slots of the context (slot 0 / 1; they live until the same slot is uploaded again):
+ * whichever of off (n + 1 entries, or 2 with is_const), len, bytes (nbytes), valid, child_valid and fixed `host` sets is copied, *dev =
+ * the same description with device pointers.  Host callers and the tests come in through here. */
+int dhts_udf_upload(dhts_ctx *, int slot, const dhts_udf_arg *host, int64_t n_rows, dhts_udf_arg *dev);
+/* result = op(a0[, a1]) for n_rows rows (0 is valid); a1 = NULL for the one-argument functions.  A VARCHAR arena is addressed with 32-bit
+ * offsets: a result that would reach 4 GiB is an error that says so.  The SEQ column of a batch scanned under dhts_bam_set_seq_packed holds
+ * 4-bit codes, not text: it is refused with an error that names packed SEQ.  DHTS_UDF_GROUP = 4 | 16 | 64 forces the lanes per row of the
+ * text kernels (default: by the column's mean width). */
+int dhts_udf_apply(dhts_ctx *, int op, const dhts_udf_arg *a0, const dhts_udf_arg *a1, int64_t n_rows, dhts_udf_result *out);
+/* read-back with one wait: *out = *r with HOST pointers into dst (dhts_udf_result_host_bytes = the room dst needs) */
+uint64_t dhts_udf_result_host_bytes(const dhts_udf_result *r);
+int dhts_udf_fetch(dhts_ctx *, const dhts_udf_result *r, void *dst, uint64_t cap, dhts_udf_result *out);
+/* seq_kmers over a column: k-mer number t (0-based, counted over the whole column in row order) lies in row `row` at the 1-based `pos`.
+ * want_text: kmer = the raw bytes (no validation, no upper-casing :944) or, canonical, what seq_canonical makes of them (NULL when the
+ * k-mer holds a byte outside ACGTN :948-963).  want_hash: hash = seq_hash_2bit(kmer), 8 bytes instead of k; needs k <= 32.  A sequence
+ * shorter than k gives no rows.  At most max_rows (<= 0: 4,194,304; always so few that the text stays below 4 GiB) k-mers from number
+ * `resume` on are returned; next = the `resume` of the following call, status = 1 with the last ones.  "seq_kmers: k must be > 0". */
+typedef struct {
+    int64_t n_rows; int32_t status; int32_t k;
+    uint64_t next, total;        /* total: k-mers of the whole column */
+    const int64_t *row, *pos;
+    dhts_col kmer;               /* valid[n_rows], off[n_rows + 1], bytes; all NULL without want_text */
+    const uint64_t *hash; const uint8_t *hash_valid;      /* NULL without want_hash */
+} dhts_udf_kmers;
+int dhts_udf_seq_kmers(dhts_ctx *, const dhts_udf_arg *seq, int64_t n_rows, int64_t k, int canonical, int want_text, int want_hash,
+                       int64_t max_rows, uint64_t resume, dhts_udf_kmers *out);
+uint64_t dhts_udf_kmers_host_bytes(const dhts_udf_kmers *b);
+int dhts_udf_kmers_fetch(dhts_ctx *, const dhts_udf_kmers *b, void *dst, uint64_t cap, dhts_udf_kmers *out);
+
 /* ---- utilities ------------------------------------------------------------------------------ */
 int dhts_memcpy_d2h(dhts_ctx *, void *dst, const void *src_dev, uint64_t n);
 int dhts_sync(dhts_ctx *);

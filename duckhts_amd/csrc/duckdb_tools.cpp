@@ -4,65 +4,25 @@
 // Each function does its work at bind time and returns one row, like the reference.  htslib's bgzf_write / bgzf_read / sam_index_build3 /
 // bcf_index_build3 / tbx_index_build3 underneath are replaced by include/duckhts_amd.h: DEFLATE compression and inflation, the record scans
 // that feed the index and the tabix interval rule all run on the GPU; the binning index itself (hts_idx_push / hts_idx_finish) is host work.
-#include "../../include/duckhts_amd.h"
-#include "../../include/duckhts_extension.h"
+#include "duckdb_surface.h"
 
 #include <errno.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include <string>
-#include <vector>
-
-#define API(ret, name, ...) ((ret(*)(__VA_ARGS__))duckdb_ext_api[SLOT_##name])
 
 namespace {
 struct OneRow { bool emitted = false; std::string path, format; int64_t bytes_in = 0, bytes_out = 0; bool four = false, two = false; };
 void destroy_row(void *p) { delete (OneRow *)p; }
 
-char *named_varchar(duckdb_bind_info info, const char *name) {
-    duckdb_value v = API(duckdb_value, duckdb_bind_get_named_parameter, duckdb_bind_info, const char *)(info, name);
-    char *s = nullptr;
-    if (v && !API(bool, duckdb_is_null_value, duckdb_value)(v)) s = API(char *, duckdb_get_varchar, duckdb_value)(v);
-    if (v) API(void, duckdb_destroy_value, duckdb_value *)(&v);
-    return s;
-}
-bool named_int(duckdb_bind_info info, const char *name, int64_t *out) {
-    duckdb_value v = API(duckdb_value, duckdb_bind_get_named_parameter, duckdb_bind_info, const char *)(info, name);
-    bool set = false;
-    if (v && !API(bool, duckdb_is_null_value, duckdb_value)(v)) { *out = API(int64_t, duckdb_get_int64, duckdb_value)(v); set = true; }
-    if (v) API(void, duckdb_destroy_value, duckdb_value *)(&v);
-    return set;
-}
-bool named_bool(duckdb_bind_info info, const char *name, bool *out) {
-    duckdb_value v = API(duckdb_value, duckdb_bind_get_named_parameter, duckdb_bind_info, const char *)(info, name);
-    bool set = false;
-    if (v && !API(bool, duckdb_is_null_value, duckdb_value)(v)) { *out = API(bool, duckdb_get_bool, duckdb_value)(v); set = true; }
-    if (v) API(void, duckdb_destroy_value, duckdb_value *)(&v);
-    return set;
-}
-std::string take(char *s) { std::string r = s ? s : ""; if (s) API(void, duckdb_free, void *)(s); return r; }
-std::string positional_path(duckdb_bind_info info) {
-    duckdb_value v = API(duckdb_value, duckdb_bind_get_parameter, duckdb_bind_info, idx_t)(info, 0);
-    char *s = API(char *, duckdb_get_varchar, duckdb_value)(v);
-    API(void, duckdb_destroy_value, duckdb_value *)(&v);
-    return take(s);
-}
+std::string positional_path(duckdb_bind_info info) { std::string p; (void)take_path(info, p); return p; }
+std::string named_text(duckdb_bind_info info, const char *name) { std::string v; (void)named_string(info, name, v); return v; }   // unset = ""
 void bind_error(duckdb_bind_info info, const std::string &m) { API(void, duckdb_bind_set_error, duckdb_bind_info, const char *)(info, m.c_str()); }
 bool ends_with(const std::string &s, const char *suf) { const size_t n = strlen(suf); return s.size() >= n && s.compare(s.size() - n, n, suf) == 0; }
-int device_id() { return getenv("DHTS_DEVICE") ? atoi(getenv("DHTS_DEVICE")) : 0; }
 
-void add_columns(duckdb_bind_info info, bool four) {
-    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
-    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
-    auto add = API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type);
-    duckdb_logical_type tb = mk(DUCKDB_TYPE_BOOLEAN), tv = mk(DUCKDB_TYPE_VARCHAR), ti = mk(DUCKDB_TYPE_BIGINT);
-    add(info, "success", tb);
-    if (four) { add(info, "output_path", tv); add(info, "bytes_in", ti); add(info, "bytes_out", ti); }        // bgzip.c:74-86
-    else { add(info, "index_path", tv); add(info, "index_format", tv); }                                       // hts_index_builder.c:70-79
-    rm(&tb); rm(&tv); rm(&ti);
+void add_row_columns(duckdb_bind_info info, bool four) {
+    static const char *const names4[4] = {"success", "output_path", "bytes_in", "bytes_out"}, *const names3[3] = {"success", "index_path", "index_format"};   // bgzip.c:74-86, hts_index_builder.c:70-79
+    const int32_t types[4] = {DUCKDB_TYPE_BOOLEAN, DUCKDB_TYPE_VARCHAR, four ? DUCKDB_TYPE_BIGINT : DUCKDB_TYPE_VARCHAR, DUCKDB_TYPE_BIGINT};
+    add_columns(info, four ? names4 : names3, types, four ? 4 : 3);
 }
 void row_init(duckdb_init_info info) { ((OneRow *)API(void *, duckdb_init_get_bind_data, duckdb_init_info)(info))->emitted = false; }
 void row_scan(duckdb_function_info info, duckdb_data_chunk output) {
@@ -80,7 +40,7 @@ void row_scan(duckdb_function_info info, duckdb_data_chunk output) {
     setn(output, 1);
 }
 void finish_bind(duckdb_bind_info info, OneRow *r) {
-    add_columns(info, r->four);
+    add_row_columns(info, r->four);
     API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, r, destroy_row);
 }
 
@@ -89,7 +49,7 @@ void bgzip_bind_common(duckdb_bind_info info, bool decompress) {
     const char *fn = decompress ? "bgunzip" : "bgzip";
     const std::string input = positional_path(info);
     if (input.empty()) { bind_error(info, std::string(fn) + " requires a file path"); return; }
-    std::string output = take(named_varchar(info, "output_path"));
+    std::string output = named_text(info, "output_path");
     int64_t threads = 4, level = -1; bool keep = true, overwrite = false;
     (void)named_int(info, "threads", &threads);                                   // (accepted; the blocks are processed by the GPU, not by bgzf_mt threads)
     if (!decompress) (void)named_int(info, "level", &level);
@@ -100,8 +60,9 @@ void bgzip_bind_common(duckdb_bind_info info, bool decompress) {
     }
     struct stat st;
     if (!overwrite && stat(output.c_str(), &st) == 0) { bind_error(info, std::string(fn) + ": output '" + output + "' already exists (use overwrite := TRUE to replace)"); return; }
-    dhts_ctx *c = dhts_create(device_id());
-    if (!c) { bind_error(info, std::string(fn) + ": no MI355X (gfx950) device available; this build has no CPU fallback"); return; }
+    std::string no_device;
+    dhts_ctx *c = create_ctx(fn, no_device, env_device());
+    if (!c) { bind_error(info, no_device); return; }
     int64_t nin = 0, nout = 0;
     const int rc = decompress ? dhts_bgunzip_file(c, input.c_str(), output.c_str(), &nin, &nout) : dhts_bgzip_file(c, input.c_str(), output.c_str(), (int)level, &nin, &nout);
     if (rc != 0) {
@@ -123,7 +84,7 @@ void bgunzip_bind(duckdb_bind_info info) { bgzip_bind_common(info, true); }
 // Returns htslib's code: 0, -1 indexing failed, -2 cannot open, -3 format not indexable, -4 the index could not be saved.
 struct TbxConfHost { int preset, sc, bc, ec, meta, skip; };
 int build_index_file(int kind, const std::string &path, const std::string &index_path, int min_shift, bool *wrote_csi, const TbxConfHost *conf = nullptr) {
-    dhts_ctx *c = dhts_create(device_id());
+    dhts_ctx *c = dhts_create(env_device());
     if (!c) return -1;
     int rc = 0; int64_t n = -1; bool csi = false, compressed = false;
     if (dhts_open_path(c, path.c_str()) != 0) rc = kind == 2 ? -1 : -2;
@@ -171,10 +132,10 @@ void index_bind_common(duckdb_bind_info info, int kind) {
     const std::string path = positional_path(info);
     if (path.empty()) { bind_error(info, std::string(fn) + " requires a file path"); return; }
     int64_t min_shift = kind == 1 && ends_with(path, ".bcf") ? 14 : 0, threads = 4, v = 0;
-    std::string index_path = take(named_varchar(info, "index_path"));
+    std::string index_path = named_text(info, "index_path");
     TbxConfHost conf = {2, 1, 2, 0, '#', 0};                                           // tbx_conf_vcf (tbx.c:55)
     if (kind == 2) {
-        const std::string preset = take(named_varchar(info, "preset"));
+        const std::string preset = named_text(info, "preset");
         if (preset.empty() || preset == "vcf") {}
         else if (preset == "bed") conf = {0x10000, 1, 2, 3, '#', 0};                   // tbx_conf_bed / _gff / _sam (tbx.c:43-52)
         else if (preset == "gff") conf = {0, 1, 4, 5, '#', 0};
@@ -183,7 +144,7 @@ void index_bind_common(duckdb_bind_info info, int kind) {
         if (named_int(info, "seq_col", &v)) conf.sc = (int)v;                           // hts_index_builder.c:264-287
         if (named_int(info, "start_col", &v)) conf.bc = (int)v;
         if (named_int(info, "end_col", &v)) conf.ec = (int)v;
-        const std::string cc = take(named_varchar(info, "comment_char"));
+        const std::string cc = named_text(info, "comment_char");
         if (!cc.empty()) conf.meta = (unsigned char)cc[0];
         if (named_int(info, "skip_lines", &v)) conf.skip = (int)v;
         if ((conf.preset & 0xffff) == 2 && (conf.sc != 1 || conf.bc != 2 || conf.ec != 0 || conf.meta != '#' || conf.skip != 0)) {
@@ -218,11 +179,11 @@ bool write_whole(const std::string &tmp, const void *p, size_t n) {
 void fasta_index_bind(duckdb_bind_info info) {
     const std::string path = positional_path(info);
     if (path.empty()) { bind_error(info, "fasta_index requires a file path"); return; }
-    const std::string index_path = take(named_varchar(info, "index_path"));
+    const std::string index_path = named_text(info, "index_path");
     const std::string fai_path = index_path.empty() ? path + ".fai" : index_path, gzi_path = path + ".gzi";
     const std::string tmp_fai = fai_path + ".tmp" + std::to_string((long)getpid()), tmp_gzi = gzi_path + ".tmp" + std::to_string((long)getpid());
     bool ok = false;
-    if (dhts_ctx *c = dhts_create(device_id())) {
+    if (dhts_ctx *c = dhts_create(env_device())) {
         int64_t n = -1, m = 0;
         if (dhts_open_path(c, path.c_str()) == 0 && dhts_bgzf_index(c) >= 0 && (n = dhts_fasta_build_index(c)) >= 0 && (m = dhts_fasta_gzi_bytes(c, nullptr, 0)) >= 0) {
             std::vector<uint8_t> fai((size_t)n + 1), gzi((size_t)m + 1);
@@ -234,35 +195,15 @@ void fasta_index_bind(duckdb_bind_info info) {
         dhts_destroy(c);
     }
     if (!ok) { bind_error(info, "fasta_index: failed to build index for " + path); return; }
-    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
-    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
-    auto add = API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type);
-    duckdb_logical_type tb = mk(DUCKDB_TYPE_BOOLEAN), tv = mk(DUCKDB_TYPE_VARCHAR);
-    add(info, "success", tb); add(info, "index_path", tv);                       // seq_reader.c:702-707
-    rm(&tb); rm(&tv);
+    static const char *const names[2] = {"success", "index_path"};                // seq_reader.c:702-707
+    static const int32_t types[2] = {DUCKDB_TYPE_BOOLEAN, DUCKDB_TYPE_VARCHAR};
+    add_columns(info, names, types, 2);
     OneRow *r = new OneRow(); r->two = true; r->path = index_path;               // the parameter, or "" (seq_reader.c:710)
     API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, r, destroy_row);
 }
 
-struct Param { const char *name; int type; };
 void register_one(duckdb_connection connection, const char *name, duckdb_table_function_bind_t bind, const std::vector<Param> &params) {
-    duckdb_table_function tf = API(duckdb_table_function, duckdb_create_table_function, void)();
-    API(void, duckdb_table_function_set_name, duckdb_table_function, const char *)(tf, name);
-    auto mk = API(duckdb_logical_type, duckdb_create_logical_type, int);
-    auto rm = API(void, duckdb_destroy_logical_type, duckdb_logical_type *);
-    duckdb_logical_type tv = mk(DUCKDB_TYPE_VARCHAR);
-    API(void, duckdb_table_function_add_parameter, duckdb_table_function, duckdb_logical_type)(tf, tv);
-    rm(&tv);
-    for (const Param &p : params) {
-        duckdb_logical_type t = mk(p.type);
-        API(void, duckdb_table_function_add_named_parameter, duckdb_table_function, const char *, duckdb_logical_type)(tf, p.name, t);
-        rm(&t);
-    }
-    API(void, duckdb_table_function_set_bind, duckdb_table_function, duckdb_table_function_bind_t)(tf, bind);
-    API(void, duckdb_table_function_set_init, duckdb_table_function, duckdb_table_function_init_t)(tf, row_init);
-    API(void, duckdb_table_function_set_function, duckdb_table_function, duckdb_table_function_t)(tf, row_scan);
-    API(duckdb_state, duckdb_register_table_function, duckdb_connection, duckdb_table_function)(connection, tf);
-    API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
+    register_table_function(connection, name, params, bind, row_init, nullptr, row_scan, false);
 }
 }  // namespace
 

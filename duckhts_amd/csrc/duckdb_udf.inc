@@ -17,7 +17,7 @@ dhts_ctx *udf_ctx_take() {
         std::lock_guard<std::mutex> lk(g_udf_mu);
         if (!g_udf_idle.empty()) { dhts_ctx *c = g_udf_idle.back(); g_udf_idle.pop_back(); return c; }
     }
-    return dhts_create(getenv("DHTS_DEVICE") ? atoi(getenv("DHTS_DEVICE")) : 0);
+    return dhts_create(env_device());
 }
 void udf_ctx_give(dhts_ctx *c) {
     {
@@ -167,7 +167,6 @@ bool udf_run(dhts_ctx *c, int op, duckdb_data_chunk input, duckdb_vector output,
     else { memcpy(out, h.col.fixed, n * 8); for (idx_t i = 0; i < n; i++) if (!valid[i]) set_null(output, i); }      // BIGINT, UBIGINT, DOUBLE
     return true;
 }
-void udf_no_device(char *buf, size_t cap, const char *name) { snprintf(buf, cap, "%s: no MI355X (gfx950) device available; this build has no CPU fallback", name); }
 
 void udf_scalar(duckdb_function_info info, duckdb_data_chunk input, duckdb_vector output) {
     const int op = (int)(uintptr_t)API(void *, duckdb_scalar_function_get_extra_info, duckdb_function_info)(info) - 1;
@@ -176,7 +175,7 @@ void udf_scalar(duckdb_function_info info, duckdb_data_chunk input, duckdb_vecto
     if (n == 0) return;
     char msg[640];
     dhts_ctx *c = udf_ctx_take();
-    if (!c) { udf_no_device(msg, sizeof(msg), UDF_SQL_NAMES[op]); API(void, duckdb_scalar_function_set_error, duckdb_function_info, const char *)(info, msg); return; }
+    if (!c) { API(void, duckdb_scalar_function_set_error, duckdb_function_info, const char *)(info, no_device_message(UDF_SQL_NAMES[op]).c_str()); return; }
     std::string err;
     const bool ok = udf_run(c, op, input, output, n, err);
     udf_ctx_give(c);
@@ -207,7 +206,7 @@ void kmers_bind(duckdb_bind_info info) {
     KmersBind *b = new KmersBind(); b->seq = seq; b->k = k; b->canonical = canonical;
     API(void, duckdb_free, void *)(seq);
     if (k <= 0) { delete b; bind_err("seq_kmers: k must be > 0"); return; }
-    if (dhts_device_count() <= 0) { delete b; char msg[160]; udf_no_device(msg, sizeof(msg), "seq_kmers"); bind_err(msg); return; }
+    if (dhts_device_count() <= 0) { delete b; bind_err(no_device_message("seq_kmers").c_str()); return; }
     duckdb_logical_type tb = API(duckdb_logical_type, duckdb_create_logical_type, int)(DUCKDB_TYPE_BIGINT), tv = API(duckdb_logical_type, duckdb_create_logical_type, int)(DUCKDB_TYPE_VARCHAR);
     API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type)(info, "pos", tb);
     API(void, duckdb_bind_add_result_column, duckdb_bind_info, const char *, duckdb_logical_type)(info, "kmer", tv);
@@ -227,7 +226,7 @@ void kmers_function(duckdb_function_info info, duckdb_data_chunk output) {
     if (!b || !st || st->done || b->seq.size() < (uint64_t)b->k) { API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t)(output, 0); return; }
     char msg[640];
     dhts_ctx *c = udf_ctx_take();
-    if (!c) { udf_no_device(msg, sizeof(msg), "seq_kmers"); fn_err(msg); return; }
+    if (!c) { fn_err(no_device_message("seq_kmers").c_str()); return; }
     const idx_t vs = API(idx_t, duckdb_vector_size)();
     const uint32_t off[2] = {0, (uint32_t)b->seq.size()};
     dhts_udf_arg h; memset(&h, 0, sizeof(h)); h.off = off; h.bytes = (const uint8_t *)b->seq.data(); h.nbytes = b->seq.size();
@@ -250,19 +249,7 @@ void kmers_function(duckdb_function_info info, duckdb_data_chunk output) {
     API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t)(output, m);
 }
 void register_seq_kmers(duckdb_connection connection) {                 // :1199-1221
-    duckdb_table_function tf = API(duckdb_table_function, duckdb_create_table_function)();
-    API(void, duckdb_table_function_set_name, duckdb_table_function, const char *)(tf, "seq_kmers");
-    duckdb_logical_type tv = API(duckdb_logical_type, duckdb_create_logical_type, int)(DUCKDB_TYPE_VARCHAR), ti = API(duckdb_logical_type, duckdb_create_logical_type, int)(DUCKDB_TYPE_BIGINT),
-                        tb = API(duckdb_logical_type, duckdb_create_logical_type, int)(DUCKDB_TYPE_BOOLEAN);
-    API(void, duckdb_table_function_add_parameter, duckdb_table_function, duckdb_logical_type)(tf, tv);
-    API(void, duckdb_table_function_add_parameter, duckdb_table_function, duckdb_logical_type)(tf, ti);
-    API(void, duckdb_table_function_add_named_parameter, duckdb_table_function, const char *, duckdb_logical_type)(tf, "canonical", tb);
-    API(void, duckdb_table_function_set_bind, duckdb_table_function, duckdb_table_function_bind_t)(tf, kmers_bind);
-    API(void, duckdb_table_function_set_init, duckdb_table_function, duckdb_table_function_init_t)(tf, kmers_init);
-    API(void, duckdb_table_function_set_function, duckdb_table_function, duckdb_table_function_t)(tf, kmers_function);
-    API(duckdb_state, duckdb_register_table_function, duckdb_connection, duckdb_table_function)(connection, tf);
-    API(void, duckdb_destroy_logical_type, duckdb_logical_type *)(&tv); API(void, duckdb_destroy_logical_type, duckdb_logical_type *)(&ti); API(void, duckdb_destroy_logical_type, duckdb_logical_type *)(&tb);
-    API(void, duckdb_destroy_table_function, duckdb_table_function *)(&tf);
+    register_table_function(connection, "seq_kmers", {{nullptr, DUCKDB_TYPE_BIGINT}, {"canonical", DUCKDB_TYPE_BOOLEAN}}, kmers_bind, kmers_init, nullptr, kmers_function, false);   // (sequence, k, canonical := ...)
 }
 // one scalar function: name, up to two parameter types, the return type (ret = 0: LIST(UTINYINT) in / out as marked, -1: the flag struct)
 void register_udf_scalar(duckdb_connection connection, int op, int p0, int p1, int ret) {

@@ -107,6 +107,15 @@ def test_entrypoint_and_errors_without_gpu_dependency():
         assert "unknown named parameter" not in out
 
 
+def test_registered_catalog_matches_the_recorded_one():
+    """every table function with all five opt-in sets on: order, pushdown flag, callbacks set, named parameters with type codes --
+    the listing needs no device; tests/golden/surface_catalog.txt was recorded before the registration code was shared"""
+    env = dict(os.environ, DHTS_SEQ_FUNCTIONS="1", DHTS_INTERVAL_FUNCTIONS="1", DHTS_NUC_FUNCTIONS="1", DHTS_KMER_FUNCTIONS="1", DHTS_TABIX_FUNCTIONS="1")
+    r = subprocess.run([HOST, duckhts_amd.LIB_PATH, "--catalog", "x"], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout == open(os.path.join(GOLDEN, "surface_catalog.txt")).read()
+
+
 def expect_chunks(exp, proj):
     names = [s[0] for s in SCHEMA]
     n = exp["n_rows"]

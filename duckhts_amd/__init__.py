@@ -179,6 +179,7 @@ def lib():
         L.dhts_debug_sam_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64)]
         L.dhts_debug_fastq_records.restype = C.c_int64
         L.dhts_debug_fastq_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64)]
+        L.dhts_debug_tile_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.dhts_bam_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dhts_bam_set_block_range.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int]
         L.dhts_shard_cut.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -380,6 +381,15 @@ class Context:
         buf = np.zeros(max(size, 1), np.uint8)
         self._chk(self.L.dhts_debug_sam_records(self.h, buf.ctypes.data, size, C.byref(n)))
         return buf[:size].tobytes(), n.value
+
+    TILE_STATS = ("repaired_tiles", "repair_rounds", "fallback_batches", "spec_retries", "validate_rejections", "gave_up")
+
+    def debug_tile_stats(self):
+        """what the record stage's repair and retry paths did since the scan was opened or rewound (read_bam and read_bcf alike):
+        {TILE_STATS name: count} (include/duckhts_amd_debug.h: dhts_debug_tile_stats)"""
+        out = (C.c_uint64 * 8)()
+        self._chk(self.L.dhts_debug_tile_stats(self.h, out))
+        return {k: int(out[i]) for i, k in enumerate(self.TILE_STATS)}
 
     def debug_fastq_records(self):
         """the BAM records the device encoder made of the last FASTQ / FASTA batch: (bytes, number of records)"""
@@ -1518,9 +1528,9 @@ def _concat_tables(parts, schema_cols):
     return out
 
 
-def read_bcf(src, tidy=False, columns=None, device=0, max_blocks=0, block_range=None, region=None, index=None):
+def read_bcf(src, tidy=False, columns=None, device=0, max_blocks=0, block_range=None, region=None, index=None, stats=None):
     """Full sequential read_bcf scan (every record in file order); returns the canonical column table.
-    columns: optional projection (names or schema ids), like DuckDB's projection pushdown."""
+    columns: optional projection (names or schema ids), like DuckDB's projection pushdown.  stats: a dict that receives Context.debug_tile_stats()."""
     ctx = Context(device)
     try:
         ctx.open(src)
@@ -1547,6 +1557,8 @@ def read_bcf(src, tidy=False, columns=None, device=0, max_blocks=0, block_range=
                 status = b.status
                 if b.status != 0:
                     break
+        if stats is not None:
+            stats.update(ctx.debug_tile_stats())
         proj = [sc.schema[i] for i in sc.projection]
         cols = _concat_tables(parts, proj)
         if cols is None:
@@ -1589,8 +1601,11 @@ def std_tags():
     return _STD_TAGS
 
 
-def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, std_tags_cols=None, aux_map=None, overlap=None, sparse=None, overlap_bed=None):
+def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, std_tags_cols=None, aux_map=None, overlap=None, sparse=None, overlap_bed=None,
+             block_range=None, stats=None):
     """Full sequential scan (reference mode (i)): all rows in file order.
+    block_range=(b0, b1, speculative): one shard of BGZF blocks (Context.set_block_range); the result carries first_rec_uoff / end_uoff.
+    stats: a dict that receives Context.debug_tile_stats().
     region: the reference's region := string (rows filtered on the device); index: BAI bytes narrowing the scan window.
     sparse=(header_bytes, beg[], end[]) with a path: only the header blocks and those file ranges are staged (Context.region_segments)."""
     ctx = Context(device)
@@ -1603,6 +1618,8 @@ def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, s
         hdr = ctx.bam_open()
         if shard is not None:
             ctx.set_shard(*shard)
+        if block_range is not None:
+            ctx.set_block_range(*block_range)
         if region is not None:
             if not ctx.set_regions(region):
                 raise DhtsError(f"No reads found for region(s): {region}")
@@ -1619,9 +1636,12 @@ def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, s
             n_bed = ctx.set_overlap_bed(overlap_bed); overlap = True
         parts, tparts, aparts, oparts = [], [], [], []
         status = 0
+        first_uoff = end_uoff = None
         while True:
             b = ctx.next_batch(max_blocks)
+            end_uoff = int(b.end_uoff)
             if b.n_rows:
+                first_uoff = int(b.first_rec_uoff) if first_uoff is None else first_uoff
                 parts.append(ctx.batch_to_host(b, hdr))
                 if std_tags_cols is not None:
                     tparts.append(ctx.tag_table(b))
@@ -1632,7 +1652,9 @@ def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, s
             status = b.status
             if b.status != 0:
                 break
-        out = {"n_rows": sum(p["n_rows"] for p in parts), "status": status, "header": hdr}
+        out = {"n_rows": sum(p["n_rows"] for p in parts), "status": status, "header": hdr, "first_rec_uoff": first_uoff, "end_uoff": end_uoff}
+        if stats is not None:
+            stats.update(ctx.debug_tile_stats())
         if std_tags_cols is not None:
             out["tags"] = {"n_rows": out["n_rows"], "cols": _concat_tables(tparts, None) or []}
         if aux_map is not None:

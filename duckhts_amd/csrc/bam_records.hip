@@ -58,6 +58,19 @@ struct TileOut {
     int32_t *err;        // 0, or 1 = chain stopped on an invalid record at end_next
 };
 
+// A shard that starts mid-stream: the record starts on the chains of the candidates that have failed so far (up to 8 ascending lists).  A
+// member of such a chain, taken as a candidate, walks the same hops to the same break, so the search passes over it without a tile pass.
+#define SPEC_LISTS 8
+struct SpecSkip { const uint32_t *off[SPEC_LISTS]; uint32_t n[SPEC_LISTS]; int32_t lists; };
+__device__ __forceinline__ bool spec_skipped(const SpecSkip &sk, uint64_t o) {
+    for (int l = 0; l < sk.lists; l++) {
+        uint32_t lo = 0, hi = sk.n[l];
+        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)sk.off[l][mid] < o) lo = mid + 1; else hi = mid; }
+        if (lo < sk.n[l] && (uint64_t)sk.off[l][lo] == o) return true;
+    }
+    return false;
+}
+
 // chain walk used by the repair kernels: same core-only tests as rec_hop in bam_tiles_lds.hip (the CIGAR/qlen test and the
 // CG swap are checked per row by bam_tile_unpack)
 __device__ void tile_walk(const BamStream &st, uint64_t start, uint64_t tile_end, uint64_t &end_next, uint32_t &count, int &err) {
@@ -119,18 +132,24 @@ bam_tile_fix(BamStream st, uint32_t tile_bytes, int64_t ntiles, TileOut in, Tile
 }
 
 // Sequential fallback (pathological inputs only): one thread proves/repairs every tile in order.
-extern "C" __global__ void bam_tile_fix_seq(BamStream st, uint32_t tile_bytes, int64_t ntiles, TileOut out) {
+// *nfixed (zeroed by the host) counts the tiles it changed, as a repair round does.
+extern "C" __global__ void bam_tile_fix_seq(BamStream st, uint32_t tile_bytes, int64_t ntiles, TileOut out, uint32_t *nfixed) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    uint32_t nf = 0;
     for (int64_t t = 1; t < ntiles; t++) {
-        if (out.err[t - 1]) return;
+        if (out.err[t - 1]) break;
         uint64_t p = out.end_next[t - 1];
         uint64_t tb = (uint64_t)t * tile_bytes, te = tb + tile_bytes; if (te > st.ulen) te = st.ulen;
-        if (p >= te) { out.first[t] = NONE64; out.count[t] = 0; out.err[t] = 0; out.end_next[t] = p; continue; }
+        if (p >= te) {
+            if (!(out.first[t] == NONE64 && out.count[t] == 0 && out.err[t] == 0 && out.end_next[t] == p)) nf++;
+            out.first[t] = NONE64; out.count[t] = 0; out.err[t] = 0; out.end_next[t] = p; continue;
+        }
         if (out.first[t] == p) continue;
         uint64_t en; uint32_t cnt; int err;
         tile_walk(st, p, te, en, cnt, err);
-        out.first[t] = p; out.count[t] = cnt; out.err[t] = err; out.end_next[t] = en;
+        out.first[t] = p; out.count[t] = cnt; out.err[t] = err; out.end_next[t] = en; nf++;
     }
+    *nfixed = nf;
 }
 
 // Single-workgroup finalize: first error tile E, exclusive prefix of counts, totals (rows of tiles after E are never used).

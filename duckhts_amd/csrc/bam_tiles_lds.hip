@@ -354,6 +354,37 @@ bam_tile_scan(BamStream st, uint64_t start0, int64_t ntiles, TileOut out, uint16
     for (uint32_t k = lane; k < cnt && k < TL_RECS; k += 64) tile_recs[(size_t)t * TL_RECS + k] = rl[k];
 }
 
+// The retry of a speculated shard start: tile 0's search of bam_tile_scan (same filter, three deep, first hit from `from` on) as one wave
+// over global memory, passing over the members of failed chains.  *out = the candidate or NONE64.
+extern "C" __global__ void __launch_bounds__(64)
+bam_spec_next(BamStream st, uint64_t from, SpecSkip sk, uint64_t *out) {
+    const int lane = threadIdx.x;
+    GSrc gs; gs.g = st.u;
+    uint64_t first = NONE64;
+    for (uint64_t base = from & ~63ull; base < st.ulen; base += 64) {
+        const uint64_t o = base + (uint64_t)lane;
+        bool ok = false;
+        if (o < st.ulen && o >= from) {
+            RecInfo r;
+            if (rec_check_t(st, gs, o, r, false) == REC_OK) {
+                ok = true;
+                uint64_t o2 = o + 4ull + r.block_len;
+                for (int k = 0; k < 2 && ok; k++) {
+                    RecInfo r2;
+                    const int rc = rec_check_t(st, gs, o2, r2, false);
+                    if (rc == REC_INVALID) ok = false;
+                    else if (rc == REC_INCOMPLETE) break;
+                    else o2 += 4ull + r2.block_len;
+                }
+                if (ok && spec_skipped(sk, o)) ok = false;       // (last: nearly every offset fails the filter's first word, and the lists are searched in HBM)
+            }
+        }
+        const uint64_t m = __ballot(ok);
+        if (m) { first = base + (uint64_t)(__ffsll((unsigned long long)m) - 1); break; }
+    }
+    if (lane == 0) *out = first;
+}
+
 // The @RG dictionary as unpack_one reads it: in HBM (DictG), or -- when it is small, as it nearly always is -- in a copy the workgroup made
 // in LDS (DictL).  Two types with the same members so that each instantiation keeps its address space (a pointer that may be either
 // becomes a flat access, and flat accesses to LDS fault on this system).  The comparison loop is a chain of dependent byte loads per

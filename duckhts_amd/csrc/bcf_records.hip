@@ -130,6 +130,36 @@ bcf_tile_scan(BcfStream st, uint64_t start0, int64_t ntiles, TileOut out, uint64
     }
 }
 
+// the retry of a speculated shard start (see bam_spec_next)
+extern "C" __global__ void __launch_bounds__(64)
+bcf_spec_next(BcfStream st, uint64_t from, SpecSkip sk, uint64_t *out) {
+    const int lane = threadIdx.x;
+    GSrc gs; gs.g = st.u;
+    uint64_t first = NONE64;
+    for (uint64_t base = from & ~63ull; base < st.ulen; base += 64) {
+        const uint64_t o = base + (uint64_t)lane;
+        bool ok = false;
+        if (o < st.ulen && o >= from) {
+            uint64_t sz = 0;
+            if (bcf_hop(st, gs, o, sz, true) == REC_OK) {
+                ok = true;
+                uint64_t o2 = o + sz;
+                for (int k = 0; k < 2 && ok; k++) {
+                    uint64_t s2 = 0;
+                    const int rc = bcf_hop(st, gs, o2, s2, true);
+                    if (rc == REC_INVALID) ok = false;
+                    else if (rc == REC_INCOMPLETE) break;
+                    else o2 += s2;
+                }
+                if (ok && spec_skipped(sk, o)) ok = false;
+            }
+        }
+        const uint64_t m = __ballot(ok);
+        if (m) { first = base + (uint64_t)(__ffsll((unsigned long long)m) - 1); break; }
+    }
+    if (lane == 0) *out = first;
+}
+
 // out-of-place continuity proof + repair round (same protocol as bam_tile_fix)
 extern "C" __global__ void __launch_bounds__(256)
 bcf_tile_fix(BcfStream st, uint32_t tile_bytes, int64_t ntiles, TileOut in, TileOut out, uint32_t *nfixed) {
@@ -150,18 +180,23 @@ bcf_tile_fix(BcfStream st, uint32_t tile_bytes, int64_t ntiles, TileOut in, Tile
     out.first[t] = f; out.end_next[t] = en; out.count[t] = cnt; out.err[t] = err;
 }
 
-extern "C" __global__ void bcf_tile_fix_seq(BcfStream st, uint32_t tile_bytes, int64_t ntiles, TileOut out) {
+extern "C" __global__ void bcf_tile_fix_seq(BcfStream st, uint32_t tile_bytes, int64_t ntiles, TileOut out, uint32_t *nfixed) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    uint32_t nf = 0;
     for (int64_t t = 1; t < ntiles; t++) {
-        if (out.err[t - 1]) return;
+        if (out.err[t - 1]) break;
         uint64_t p = out.end_next[t - 1];
         uint64_t tb = (uint64_t)t * tile_bytes, te = tb + tile_bytes; if (te > st.ulen) te = st.ulen;
-        if (p >= te) { out.first[t] = NONE64; out.count[t] = 0; out.err[t] = 0; out.end_next[t] = p; continue; }
+        if (p >= te) {
+            if (!(out.first[t] == NONE64 && out.count[t] == 0 && out.err[t] == 0 && out.end_next[t] == p)) nf++;
+            out.first[t] = NONE64; out.count[t] = 0; out.err[t] = 0; out.end_next[t] = p; continue;
+        }
         if (out.first[t] == p) continue;
         uint64_t en; uint32_t cnt; int err;
         bcf_tile_walk(st, p, te, en, cnt, err);
-        out.first[t] = p; out.count[t] = cnt; out.err[t] = err; out.end_next[t] = en;
+        out.first[t] = p; out.count[t] = cnt; out.err[t] = err; out.end_next[t] = en; nf++;
     }
+    *nfixed = nf;
 }
 
 // record offsets by record id (one lane per tile; <= 256 records per 8 KiB tile)

@@ -205,6 +205,8 @@ struct UdfState {
     struct Res { DevBuf valid, fixed, len, off, bytes; } res[2]; int cur = 0;
     DevBuf clen, cnt, cum, k_row, k_pos, k_off, k_bytes, k_valid, k_hash, k_hvalid;
 };
+// words of dhts_debug_tile_stats (include/duckhts_amd_debug.h)
+enum { DHTS_TS_REPAIRED = 0, DHTS_TS_ROUNDS = 1, DHTS_TS_SEQ = 2, DHTS_TS_RETRIES = 3, DHTS_TS_VALIDATE = 4, DHTS_TS_GAVE_UP = 5 };
 struct dhts_ctx;
 static void stop_stager(dhts_ctx *c);
 struct dhts_ctx {
@@ -252,6 +254,8 @@ struct dhts_ctx {
     // dhts_open_path_async: the file is still arriving; the block table covers the staged prefix and grows (dhts_bgzf_index_staged)
     std::thread stager; StageProg *prog = nullptr; bool growing = false; uint64_t stage_total = 0;
     uint64_t debug_full_len = 0; bool debug_prefix = false;     // dhts_debug_index_prefix (tests)
+    DevBuf spec_skip[SPEC_LISTS];                                // a speculated shard start: the record starts on the chains of its failed candidates
+    uint64_t tile_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // dhts_debug_tile_stats: what the record stage's repair and retry paths did since open / rewind
     // block table
     int64_t n_blocks = 0; int bgzf_status = 0;
     DevBuf coff, clen, isize, uoff, blk_status;
@@ -467,6 +471,7 @@ static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
     c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
+    memset(c->tile_stats, 0, sizeof(c->tile_stats));
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
 

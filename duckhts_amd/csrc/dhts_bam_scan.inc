@@ -268,6 +268,14 @@ extern "C" int64_t dhts_tabix_build_index(dhts_ctx *c, int preset, int sc, int b
     return (int64_t)c->built_index.size();
 }
 
+// tests: what the repair and retry paths of the record stage (read_bam and read_bcf alike) did since the context was opened or rewound.
+// Host-side counters, bumped where the driver reads the repair rounds' counts and decides about a speculated shard start.
+extern "C" int dhts_debug_tile_stats(dhts_ctx *c, uint64_t out[8]) {
+    if (!c || !out) return -1;
+    memcpy(out, c->tile_stats, sizeof(c->tile_stats));
+    return 0;
+}
+
 // ---- the fused row pass (bam_tile_rows.hip) ------------------------------------------------------------------------------------------
 // OPT-IN (DHTS_ROWS=fused): measured slower than the three passes (profiles/r04/rows_fused_*.txt: 2.3-4.0 ms against 1.87 ms per 19,813-block
 // batch).  The record stage is bound by instruction issue, not by HBM bytes (a tile costs ~7.5 k SIMD-cycles in the unpack part and ~10 k in the
@@ -433,7 +441,11 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
     uint64_t first0 = NONE64;
     // A shard that starts mid-stream speculates its first record.  If the chain that grows from the candidate breaks inside this
     // batch, the candidate was a false start (or the file is damaged): resume the search behind it.  The true first record always
-    // survives; when every retry fails as well the damage is real and the first attempt's result stands.
+    // survives.  Every record start on a failed candidate's chain would, taken as a candidate, walk the same hops to the same break: the
+    // retries pass over them (bam_spec_next with the chains' record starts as skip lists), so a failed chain costs ONE tile pass however long
+    // it is -- a chain of decoys in a valid file, or the true chain of a damaged shard.  The search ends when a candidate stands or none is
+    // left; then the damage is real and the first attempt's result stands.  It does not end at a count of retries, which a valid file with
+    // enough decoys in front of the record would reach.
     const bool speculative = (start0 == NONE64);
     // The rows are queued behind the tile pass WITHOUT a host round trip where nothing in between needs the host: no speculated shard
     // start, no region filter (its row map comes from a scan over all rows), no shard end inside the batch (rows are cut on the host).
@@ -441,15 +453,26 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
     // pass's verdicts, the inflate's block status, the first invalid row, the heap sizes and the overflow flags: one round trip per batch.
     const bool fused = !speculative && !(c->rg_active && !c->rg_all) && !(sharded_tail && out_base + ulen > c->h_uoff[c->shard_b1]) && rows_deferred_on();
     unsigned long long hres[16] = {0}; RowsQueued rq;
-    uint64_t spec_from = 0; int spec_tries = 0; bool restoring = false;
+    uint64_t spec_from = 0, en0 = NONE64; int spec_tries = 0; bool restoring = false;
+    SpecSkip sk; memset(&sk, 0, sizeof(sk));
     int status_attempt = 0;
     for (;;) {
+        uint64_t start_eff = start0;
+        if (speculative && !restoring && spec_tries > 0) {
+            // a retry: the next candidate behind the failed one that is no member of a failed chain
+            uint64_t *d_cand = (uint64_t *)c->d_nfixed.p + 2, cand = NONE64;
+            hipLaunchKernelGGL(bam_spec_next, dim3(1), dim3(64), 0, c->stream, st, spec_from, sk, d_cand);
+            HIPCHK(c, hipMemcpyAsync(&cand, d_cand, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (cand == NONE64) { spec_from = 0; restoring = true; c->tile_stats[DHTS_TS_GAVE_UP]++; }      // none left: the first attempt is made again and stands
+            else { start_eff = cand; c->tile_stats[DHTS_TS_RETRIES]++; }
+        }
         to.first = (uint64_t *)c->t_first.p; to.end_next = (uint64_t *)c->t_end.p; to.count = (uint32_t *)c->t_count.p; to.err = (int32_t *)c->t_err.p;
         to2.first = (uint64_t *)c->t2_first.p; to2.end_next = (uint64_t *)c->t2_end.p; to2.count = (uint32_t *)c->t2_count.p; to2.err = (int32_t *)c->t2_err.p;
         uint32_t nfh[2] = {0, 0}, bst[4] = {NONE32, 0, NONE32, 0};
         {
             KTimer tm(c, DHTS_K_TILES);
-            hipLaunchKernelGGL(bam_tile_scan, dim3((unsigned)ntiles), dim3(64), 0, c->stream, st, start0, ntiles, to, (uint16_t *)c->t_recs.p, (uint64_t *)c->t_recs_first.p, spec_from);
+            hipLaunchKernelGGL(bam_tile_scan, dim3((unsigned)ntiles), dim3(64), 0, c->stream, st, start_eff, ntiles, to, (uint16_t *)c->t_recs.p, (uint64_t *)c->t_recs_first.p, spec_from);
             // two repair rounds are queued unconditionally (a 30x BAM converges in two; a round that finds nothing to repair copies the table)
             uint32_t *nf = (uint32_t *)c->d_nfixed.p;
             (void)hipMemsetAsync(nf, 0, 8, c->stream);
@@ -463,6 +486,7 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
         if (fused) { if (rows_queue(c, st, ntiles, to, colmask, rq)) return -1; HIPCHK(c, hipMemcpyAsync(hres, c->d_res.p, 128, hipMemcpyDeviceToHost, c->stream)); }
         HIPCHK(c, hipMemcpyAsync(res, c->d_res.p, 32, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(&first0, to.first, 8, hipMemcpyDeviceToHost, c->stream));
+        if (speculative) HIPCHK(c, hipMemcpyAsync(&en0, to.end_next, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(nfh, c->d_nfixed.p, 8, hipMemcpyDeviceToHost, c->stream));
         if (B.status_pending) HIPCHK(c, hipMemcpyAsync(bst, c->d_bstat.p, 16, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -473,15 +497,16 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
                 ulen = B.ulen; final_batch = B.final_batch;
                 st.ulen = ulen; st.final_batch = final_batch ? 1 : 0; c->last_stream = st;
                 ntiles = (int64_t)((ulen + TILE_BYTES - 1) / TILE_BYTES); if (ntiles < 1) ntiles = 1;
-                spec_from = 0; spec_tries = 0; restoring = false;
+                spec_from = 0; spec_tries = 0; restoring = false; sk.lists = 0;
                 continue;
             }
         }
         if (g_debug) fprintf(stderr, "[dhts] tiles=%lld nfixed=%u,%u\n", (long long)ntiles, nfh[0], nfh[1]);
+        c->tile_stats[DHTS_TS_REPAIRED] += (uint64_t)nfh[0] + nfh[1]; c->tile_stats[DHTS_TS_ROUNDS] += (nfh[0] != 0) + (nfh[1] != 0);
         if (nfh[1] != 0) {
             // the second round still repaired tiles: go on round by round, then finalize again
             KTimer tm(c, DHTS_K_TILES);
-            int rounds = 2;
+            int rounds = 2; bool seq_fallback = false;
             for (;;) {
                 (void)hipMemsetAsync(c->d_nfixed.p, 0, 4, c->stream);
                 hipLaunchKernelGGL(bam_tile_fix, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, c->stream, st, TILE_BYTES, ntiles, to, to2, (uint32_t *)c->d_nfixed.p);
@@ -491,18 +516,36 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 if (g_debug) fprintf(stderr, "[dhts] tiles=%lld round=%d nfixed=%u\n", (long long)ntiles, rounds, nfixed);
                 if (nfixed == 0) break;
-                if (++rounds > 256) { hipLaunchKernelGGL(bam_tile_fix_seq, dim3(1), dim3(1), 0, c->stream, st, TILE_BYTES, ntiles, to); break; }
+                c->tile_stats[DHTS_TS_REPAIRED] += nfixed; c->tile_stats[DHTS_TS_ROUNDS]++;
+                if (++rounds > 256) {
+                    (void)hipMemsetAsync(c->d_nfixed.p, 0, 4, c->stream);
+                    hipLaunchKernelGGL(bam_tile_fix_seq, dim3(1), dim3(1), 0, c->stream, st, TILE_BYTES, ntiles, to, (uint32_t *)c->d_nfixed.p);
+                    seq_fallback = true; break;
+                }
             }
             hipLaunchKernelGGL(bam_tile_finalize, dim3(1), dim3(1024), 0, c->stream, ntiles, to, (uint32_t *)c->t_rowbase.p, (uint64_t *)c->d_res.p);
+            uint32_t nseq = 0;
+            if (seq_fallback) HIPCHK(c, hipMemcpyAsync(&nseq, c->d_nfixed.p, 4, hipMemcpyDeviceToHost, c->stream));
+            if (speculative) HIPCHK(c, hipMemcpyAsync(&en0, to.end_next, 8, hipMemcpyDeviceToHost, c->stream));
             if (fused) { if (rows_queue(c, st, ntiles, to, colmask, rq)) return -1; HIPCHK(c, hipMemcpyAsync(hres, c->d_res.p, 128, hipMemcpyDeviceToHost, c->stream)); }
             HIPCHK(c, hipMemcpyAsync(res, c->d_res.p, 32, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(&first0, to.first, 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (seq_fallback) { c->tile_stats[DHTS_TS_REPAIRED] += nseq; c->tile_stats[DHTS_TS_SEQ]++; }
         }
         if (!speculative || restoring) break;
+        // the candidate: tile 0 looks for it through the whole batch, so it may lie behind tile 0 (a long record runs across the shard's
+        // first tiles); tile 0 then holds no record and its chain exit IS the candidate
+        if (first0 == NONE64) first0 = en0;
+        if (start_eff != NONE64) first0 = start_eff;
         bool false_start = res[2] != 0 && first0 != NONE64;
-        const bool exhausted = spec_tries > 0 && first0 == NONE64;
-        if (!false_start && !exhausted && first0 != NONE64 && (int64_t)res[0] > 0) {
+        int64_t nskip = (int64_t)res[0];                        // the chain broke: every record on it leads to the same break
+        if (false_start && nskip > 0) {
+            ENSURE(c, c->rec_off, (size_t)nskip * 4 + 16);
+            hipLaunchKernelGGL(bam_tile_offsets, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, c->stream, st, TILE_BYTES, ntiles, to, (const uint32_t *)c->t_rowbase.p,
+                               (const uint64_t *)c->d_res.p, (uint32_t *)c->rec_off.p);
+        }
+        if (!false_start && first0 != NONE64 && (int64_t)res[0] > 0) {
             // the chain holds: do its "records" also pass bam_read1's full validation?  (only speculated shard starts pay for this pass)
             const int64_t nr = (int64_t)res[0];
             unsigned long long bad0 = ~0ull;
@@ -514,9 +557,15 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
             HIPCHK(c, hipMemcpyAsync(&bad0, (uint64_t *)c->d_res.p + 4, 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             false_start = bad0 < (unsigned long long)nr;
+            if (false_start) { nskip = (int64_t)bad0 + 1; c->tile_stats[DHTS_TS_VALIDATE]++; }      // the chain holds up to a record that is refused: the records up to it lead there
         }
-        if (!false_start && !exhausted) break;
-        if (exhausted || spec_tries == 16) { spec_from = 0; restoring = true; continue; }
+        if (!false_start) break;
+        if (nskip > 0 && sk.lists < SPEC_LISTS) {            // (with every list in use the later chains' members cost a tile pass each; nothing else changes)
+            DevBuf &sb = c->spec_skip[sk.lists];
+            ENSURE(c, sb, (size_t)nskip * 4 + 16);
+            HIPCHK(c, hipMemcpyAsync(sb.p, c->rec_off.p, (size_t)nskip * 4, hipMemcpyDeviceToDevice, c->stream));
+            sk.off[sk.lists] = (const uint32_t *)sb.p; sk.n[sk.lists] = (uint32_t)nskip; sk.lists++;
+        }
         spec_from = first0 + 1; spec_tries++;
     }
     int64_t nrows = (int64_t)res[0]; uint64_t carry_start = res[1]; bool rec_err = res[2] != 0;

@@ -197,7 +197,7 @@ int dhts_bcf_rewind(dhts_ctx *c) {
     discard_prefetch(c);
     if (!c->wins.empty()) enter_window(c, 0);
     c->next_block = c->shard_b0; c->carry_len = 0; c->stream_done = c->rg_empty_window; c->first_batch = true; c->ucur = 0;
-    c->huff_b0 = c->huff_nb = 0;
+    c->huff_b0 = c->huff_nb = 0; memset(c->tile_stats, 0, sizeof(c->tile_stats));
     skip_header_blocks(c);
     if (c->vcf_text && c->shard_rank != 0 && c->shard_b0 > 0 && c->wins.empty()) c->next_block = c->shard_b0 - 1;   // (the byte in front of the shard: see vcf_text_records)
     return 0;
@@ -554,9 +554,11 @@ static int bcf_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bcf_batch *o
     if (c->first_batch && c->shard_rank == 0 && c->scan_first_uoff < out_base) return fail(c, "internal: header beyond first batch");
     uint64_t res[4] = {0, 0, 0, 0};
     // (same false-start retry as in dhts_bam_next_batch: a speculated shard start whose chain breaks inside the batch, or whose
-    //  "records" fail bcf_record_check, is replaced by the next candidate; if every retry fails too, the first attempt stands)
+    //  "records" fail bcf_record_check, is replaced by the next candidate that is no member of a failed chain; when none is left the
+    //  damage is real and the first attempt stands)
     const bool speculative = (start0 == NONE64);
-    uint64_t first0 = NONE64, spec_from = 0; int spec_tries = 0; bool restoring = false;
+    uint64_t first0 = NONE64, en0 = NONE64, spec_from = 0; int spec_tries = 0; bool restoring = false;
+    SpecSkip sk; memset(&sk, 0, sizeof(sk));
     int64_t nrec = 0; uint64_t carry_start = 0; bool rec_err = false;
     // the scan range ends with its last block (later shards / the rest of the file exist) or, for one of several index windows, exactly
     // at the window's end: windows are disjoint, so no record is delivered twice
@@ -579,10 +581,19 @@ static int bcf_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bcf_batch *o
     for (;;) {
         to.first = (uint64_t *)c->t_first.p; to.end_next = (uint64_t *)c->t_end.p; to.count = (uint32_t *)c->t_count.p; to.err = (int32_t *)c->t_err.p;
         to2.first = (uint64_t *)c->t2_first.p; to2.end_next = (uint64_t *)c->t2_end.p; to2.count = (uint32_t *)c->t2_count.p; to2.err = (int32_t *)c->t2_err.p;
+        uint64_t start_eff = start0;
+        if (speculative && !restoring && spec_tries > 0) {
+            uint64_t *d_cand = (uint64_t *)c->d_nfixed.p + 2, cand = NONE64;
+            hipLaunchKernelGGL(bcf_spec_next, dim3(1), dim3(64), 0, c->stream, st, spec_from, sk, d_cand);
+            HIPCHK(c, hipMemcpyAsync(&cand, d_cand, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (cand == NONE64) { spec_from = 0; restoring = true; c->tile_stats[DHTS_TS_GAVE_UP]++; }
+            else { start_eff = cand; c->tile_stats[DHTS_TS_RETRIES]++; }
+        }
         {
             KTimer tm(c, DHTS_K_TILES);
-            hipLaunchKernelGGL(bcf_tile_scan, dim3((unsigned)ntiles), dim3(64), 0, c->stream, st, start0, ntiles, to, spec_from);
-            int rounds = 0;
+            hipLaunchKernelGGL(bcf_tile_scan, dim3((unsigned)ntiles), dim3(64), 0, c->stream, st, start_eff, ntiles, to, spec_from);
+            int rounds = 0; bool seq_fallback = false;
             for (;;) {
                 (void)hipMemsetAsync(c->d_nfixed.p, 0, 4, c->stream);
                 hipLaunchKernelGGL(bcf_tile_fix, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, c->stream, st, TILE_BYTES, ntiles, to, to2, (uint32_t *)c->d_nfixed.p);
@@ -592,12 +603,24 @@ static int bcf_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bcf_batch *o
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 if (g_debug) fprintf(stderr, "[dhts] bcf tiles=%lld round=%d nfixed=%u\n", (long long)ntiles, rounds, nfixed);
                 if (nfixed == 0) break;
-                if (++rounds > 256) { hipLaunchKernelGGL(bcf_tile_fix_seq, dim3(1), dim3(1), 0, c->stream, st, TILE_BYTES, ntiles, to); break; }
+                c->tile_stats[DHTS_TS_REPAIRED] += nfixed; c->tile_stats[DHTS_TS_ROUNDS]++;
+                if (++rounds > 256) {
+                    (void)hipMemsetAsync(c->d_nfixed.p, 0, 4, c->stream);
+                    hipLaunchKernelGGL(bcf_tile_fix_seq, dim3(1), dim3(1), 0, c->stream, st, TILE_BYTES, ntiles, to, (uint32_t *)c->d_nfixed.p);
+                    seq_fallback = true; break;
+                }
             }
             hipLaunchKernelGGL(bam_tile_finalize, dim3(1), dim3(1024), 0, c->stream, ntiles, to, (uint32_t *)c->t_rowbase.p, (uint64_t *)c->d_res.p);
+            if (seq_fallback) {
+                uint32_t nseq = 0;
+                HIPCHK(c, hipMemcpyAsync(&nseq, c->d_nfixed.p, 4, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                c->tile_stats[DHTS_TS_REPAIRED] += nseq; c->tile_stats[DHTS_TS_SEQ]++;
+            }
         }
         HIPCHK(c, hipMemcpyAsync(res, c->d_res.p, 32, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(&first0, to.first, 8, hipMemcpyDeviceToHost, c->stream));
+        if (speculative) HIPCHK(c, hipMemcpyAsync(&en0, to.end_next, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         nrec = (int64_t)res[0]; carry_start = res[1]; rec_err = res[2] != 0;
         if (carry_start == NONE64) carry_start = ulen;
@@ -619,9 +642,20 @@ static int bcf_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bcf_batch *o
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         if (!speculative || restoring) break;
-        const bool false_start = first0 != NONE64 && (res[2] != 0 || bad < (unsigned long long)nrec), exhausted = spec_tries > 0 && first0 == NONE64;
-        if (!false_start && !exhausted) break;
-        if (exhausted || spec_tries == 16) { spec_from = 0; restoring = true; continue; }
+        if (first0 == NONE64) first0 = en0;                     // (the candidate lies behind tile 0: see dhts_bam_next_batch)
+        if (start_eff != NONE64) first0 = start_eff;
+        const bool invalid_rec = bad < (unsigned long long)nrec;
+        const bool false_start = first0 != NONE64 && (res[2] != 0 || invalid_rec);
+        if (!false_start) break;
+        if (invalid_rec) c->tile_stats[DHTS_TS_VALIDATE]++;
+        // the records that lead to the same failure: all of a chain that broke, else those up to the refused one
+        const int64_t nskip = res[2] != 0 ? nrec : (int64_t)bad + 1;
+        if (nskip > 0 && sk.lists < SPEC_LISTS) {
+            DevBuf &sb = c->spec_skip[sk.lists];
+            ENSURE(c, sb, (size_t)nskip * 4 + 16);
+            HIPCHK(c, hipMemcpyAsync(sb.p, c->b_rec_off.p, (size_t)nskip * 4, hipMemcpyDeviceToDevice, c->stream));
+            sk.off[sk.lists] = (const uint32_t *)sb.p; sk.n[sk.lists] = (uint32_t)nskip; sk.lists++;
+        }
         spec_from = first0 + 1; spec_tries++;
     }
     if (nrec > 0) {

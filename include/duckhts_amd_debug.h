@@ -37,6 +37,15 @@ int dhts_debug_meta(dhts_ctx *, int64_t s, uint32_t *out4);
  * symbols (host arrays, case after case); lens_out: ncases * nsym code lengths, codes_out: the table words (bit-reversed code | length << 16).
  * Only for count vectors the builder's loops are known to end on (tests/deflate_code_ref.py). */
 int dhts_debug_deflate_codes(dhts_ctx *, const uint32_t *counts, uint32_t nsym, uint32_t maxbits, int64_t ncases, uint8_t *lens_out, uint32_t *codes_out);
+/* tests: what the record stage's repair and retry paths did since the context was opened or rewound (host-side counters, read_bam and
+ * read_bcf alike).  out[0] tiles changed by the repair rounds and by the sequential fallback, summed over rounds and batches;
+ * out[1] repair rounds that changed a tile (the two rounds read_bam always queues count only when they repaired something, so a file that
+ * speculates correctly shows 0; the sequential fallback is no round); out[2] batches that went on to the sequential fallback (more than 256 rounds);
+ * out[3] retries of a speculated shard start (candidates tried after the first one failed; record starts on a failed chain are passed over
+ * without a retry); out[4] candidates whose chain held but whose
+ * records the full validation refused (bam_validate_rows / bcf_rec_check); out[5] batches where no candidate was left and the first
+ * attempt's result was restored; out[6], out[7] zero. */
+int dhts_debug_tile_stats(dhts_ctx *, uint64_t out[8]);
 /* (diagnostic builds only: -DDHTS_DIAG dhts_debug_diag, -DHW_DIAG dhts_debug_hw_diag, -DTR_DIAG dhts_debug_tr_diag: per-phase cycle counters) */
 int dhts_debug_diag(dhts_ctx *, unsigned long long *out8);
 int dhts_debug_hw_diag(dhts_ctx *, unsigned long long *out16, int reset);

@@ -76,6 +76,16 @@ class BedBatch(C.Structure):
     _fields_ = [("n_rows", C.c_int64), ("status", C.c_int32), ("n_cols", C.c_int32), ("cols", C.POINTER(BcfCol))]
 
 
+class BinsParams(C.Structure):
+    _fields_ = [("bin_width", C.c_int64), ("min_mapq", C.c_int32), ("require_flags", C.c_int32), ("exclude_flags", C.c_int32), ("include_flags", C.c_int32),
+                ("dedup", C.c_int32), ("emit_zero_bins", C.c_int32)]
+
+
+class BinsStats(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_flag_filtered", C.c_uint64), ("n_unplaced", C.c_uint64), ("n_out_of_range", C.c_uint64), ("n_duplicate", C.c_uint64),
+                ("n_low_mapq", C.c_uint64), ("n_counted", C.c_uint64), ("total_bins", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TabixMap(C.Structure):
     _fields_ = [("pair_off", C.c_void_p), ("valid", C.c_void_p), ("n_pairs", C.c_uint64), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p), ("key_nbytes", C.c_uint64),
                 ("val_off", C.c_void_p), ("val_bytes", C.c_void_p), ("val_nbytes", C.c_uint64)]
@@ -128,6 +138,9 @@ BED_INT_COLUMNS = (1, 2, 6, 7, 9)
 NUC_COLUMNS = ["chrom", "start", "end", "pct_at", "pct_gc", "num_a", "num_c", "num_g", "num_t", "num_n", "num_other", "seq_len", "seq"]
 NUC_DOUBLE_COLUMNS = (3, 4)
 NUC_STR_COLUMNS = (0, 12)
+BINS_COLUMNS = ["chrom", "start", "end", "bin_id", "count_total", "count_fwd", "count_rev"]
+BINS_DEDUP = {"none": 0, "adjacent": 1}
+BINS_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 7)        # FLAG, RNAME, POS, MAPQ, PNEXT: no string column
 
 # DUCKDB_TYPE_* element codes -> the canonical type tags of the test oracle's column blob
 _CANON_TYPE = {17: 1, 5: 2, 11: 3, 1: 4, 4: 5, 10: 6}
@@ -144,6 +157,7 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_fasta_build_index", "dhts_fasta_index_bytes", "dhts_fasta_gzi_bytes", "dhts_fasta_load_index", "dhts_fasta_open_regions", "dhts_fasta_fetch", "dhts_fasta_batch_host_bytes", "dhts_fasta_batch_fetch",
            "dhts_bed_open", "dhts_bed_set_projection", "dhts_bed_set_region", "dhts_bed_load_index", "dhts_bed_region_segments", "dhts_bed_next_batch", "dhts_bed_batch_host_bytes", "dhts_bed_batch_fetch",
            "dhts_nuc_open_region", "dhts_nuc_open", "dhts_nuc_set_region", "dhts_nuc_set_projection", "dhts_nuc_next_bins", "dhts_nuc_next_bed", "dhts_nuc_intervals", "dhts_nuc_batch_host_bytes", "dhts_nuc_batch_fetch",
+           "dhts_bam_bins_open", "dhts_bam_bins_accumulate", "dhts_bam_bins_scan", "dhts_bam_bins_stats", "dhts_bam_bins_next", "dhts_bam_bins_batch_host_bytes", "dhts_bam_bins_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
            "dhts_udf_upload", "dhts_udf_apply", "dhts_udf_result_host_bytes", "dhts_udf_fetch", "dhts_udf_seq_kmers", "dhts_udf_kmers_host_bytes", "dhts_udf_kmers_fetch"]
@@ -238,6 +252,14 @@ def lib():
         L.dhts_nuc_batch_host_bytes.restype = C.c_uint64
         L.dhts_nuc_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_nuc_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_bam_bins_open.argtypes = [C.c_void_p, C.POINTER(BinsParams)]
+        L.dhts_bam_bins_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
+        L.dhts_bam_bins_scan.argtypes = [C.c_void_p, C.c_int64]
+        L.dhts_bam_bins_stats.argtypes = [C.c_void_p, C.POINTER(BinsStats)]
+        L.dhts_bam_bins_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
+        L.dhts_bam_bins_batch_host_bytes.restype = C.c_uint64
+        L.dhts_bam_bins_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
+        L.dhts_bam_bins_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
         L.dhts_tabix_open.argtypes = [C.c_void_p, C.c_int]
         L.dhts_tabix_set_conf.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dhts_tabix_index_conf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -673,6 +695,46 @@ class Context:
         b = BedBatch()
         self._chk(self.L.dhts_nuc_intervals(self.h, t.ctypes.data, s.ctypes.data, e.ctypes.data, len(t), C.byref(b)))
         return self.nuc_batch_columns(b)
+
+    # ---- bam_bin_counts (the batch has dhts_bed_batch's layout) ----
+    def bam_bins_open(self, bin_width=5000, min_mapq=0, include_flags=0, require_flags=0, exclude_flags=0, dedup="none", emit_zero_bins=False):
+        """after bam_open and the optional set_regions / load_index: the table of counters, zeroed"""
+        if dedup not in BINS_DEDUP:
+            raise DhtsError("bam_bin_counts: dedup must be one of: none, adjacent")
+        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
+        p = BinsParams(clip(bin_width, 63), clip(min_mapq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31), BINS_DEDUP[dedup], int(bool(emit_zero_bins)))
+        self._chk(self.L.dhts_bam_bins_open(self.h, C.byref(p)))
+
+    def bam_bins_accumulate(self, b):
+        self._chk(self.L.dhts_bam_bins_accumulate(self.h, C.byref(b)))
+
+    def bam_bins_scan(self, max_blocks=0):
+        """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
+        rc = self.L.dhts_bam_bins_scan(self.h, max_blocks)
+        if rc < 0:
+            msg = self.L.dhts_error(self.h).decode()
+            if self.bam_bins_stats()["status"] == 0:                      # a call failed (a stream that ended on an error has set its status)
+                raise DhtsError(msg)
+        return rc
+
+    def bam_bins_stats(self):
+        st = BinsStats()
+        self._chk(self.L.dhts_bam_bins_stats(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in BinsStats._fields_ if k != "reserved"}
+
+    def bam_bins_next(self, max_rows=0):
+        """the next rows of the result: ({"n_rows", column: int64 array; chrom = the contig's id}, status)"""
+        b = BedBatch()
+        self._chk(self.L.dhts_bam_bins_next(self.h, max_rows, C.byref(b)))
+        need = int(self.L.dhts_bam_bins_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        self._chk(self.L.dhts_bam_bins_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
+        n = int(b.n_rows)
+        out = {"n_rows": n}
+        for i in range(b.n_cols):
+            out[BINS_COLUMNS[host[i].col]] = np.ctypeslib.as_array(C.cast(host[i].fixed, C.POINTER(C.c_int64)), (n,)).copy() if n else np.zeros(0, np.int64)
+        return out, int(b.status)
 
     # ---- seq_* / cigar_* / SAM flag functions on device columns (dhts_udf_*) ----
     def udf_upload(self, values, slot=0, kind="str", const=False, reserve=0):
@@ -1671,6 +1733,41 @@ def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, s
                 out[k] = np.concatenate(vals)
             else:
                 out[k] = [x for v in vals for x in v]
+        return out
+    finally:
+        ctx.close()
+
+
+def bam_bin_counts(src, bin_width=5000, min_mapq=0, include_flags=0, require_flags=0, exclude_flags=0, dedup="none", region=None, index=None, emit_zero_bins=False,
+                   device=0, max_blocks=0, max_rows=0):
+    """bam_bin_counts(path, bin_width :=, min_mapq :=, include_flags :=, require_flags :=, exclude_flags :=, dedup :=, region :=, index_path :=,
+    emit_zero_bins :=): read-start counts in fixed-width bins, accumulated on the device (the contract: include/duckhts_amd.h).
+    {"n_rows", "chrom": list of bytes, "start" .. "count_rev": int64 arrays, "stats": the seven counters, "status": how the stream ended}.
+    index: BAI / CSI bytes narrowing the scan of a region query."""
+    ctx = Context(device)
+    try:
+        ctx.open(src)
+        ctx.bgzf_index()
+        hdr = ctx.bam_open()
+        if region is not None:
+            if not ctx.set_regions(region):
+                raise DhtsError(f"No reads found for region(s): {region}")
+            if index is not None:
+                ctx.load_index(index)
+        ctx.bam_bins_open(bin_width, min_mapq, include_flags, require_flags, exclude_flags, dedup, emit_zero_bins)
+        status = ctx.bam_bins_scan(max_blocks)
+        parts = []
+        while True:
+            cols, st = ctx.bam_bins_next(max_rows)
+            parts.append(cols)
+            if st != 0:
+                break
+        out = {k: np.concatenate([p[k] for p in parts]) for k in BINS_COLUMNS}
+        names = [n.encode() if isinstance(n, str) else bytes(n) for n in hdr["ref_names"]]
+        out["chrom"] = [names[t] for t in out["chrom"]]
+        out["n_rows"] = len(out["chrom"])
+        out["stats"] = {k: v for k, v in ctx.bam_bins_stats().items() if k.startswith("n_")}
+        out["status"] = status
         return out
     finally:
         ctx.close()

@@ -16,6 +16,7 @@
 #include "fasta_index.hip"
 #include "fasta_nuc.hip"
 #include "seq_udf.hip"
+#include "bam_bins.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -198,6 +199,14 @@ struct NucState {
     DevBuf ents, names, table, cum, in_tid, in_start, in_end, tmp, keep, rank, src, rows, err, npieces, piece_off, counts;
     DevBuf name_len, name_off, name_bytes, name_valid, seq_len, seq_off32, seq_off64, seq_valid, ones, fixed[NUC_N_COLS];
 };
+// bam_bin_counts (bam_bins.hip, dhts_bam_bins.inc): the parameters, the table of counters (two 64-bit words per bin) with the bins in front of
+// every contig, the step counters, the duplicate rule's last visible row (two slots used in turn), per-batch scratch, and the window of the
+// table the result is being paged out of
+struct BinsState {
+    bool open = false, table_ready = false; dhts_bins_params P; uint64_t total_bins = 0; int32_t n_ref = 0, status = 0; int carry_cur = 0;
+    uint64_t win_b0 = 0, win_rows = 0, win_done = 0; uint32_t win_n = 0; std::vector<dhts_col> out;
+    DevBuf counts, steps, carry, bin_base, ref_len, zero_ok, step, word, vis, rank, src, keep, krank, ones, cols[DHTS_BINS_COL_COUNT];
+};
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
 struct UdfState {
@@ -241,6 +250,7 @@ struct dhts_ctx {
     FastaState fa;
     BedState bed;
     NucState nuc;
+    BinsState bins;
     UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
@@ -330,6 +340,7 @@ struct dhts_ctx {
     // scan position
     int64_t shard_b0 = 0, shard_b1 = 0;   // block range of this shard
     int shard_rank = 0, shard_world = 1;
+    bool range_cut = false;               // dhts_bam_set_shard / _set_block_range / _set_file_shard left less than the whole file (the windows of a region query are no such cut)
     int64_t next_block = 0; bool stream_done = false; bool first_batch = true;
     int64_t halo_limit = 0;
     // timing
@@ -469,8 +480,8 @@ static void stop_stager(dhts_ctx *c) {
 }
 static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
-    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
-    c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
+    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->bins.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
+    c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->range_cut = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     memset(c->tile_stats, 0, sizeof(c->tile_stats));
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
@@ -525,6 +536,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bed_scan.inc"
 #include "dhts_tabix_scan.inc"
 #include "dhts_fasta_nuc.inc"
+#include "dhts_bam_bins.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

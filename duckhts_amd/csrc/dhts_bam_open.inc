@@ -227,6 +227,7 @@ int dhts_bam_set_block_range(dhts_ctx *c, int64_t b0, int64_t b1, int speculativ
     if (c->sam_text && (b0 != 0 || b1 != c->n_blocks || speculative_start)) return fail(c, "read_bam: shards of SAM text are not supported (%s)", SAM_SEQ_ONLY);
     c->wins.clear(); c->scan_end_uoff = ~0ull;
     c->shard_b0 = b0; c->shard_b1 = b1; c->shard_rank = speculative_start ? 1 : 0; c->shard_world = (b1 < c->n_blocks || speculative_start) ? 2 : 1;
+    c->range_cut = b0 != 0 || c->shard_world != 1;
     c->scan_first_uoff = c->first_rec_uoff;
     return dhts_bam_rewind(c);
 }

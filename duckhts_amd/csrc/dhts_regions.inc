@@ -77,7 +77,7 @@ int dhts_bam_set_regions(dhts_ctx *c, const char *regions) {
     HIPCHK(c, hipSetDevice(c->device));
     c->rg_active = false; c->rg_all = false; c->rg_nocoor = false; c->rg_empty_window = false; c->rg_beg.clear(); c->rg_end.clear(); c->rg_tid_first.clear();
     c->wins.clear(); c->win_cur = 0; c->scan_end_uoff = ~0ull;
-    c->scan_first_uoff = c->first_rec_uoff; c->shard_b0 = 0; c->shard_b1 = c->n_blocks; c->shard_rank = 0; c->shard_world = 1;
+    c->scan_first_uoff = c->first_rec_uoff; c->shard_b0 = 0; c->shard_b1 = c->n_blocks; c->shard_rank = 0; c->shard_world = 1; c->range_cut = false;
     if (!regions || !*regions) return dhts_bam_rewind(c);
     const size_t n_ref = c->ref_name.size();
     std::vector<std::vector<std::pair<int64_t, int64_t>>> per(n_ref);

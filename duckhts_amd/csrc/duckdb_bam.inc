@@ -103,13 +103,9 @@ __attribute__((target("ssse3"))) static inline void expand_seq(const uint8_t *sr
     (void)g_seq_pair_init;
 }
 
-static void bam_read_bind(duckdb_bind_info info) {
-    auto set_error = API(void, duckdb_bind_set_error, duckdb_bind_info, const char *);
-    std::string file_path, region, idx;
-    if (!take_path(info, file_path)) { set_error(info, "read_bam requires a file path"); return; }                          // bam_reader.c:416
-    (void)named_string(info, "region", region); (void)named_string(info, "index_path", idx);          // (reference is accepted and not read: CRAM is refused)
-    const int standard_tags = named_flag(info, "standard_tags"), auxiliary_tags = named_flag(info, "auxiliary_tags");
-    BamBind *b = new BamBind();
+// What bind does with the file, for read_bam and for bam_bin_counts: the head of the file on a bind-time context, the header, the index
+// lookup, the region string.  false: `error` is the bind error (the caller destroys b).
+static bool bam_bind_file(BamBind *b, const char *fn_name, const std::string &file_path, const std::string &region, const std::string &idx, std::string &error) {
     b->path = file_path;
     // parse_regions (bam_reader.c:319-345) splits with strtok: a string without a non-empty token ('' or ',,') is no region at all
     const bool has_region = region.find_first_not_of(',') != std::string::npos;
@@ -117,29 +113,29 @@ static void bam_read_bind(duckdb_bind_info info) {
     char err[768];
     if (!file_exists(b->path)) {
         snprintf(err, sizeof(err), "Failed to open SAM/BAM/CRAM file: %s", b->path.c_str());   // bam_reader.c:446
-        set_error(info, err); delete b; return;
+        error = err; return false;
     }
     static const bool trace_bind = getenv("DHTS_TRACE") != nullptr;
     const double tb0 = now_s();
     std::string no_device;
-    b->ctx = create_ctx("read_bam", no_device);
+    b->ctx = create_ctx(fn_name, no_device);
     const double tb1 = now_s();
-    if (!b->ctx) { set_error(info, no_device.c_str()); destroy_bind(b); return; }
+    if (!b->ctx) { error = no_device; return false; }
     // like the reference, bind reads the header only (sam_open + sam_hdr_read, bam_reader.c:441-461): the head of the file is staged,
     // four times more whenever the header turns out to be longer.  The scan stages the file itself (bam_read_global_init).
     bool hdr_ok = false;
     for (uint64_t head = 1u << 20;; head *= 4) {
         if (dhts_open_path_range(b->ctx, b->path.c_str(), 0, head) != 0) {
             snprintf(err, sizeof(err), "Failed to open SAM/BAM/CRAM file: %s", b->path.c_str());
-            set_error(info, err); destroy_bind(b); return;
+            error = err; return false;
         }
         const bool whole = dhts_resident_bytes(b->ctx) < head;
         if (dhts_bgzf_index(b->ctx) > 0 && dhts_bam_open(b->ctx) == 0 && dhts_bam_header_get(b->ctx, &b->hdr) == 0) { hdr_ok = true; break; }
         if (whole || head >= (1ull << 34)) break;
     }
     if (!hdr_ok) {
-        set_error(info, "Failed to read SAM/BAM/CRAM header");                    // bam_reader.c:461 (also what SAM/CRAM input gets here)
-        destroy_bind(b); return;
+        error = "Failed to read SAM/BAM/CRAM header";                             // bam_reader.c:461 (also what SAM/CRAM input gets here)
+        return false;
     }
     b->header_bytes = dhts_bam_header_bytes(b->ctx);
     if (trace_bind) fprintf(stderr, "[dhts] bind: context %.4f s, head of the file + block table + header %.4f s\n", tb1 - tb0, now_s() - tb1);
@@ -155,6 +151,18 @@ static void bam_read_bind(duckdb_bind_info info) {
     }
     b->has_index = !b->index_file.empty();                                       // bam_reader.c:499-503
     if (has_region) b->region = region;
+    return true;
+}
+
+static void bam_read_bind(duckdb_bind_info info) {
+    auto set_error = API(void, duckdb_bind_set_error, duckdb_bind_info, const char *);
+    std::string file_path, region, idx;
+    if (!take_path(info, file_path)) { set_error(info, "read_bam requires a file path"); return; }                          // bam_reader.c:416
+    (void)named_string(info, "region", region); (void)named_string(info, "index_path", idx);          // (reference is accepted and not read: CRAM is refused)
+    const int standard_tags = named_flag(info, "standard_tags"), auxiliary_tags = named_flag(info, "auxiliary_tags");
+    BamBind *b = new BamBind();
+    std::string bind_error;
+    if (!bam_bind_file(b, "read_bam", file_path, region, idx, bind_error)) { set_error(info, bind_error.c_str()); destroy_bind(b); return; }
     b->standard_tags = standard_tags; b->auxiliary_tags = auxiliary_tags;
 
     static const char *const core_names[DHTS_BAM_CORE_COUNT] = {"QNAME", "FLAG", "RNAME", "POS", "MAPQ", "CIGAR", "RNEXT", "PNEXT", "TLEN", "SEQ", "QUAL", "READ_GROUP_ID", "SAMPLE_ID"};   // bam_reader.c:514-526
@@ -371,6 +379,37 @@ static void producer_main(BamScan *g, Producer *p) {
     g->cv_ready.notify_all();
 }
 
+// What init does with the region of a query, for read_bam and for bam_bin_counts: the index is required, the regions are validated on the
+// bind context, the index bytes are read and turned into the file byte ranges to stage (seg_count -1: the whole file).  false: `error`.
+static bool bam_region_prepare(BamBind *bind, std::vector<uint8_t> &index_bytes, std::vector<uint64_t> &seg_beg, std::vector<uint64_t> &seg_end, int64_t &seg_count, std::string &error) {
+    if (bind->region.empty()) return true;
+    {
+        // bam_reader.c:639-668: a region needs an index; sam_itr_regarray failing reports "No reads found"
+        if (!bind->has_index) { error = "Region query requires an index (.bai/.csi/.crai)"; return false; }
+        int rc = dhts_bam_set_regions(bind->ctx, bind->region.c_str());          // (validated on the bind context: it holds the header)
+        if (rc != 0) {
+            char err[640]; snprintf(err, sizeof(err), "No reads found for region(s): %s", bind->region.c_str());
+            error = rc == 1 ? err : dhts_error(bind->ctx); return false;
+        }
+        // the index (BAI or CSI) narrows the scan window; the device predicate decides the rows
+        FILE *f = fopen(bind->index_file.c_str(), "rb");
+        if (f) {
+            std::vector<uint8_t> ib; uint8_t tmp[65536]; size_t k;
+            while ((k = fread(tmp, 1, sizeof(tmp), f)) > 0) ib.insert(ib.end(), tmp, tmp + k);
+            fclose(f);
+            const bool known = ib.size() >= 4 && (memcmp(ib.data(), "BAI\1", 4) == 0 || memcmp(ib.data(), "CSI\1", 4) == 0 || (ib[0] == 0x1f && ib[1] == 0x8b));
+            if (known) index_bytes.swap(ib);
+        }
+        // only the index windows are staged (the reference seeks to them): byte ranges from the bind context, which holds the header
+        static const bool env_nosparse = getenv("DHTS_SPARSE") && atoi(getenv("DHTS_SPARSE")) == 0;
+        if (!index_bytes.empty() && !env_nosparse) {
+            seg_beg.resize(4096); seg_end.resize(4096);
+            if (dhts_bam_region_segments(bind->ctx, index_bytes.data(), index_bytes.size(), seg_beg.data(), seg_end.data(), 4096, &seg_count) != 0) seg_count = -1;   // fall back to the whole file
+        }
+    }
+    return true;
+}
+
 static void bam_read_global_init(duckdb_init_info info) {
     BamBind *bind = (BamBind *)API(void *, duckdb_init_get_bind_data, duckdb_init_info)(info);
     auto init_error = API(void, duckdb_init_set_error, duckdb_init_info, const char *);
@@ -388,30 +427,7 @@ static void bam_read_global_init(duckdb_init_info info) {
         g->tag_slot.push_back(sl);
         if (bind->auxiliary_tags && id == bind->aux_col_idx) g->want_aux = true;
     }
-    if (!bind->region.empty()) {
-        // bam_reader.c:639-668: a region needs an index; sam_itr_regarray failing reports "No reads found"
-        if (!bind->has_index) { init_error(info, "Region query requires an index (.bai/.csi/.crai)"); delete g; return; }
-        int rc = dhts_bam_set_regions(bind->ctx, bind->region.c_str());          // (validated on the bind context: it holds the header)
-        if (rc != 0) {
-            char err[640]; snprintf(err, sizeof(err), "No reads found for region(s): %s", bind->region.c_str());
-            init_error(info, rc == 1 ? err : dhts_error(bind->ctx)); delete g; return;
-        }
-        // the index (BAI or CSI) narrows the scan window; the device predicate decides the rows
-        FILE *f = fopen(bind->index_file.c_str(), "rb");
-        if (f) {
-            std::vector<uint8_t> ib; uint8_t tmp[65536]; size_t k;
-            while ((k = fread(tmp, 1, sizeof(tmp), f)) > 0) ib.insert(ib.end(), tmp, tmp + k);
-            fclose(f);
-            const bool known = ib.size() >= 4 && (memcmp(ib.data(), "BAI\1", 4) == 0 || memcmp(ib.data(), "CSI\1", 4) == 0 || (ib[0] == 0x1f && ib[1] == 0x8b));
-            if (known) g->index_bytes.swap(ib);
-        }
-        // only the index windows are staged (the reference seeks to them): byte ranges from the bind context, which holds the header
-        static const bool env_nosparse = getenv("DHTS_SPARSE") && atoi(getenv("DHTS_SPARSE")) == 0;
-        if (!g->index_bytes.empty() && !env_nosparse) {
-            g->seg_beg.resize(4096); g->seg_end.resize(4096);
-            if (dhts_bam_region_segments(bind->ctx, g->index_bytes.data(), g->index_bytes.size(), g->seg_beg.data(), g->seg_end.data(), 4096, &g->seg_count) != 0) g->seg_count = -1;   // fall back to the whole file
-        }
-    }
+    { std::string rg_error; if (!bam_region_prepare(bind, g->index_bytes, g->seg_beg, g->seg_end, g->seg_count, rg_error)) { init_error(info, rg_error.c_str()); delete g; return; } }
     // sequential mode unless the user asks for parallel fill (bam_reader.c:577-585: the reference goes parallel only with an index)
     int thr = getenv("DHTS_THREADS") ? atoi(getenv("DHTS_THREADS")) : 1; if (thr < 1) thr = 1; if (thr > 64) thr = 64;
     g->n_workers = thr;

@@ -1,0 +1,113 @@
+// duckdb_bins.inc -- part of duckdb_ext.cpp (included there behind duckdb_bam.inc; not a translation unit of its own): the bam_bin_counts table function.
+// bam_bin_counts(path, bin_width, min_mapq, include_flags, require_flags, exclude_flags, dedup, region, index_path, emit_zero_bins): read-start
+// counts in fixed-width bins (the contract: include/duckhts_amd.h).  bind checks the parameters and opens the file as read_bam does
+// (bam_bind_file, bam_region_prepare: the same errors); init stages the file -- for a region only the index windows -- and runs the whole
+// scan on one device: no row leaves it; the scan callback pages the table's rows out, vector_size rows per chunk.
+static const char *const kBinsCols[DHTS_BINS_COL_COUNT] = {"chrom", "start", "end", "bin_id", "count_total", "count_fwd", "count_rev"};
+static const int32_t kBinsTypes[DHTS_BINS_COL_COUNT] = {DHTS_T_VARCHAR, DHTS_T_BIGINT, DHTS_T_BIGINT, DHTS_T_BIGINT, DHTS_T_BIGINT, DHTS_T_BIGINT, DHTS_T_BIGINT};
+struct BinsBind {
+    BamBind bam; dhts_bins_params P;
+    std::vector<uint8_t> index_bytes; std::vector<uint64_t> seg_beg, seg_end; int64_t seg_count = -1;
+    ~BinsBind() { if (bam.ctx) dhts_destroy(bam.ctx); }
+};
+struct BinsScanState {
+    dhts_ctx *ctx = nullptr; BinsBind *bind = nullptr; PinnedArena arena; Projection pj; ColBatch cb; bool want_chrom = false;
+    std::vector<uint32_t> chrom_off; std::string chrom_bytes;                  // the chrom column of the batch at hand: the contigs' names by id
+    ~BinsScanState() { if (ctx) dhts_destroy(ctx); }
+};
+static void destroy_bins_bind(void *p) { delete (BinsBind *)p; }
+static void destroy_bins_scan(void *p) { delete (BinsScanState *)p; }
+static void bam_bin_counts_bind(duckdb_bind_info info) {
+    auto set_error = API(void, duckdb_bind_set_error, duckdb_bind_info, const char *);
+    std::string file_path, region, idx, dedup = "none";
+    if (!take_path(info, file_path)) { set_error(info, "bam_bin_counts requires a file path"); return; }
+    BinsBind *b = new BinsBind();
+    int64_t bin_width = 5000, min_mapq = 0, include_flags = 0, require_flags = 0, exclude_flags = 0;
+    (void)named_int(info, "bin_width", &bin_width); (void)named_int(info, "min_mapq", &min_mapq);
+    (void)named_int(info, "include_flags", &include_flags); (void)named_int(info, "require_flags", &require_flags); (void)named_int(info, "exclude_flags", &exclude_flags);
+    (void)named_string(info, "dedup", dedup); (void)named_string(info, "region", region); (void)named_string(info, "index_path", idx);
+    const bool emit_zero = named_flag(info, "emit_zero_bins");
+    const char *bad = nullptr;
+    if (bin_width <= 0) bad = "bam_bin_counts: bin_width must be > 0";
+    else if (min_mapq < 0 || min_mapq > 255) bad = "bam_bin_counts: min_mapq must be between 0 and 255";
+    else if (include_flags < 0 || include_flags > 65535) bad = "bam_bin_counts: include_flags must be between 0 and 65535";
+    else if (require_flags < 0 || require_flags > 65535) bad = "bam_bin_counts: require_flags must be between 0 and 65535";
+    else if (exclude_flags < 0 || exclude_flags > 65535) bad = "bam_bin_counts: exclude_flags must be between 0 and 65535";
+    else if (dedup != "none" && dedup != "adjacent") bad = "bam_bin_counts: dedup must be one of: none, adjacent";
+    if (bad) { set_error(info, bad); delete b; return; }
+    b->P.bin_width = bin_width; b->P.min_mapq = (int32_t)min_mapq; b->P.include_flags = (int32_t)include_flags; b->P.require_flags = (int32_t)require_flags; b->P.exclude_flags = (int32_t)exclude_flags;
+    b->P.dedup = dedup == "adjacent" ? DHTS_BINS_DEDUP_ADJACENT : DHTS_BINS_DEDUP_NONE; b->P.emit_zero_bins = emit_zero ? 1 : 0;
+    std::string err;
+    if (!bam_bind_file(&b->bam, "bam_bin_counts", file_path, region, idx, err) || !bam_region_prepare(&b->bam, b->index_bytes, b->seg_beg, b->seg_end, b->seg_count, err)) { set_error(info, err.c_str()); delete b; return; }
+    // the table's size is known from the header: the limit is a bind error in dhts_bam_bins_open's own words (the table itself is not made here)
+    if (dhts_bam_bins_open(b->bam.ctx, &b->P) != 0) { err = dhts_error(b->bam.ctx); set_error(info, err.c_str()); delete b; return; }
+    add_columns(info, kBinsCols, kBinsTypes, DHTS_BINS_COL_COUNT);
+    API(void, duckdb_bind_set_bind_data, duckdb_bind_info, void *, duckdb_delete_callback_t)(info, b, destroy_bins_bind);
+}
+static void bam_bin_counts_init(duckdb_init_info info) {
+    BinsBind *bind = (BinsBind *)API(void *, duckdb_init_get_bind_data, duckdb_init_info)(info);
+    auto init_error = API(void, duckdb_init_set_error, duckdb_init_info, const char *);
+    BinsScanState *g = new BinsScanState();
+    g->bind = bind;
+    std::string msg;
+    g->ctx = create_ctx("bam_bin_counts", msg);
+    if (!g->ctx) { init_error(info, msg.c_str()); delete g; return; }
+    dhts_ctx *c = g->ctx;
+    const std::string &path = bind->bam.path;
+    int rc = bind->seg_count >= 0 ? dhts_open_path_segments(c, path.c_str(), bind->bam.header_bytes, bind->seg_beg.data(), bind->seg_end.data(), bind->seg_count) : dhts_open_path(c, path.c_str());
+    if (rc == 0 && (dhts_bgzf_index(c) <= 0 || dhts_bam_open(c) != 0)) rc = -1;
+    if (rc != 0) { msg = std::string("Failed to open SAM/BAM/CRAM file: ") + path; init_error(info, msg.c_str()); delete g; return; }   // (as read_bam's producer)
+    if (!bind->bam.region.empty()) {
+        rc = dhts_bam_set_regions(c, bind->bam.region.c_str());
+        if (rc == 0 && !bind->index_bytes.empty()) rc = dhts_bam_load_index(c, bind->index_bytes.data(), bind->index_bytes.size());
+    }
+    if (rc == 0) rc = dhts_bam_bins_open(c, &bind->P);
+    static const int64_t env_mb = getenv("DHTS_BATCH_BLOCKS") ? atoll(getenv("DHTS_BATCH_BLOCKS")) : 0;
+    if (rc == 0 && dhts_bam_bins_scan(c, env_mb > 0 ? env_mb : 0) < 0) {
+        // a stream that ends on an error ends the scan silently, its rows counted (bam_reader.c:754-766); a call that failed is the error
+        dhts_bins_stats st;
+        if (dhts_bam_bins_stats(c, &st) != 0 || st.status == 0) rc = -1;
+    }
+    if (rc != 0) { msg = dhts_error(c); init_error(info, msg.c_str()); delete g; return; }
+    map_projection(info, DHTS_BINS_COL_COUNT, g->pj);
+    for (size_t ci = 0; ci < g->pj.slot.size(); ci++) {                     // all seven columns are read back: a slot is the column's own id
+        const idx_t id = g->pj.column_ids[ci];
+        if (g->pj.slot[ci] >= 0) { g->pj.slot[ci] = (int)id; if (id == DHTS_BINS_CHROM) g->want_chrom = true; }
+        g->cb.kind.push_back(g->pj.slot[ci] < 0 ? COL_NULL : id == DHTS_BINS_CHROM ? COL_STRING : COL_FIXED8_NOT_NULL);
+    }
+    g->cb.host.resize(DHTS_BINS_COL_COUNT);
+    API(void, duckdb_init_set_max_threads, duckdb_init_info, idx_t)(info, 1);
+    API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, g, destroy_bins_scan);
+}
+// the next rows of the table, read back; false at the end (or on a failure: err set)
+static bool bins_next(BinsScanState *g, std::string &err) {
+    ColBatch &cb = g->cb;
+    while (cb.status == 0) {
+        dhts_bins_batch b;
+        if (dhts_bam_bins_next(g->ctx, 0, &b) != 0) { err = dhts_error(g->ctx); return false; }
+        cb.status = b.status;
+        if (b.n_rows == 0) continue;
+        if (!g->arena.reserve(dhts_bam_bins_batch_host_bytes(&b))) { err = "bam_bin_counts: out of pinned host memory"; return false; }
+        if (dhts_bam_bins_batch_fetch(g->ctx, &b, g->arena.p, g->arena.cap, cb.host.data()) != 0) { err = dhts_error(g->ctx); return false; }
+        if (g->want_chrom) {
+            const dhts_bam_header &h = g->bind->bam.hdr;
+            dhts_col &hc = cb.host[DHTS_BINS_CHROM]; const int64_t *tid = (const int64_t *)hc.fixed;
+            g->chrom_off.assign((size_t)b.n_rows + 1, 0); g->chrom_bytes.clear();
+            for (int64_t r = 0; r < b.n_rows; r++) { if (tid[r] >= 0 && tid[r] < h.n_ref) g->chrom_bytes += h.ref_name[tid[r]]; g->chrom_off[(size_t)r + 1] = (uint32_t)g->chrom_bytes.size(); }
+            hc.off = g->chrom_off.data(); hc.bytes = (const uint8_t *)g->chrom_bytes.data(); hc.nbytes = g->chrom_bytes.size();
+        }
+        cb.n = b.n_rows; cb.pos = 0;
+        return true;
+    }
+    return false;
+}
+static void bam_bin_counts_function(duckdb_function_info info, duckdb_data_chunk output) {
+    BinsScanState *g = (BinsScanState *)API(void *, duckdb_function_get_init_data, duckdb_function_info)(info);
+    if (!g) { API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t)(output, 0); return; }
+    scan_chunks(info, output, g->pj, g->cb, nullptr, [&](std::string &err) { return bins_next(g, err); });
+}
+extern "C" __attribute__((visibility("default"))) void register_bam_bin_counts_function(duckdb_connection connection) {
+    register_table_function(connection, "bam_bin_counts", {{"bin_width", DUCKDB_TYPE_BIGINT}, {"min_mapq", DUCKDB_TYPE_BIGINT}, {"include_flags", DUCKDB_TYPE_BIGINT}, {"require_flags", DUCKDB_TYPE_BIGINT},
+                            {"exclude_flags", DUCKDB_TYPE_BIGINT}, {"dedup", DUCKDB_TYPE_VARCHAR}, {"region", DUCKDB_TYPE_VARCHAR}, {"index_path", DUCKDB_TYPE_VARCHAR}, {"emit_zero_bins", DUCKDB_TYPE_BOOLEAN}},
+                            bam_bin_counts_bind, bam_bin_counts_init, nullptr, bam_bin_counts_function, true);
+}

@@ -492,6 +492,69 @@ int dhts_nuc_intervals(dhts_ctx *fasta, const int32_t *tid, const int64_t *start
 uint64_t dhts_nuc_batch_host_bytes(const dhts_nuc_batch *b);
 int dhts_nuc_batch_fetch(dhts_ctx *fasta, const dhts_nuc_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- bam_bin_counts --------------------------------------------------------------------------
+ * Read-start counts in fixed-width bins with a strand split, accumulated on the device from the fixed-width columns a read_bam batch
+ * leaves in HBM: no row crosses PCIe.  The reference has only a plan for it (.github/PLAN.md, Phase 10, 10.7.2; its SQL equivalent is
+ * read_bam + flag functions + GROUP BY), so this is the specification.
+ *   Input: the rows of the context's read_bam scan in file order, i.e. what dhts_bam_open reads after the device region filter.  Per row:
+ *     flag, tid, pos0 = POS - 1, mapq, pnext.
+ *   Each row falls out at exactly one step, and every step has a 64-bit counter:
+ *     1. flags -> n_flag_filtered: the row passes iff (flag & require_flags) == require_flags, (flag & exclude_flags) == 0 and
+ *        (include_flags == 0 || (flag & include_flags) != 0)            (samtools -f / -F / --rf)
+ *     2. placement: tid < 0 or pos0 < 0 -> n_unplaced; pos0 >= ref_len[tid] -> n_out_of_range.  Such rows never touch the table.
+ *     3. duplicate, only with dedup = adjacent -> n_duplicate: let p be the previous row, in file order and across batches, that passed
+ *        steps 1 and 2.  The row is a duplicate iff p exists, p.tid == tid, p.pos0 == pos0 and ((flag & 1) == 0 or p.pnext == pnext).
+ *        Rows that failed step 1 or 2 are invisible to the rule; rows that fall out at step 3 or 4 still become p for the next row.
+ *        This is the adjacent-start rule of the plan, "WisecondorX-like"; it is not FLAG & 0x400 and not exact compatibility.
+ *     4. MAPQ -> n_low_mapq: mapq < min_mapq (after the duplicate step, as in the plan)
+ *     5. counted -> n_counted: bin b = pos0 / bin_width of contig tid, reverse iff flag & 0x10, forward otherwise.
+ *     n_rows = the sum of the six counters.
+ *   Result rows: contigs in header order, bins ascending; a bin is a row where count_total > 0, or everywhere with emit_zero_bins
+ *     (with regions: every bin of every contig a region names).  chrom (here: the contig's id), start = b * bin_width,
+ *     end = min(start + bin_width, ref_len) -- the clipping of fasta_nuc's bins, so the two join on (chrom, start, end) -- bin_id = b,
+ *     count_total = count_fwd + count_rev, count_fwd, count_rev.  A contig of length 0 has no bins; a header without references gives no rows.
+ *   Limits: more than 2^28 bins in total is an error that states the bin count.  A batch with status < 0 has its rows counted and the
+ *     result carries that status.  A shard or a block range other than the whole file is refused: the duplicate rule does not cross shards.
+ *   Left out of the plan's signature: strand_mode (both strands are always counted) and reference (CRAM is not read; GC columns are a
+ *     join with fasta_nuc).
+ * Every call on a context in the wrong state fails with a dhts_error that names what is missing.  The kernels are timed as DHTS_K_BCF_CHECK. */
+enum { DHTS_BINS_DEDUP_NONE = 0, DHTS_BINS_DEDUP_ADJACENT = 1 };
+enum { DHTS_BINS_CHROM = 0, DHTS_BINS_START, DHTS_BINS_END, DHTS_BINS_BIN_ID, DHTS_BINS_COUNT_TOTAL, DHTS_BINS_COUNT_FWD, DHTS_BINS_COUNT_REV, DHTS_BINS_COL_COUNT };
+typedef struct {
+    int64_t bin_width;       /* > 0 (the table function's default: 5000)                                      */
+    int32_t min_mapq;        /* 0..255                                                                        */
+    int32_t require_flags, exclude_flags, include_flags;   /* 0..65535                                        */
+    int32_t dedup;           /* DHTS_BINS_DEDUP_*                                                             */
+    int32_t emit_zero_bins;
+} dhts_bins_params;
+typedef struct {
+    uint64_t n_rows, n_flag_filtered, n_unplaced, n_out_of_range, n_duplicate, n_low_mapq, n_counted;
+    uint64_t total_bins;     /* bins of the table: the sum of ceil(ref_len / bin_width)                        */
+    int32_t status;          /* the status of the last batch that had one: 0 = the scan has not ended, 1 = clean end, < 0 = the stream
+                                ended on an error after the counted rows                                       */
+    int32_t reserved;
+} dhts_bins_stats;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows follow, 1 = the last batch                                                                   */
+    int32_t n_cols;          /* DHTS_BINS_COL_COUNT, in that order                                                                         */
+    const dhts_col *cols;    /* host array of descriptors, DEVICE pointers inside: valid[n_rows] (all 1), fixed = 8-byte integers           */
+} dhts_bins_batch;
+/* after dhts_bam_open and the optional dhts_bam_set_regions / dhts_bam_load_index: the table and the counters, zeroed */
+int dhts_bam_bins_open(dhts_ctx *, const dhts_bins_params *params);
+/* any batch of this context's scan (a caller may feed the batches it scans itself; FLAG, tid, POS, MAPQ and PNEXT are always there) */
+int dhts_bam_bins_accumulate(dhts_ctx *, const dhts_bam_batch *batch);
+/* dhts_bam_next_batch (<= max_blocks blocks each, no string column) + accumulate to the end of the stream.  Returns the status the stream
+ * ended on: 1, or its negative status (the rows are counted; dhts_bins_stats.status repeats it); a call that failed returns < 0 with
+ * dhts_error set and leaves dhts_bins_stats.status 0. */
+int dhts_bam_bins_scan(dhts_ctx *, int64_t max_blocks);
+int dhts_bam_bins_stats(dhts_ctx *, dhts_bins_stats *out);
+/* the next <= max_rows result rows (0 = default); an accumulate call starts the result over */
+int dhts_bam_bins_next(dhts_ctx *, int64_t max_rows, dhts_bins_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst */
+uint64_t dhts_bam_bins_batch_host_bytes(const dhts_bins_batch *b);
+int dhts_bam_bins_batch_fetch(dhts_ctx *, const dhts_bins_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
 /* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
  * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and
  * uncompressed text are read.  Bind is dhts_tabix_set_conf + dhts_tabix_sniff + dhts_tabix_resolve_schema + dhts_tabix_set_schema;

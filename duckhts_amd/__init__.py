@@ -86,6 +86,16 @@ class BinsStats(C.Structure):
                 ("n_low_mapq", C.c_uint64), ("n_counted", C.c_uint64), ("total_bins", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BedcovParams(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("require_flags", C.c_int32), ("exclude_flags", C.c_int32), ("include_flags", C.c_int32),
+                ("count_deletions", C.c_int32), ("count_ref_skips", C.c_int32)]
+
+
+class BedcovStats(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_flag_filtered", C.c_uint64), ("n_unplaced", C.c_uint64), ("n_low_mapq", C.c_uint64), ("n_counted", C.c_uint64),
+                ("n_bed_rows", C.c_uint64), ("n_breakpoints", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TabixMap(C.Structure):
     _fields_ = [("pair_off", C.c_void_p), ("valid", C.c_void_p), ("n_pairs", C.c_uint64), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p), ("key_nbytes", C.c_uint64),
                 ("val_off", C.c_void_p), ("val_bytes", C.c_void_p), ("val_nbytes", C.c_uint64)]
@@ -140,6 +150,9 @@ NUC_DOUBLE_COLUMNS = (3, 4)
 NUC_STR_COLUMNS = (0, 12)
 BINS_COLUMNS = ["chrom", "start", "end", "bin_id", "count_total", "count_fwd", "count_rev"]
 BINS_DEDUP = {"none": 0, "adjacent": 1}
+BEDCOV_COLUMNS = ["chrom", "start", "end", "name", "score", "strand", "bases_covered", "read_count"]
+BEDCOV_INT_COLUMNS = (1, 2, 6, 7)
+BEDCOV_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4)                # FLAG, RNAME, POS, MAPQ: no string column (the CIGARs are read in their binary form)
 BINS_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 7)        # FLAG, RNAME, POS, MAPQ, PNEXT: no string column
 
 # DUCKDB_TYPE_* element codes -> the canonical type tags of the test oracle's column blob
@@ -158,6 +171,7 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_bed_open", "dhts_bed_set_projection", "dhts_bed_set_region", "dhts_bed_load_index", "dhts_bed_region_segments", "dhts_bed_next_batch", "dhts_bed_batch_host_bytes", "dhts_bed_batch_fetch",
            "dhts_nuc_open_region", "dhts_nuc_open", "dhts_nuc_set_region", "dhts_nuc_set_projection", "dhts_nuc_next_bins", "dhts_nuc_next_bed", "dhts_nuc_intervals", "dhts_nuc_batch_host_bytes", "dhts_nuc_batch_fetch",
            "dhts_bam_bins_open", "dhts_bam_bins_accumulate", "dhts_bam_bins_scan", "dhts_bam_bins_stats", "dhts_bam_bins_next", "dhts_bam_bins_batch_host_bytes", "dhts_bam_bins_batch_fetch",
+           "dhts_bam_bedcov_open", "dhts_bam_bedcov_accumulate", "dhts_bam_bedcov_scan", "dhts_bam_bedcov_stats", "dhts_bam_bedcov_next", "dhts_bam_bedcov_batch_host_bytes", "dhts_bam_bedcov_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
            "dhts_udf_upload", "dhts_udf_apply", "dhts_udf_result_host_bytes", "dhts_udf_fetch", "dhts_udf_seq_kmers", "dhts_udf_kmers_host_bytes", "dhts_udf_kmers_fetch"]
@@ -260,6 +274,16 @@ def lib():
         L.dhts_bam_bins_batch_host_bytes.restype = C.c_uint64
         L.dhts_bam_bins_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_bam_bins_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_bam_bedcov_open.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BedcovParams)]
+        L.dhts_bam_bedcov_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
+        L.dhts_bam_bedcov_scan.argtypes = [C.c_void_p, C.c_int64]
+        L.dhts_bam_bedcov_stats.argtypes = [C.c_void_p, C.POINTER(BedcovStats)]
+        L.dhts_bam_bedcov_next.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
+        L.dhts_bam_bedcov_batch_host_bytes.restype = C.c_uint64
+        L.dhts_bam_bedcov_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
+        L.dhts_bam_bedcov_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_debug_bedcov_max_rows.restype = None
+        L.dhts_debug_bedcov_max_rows.argtypes = [C.c_uint64]
         L.dhts_tabix_open.argtypes = [C.c_void_p, C.c_int]
         L.dhts_tabix_set_conf.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dhts_tabix_index_conf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -734,6 +758,60 @@ class Context:
         out = {"n_rows": n}
         for i in range(b.n_cols):
             out[BINS_COLUMNS[host[i].col]] = np.ctypeslib.as_array(C.cast(host[i].fixed, C.POINTER(C.c_int64)), (n,)).copy() if n else np.zeros(0, np.int64)
+        return out, int(b.status)
+
+    # ---- bam_bedcov (the batch has dhts_bed_batch's layout) ----
+    def bam_bedcov_open(self, bed_ctx, min_mapq=0, require_flags=0, exclude_flags=0, include_flags=0, count_deletions=True, count_ref_skips=True):
+        """after bam_open and the optional set_regions / load_index; bed_ctx: a second Context on this device after bed_open.  One pass over
+        the BED, the breakpoints to the device, the counters zeroed.  The masks are taken as given (the C ABI's rule)."""
+        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
+        p = BedcovParams(clip(min_mapq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31), int(count_deletions), int(count_ref_skips))
+        self._chk(self.L.dhts_bam_bedcov_open(self.h, bed_ctx.h if bed_ctx is not None else None, C.byref(p)))
+
+    def bam_bedcov_accumulate(self, b):
+        """b: the batch next_batch returned last on this context"""
+        self._chk(self.L.dhts_bam_bedcov_accumulate(self.h, C.byref(b)))
+
+    def bam_bedcov_scan(self, max_blocks=0):
+        """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
+        rc = self.L.dhts_bam_bedcov_scan(self.h, max_blocks)
+        if rc < 0:
+            msg = self.L.dhts_error(self.h).decode()
+            if self.bam_bedcov_stats()["status"] == 0:                    # a call failed (a stream that ended on an error has set its status)
+                raise DhtsError(msg)
+        return rc
+
+    def bam_bedcov_stats(self):
+        st = BedcovStats()
+        self._chk(self.L.dhts_bam_bedcov_stats(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in BedcovStats._fields_ if k != "reserved"}
+
+    def bam_bedcov_next(self, bed_ctx, max_blocks=0):
+        """the result for the next batch of the BED: ({"n_rows", chrom / name / score / strand: lists of bytes or None, start / end: lists of
+        int or None, bases_covered / read_count: int64 arrays}, status)"""
+        b = BedBatch()
+        self._chk(self.L.dhts_bam_bedcov_next(self.h, bed_ctx.h if bed_ctx is not None else None, max_blocks, C.byref(b)))
+        n = int(b.n_rows)
+        need = int(self.L.dhts_bam_bedcov_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        self._chk(self.L.dhts_bam_bedcov_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
+        base = arena.ctypes.data
+        out = {"n_rows": n}
+        for i in range(b.n_cols):
+            hc = host[i]
+            name = BEDCOV_COLUMNS[hc.col]
+            if n == 0:
+                out[name] = np.zeros(0, np.int64) if hc.col >= 6 else []
+                continue
+            valid = arena[hc.valid - base: hc.valid - base + n]
+            if hc.col in BEDCOV_INT_COLUMNS:
+                vals = arena[hc.fixed - base: hc.fixed - base + 8 * n].view(np.int64)
+                out[name] = vals.copy() if hc.col >= 6 else [int(v) if ok else None for v, ok in zip(vals, valid)]
+            else:
+                off = arena[hc.off - base: hc.off - base + 4 * (n + 1)].view(np.uint32)
+                data = arena[hc.bytes - base: hc.bytes - base + int(hc.nbytes)].tobytes()
+                out[name] = [data[int(off[r]):int(off[r + 1])] if valid[r] else None for r in range(n)]
         return out, int(b.status)
 
     # ---- seq_* / cigar_* / SAM flag functions on device columns (dhts_udf_*) ----
@@ -1770,6 +1848,50 @@ def bam_bin_counts(src, bin_width=5000, min_mapq=0, include_flags=0, require_fla
         out["status"] = status
         return out
     finally:
+        ctx.close()
+
+
+def bam_bedcov(src, bed, min_mapq=0, require_flags=0, exclude_flags=0x704, include_flags=0, count_deletions=True, count_ref_skips=True, region=None, index=None,
+               max_blocks=0, device=0, bed_max_blocks=0):
+    """bam_bedcov(path, bed_path :=, min_mapq :=, require_flags :=, exclude_flags :=, include_flags :=, count_deletions :=, count_ref_skips :=,
+    region :=, index_path :=): for every row of the BED (a path or the file's bytes) the summed per-base depth and the number of overlapping
+    reads, accumulated on the device (the contract: include/duckhts_amd.h).  {"n_rows", "chrom", "name", "score", "strand": lists of bytes or
+    None, "start", "end": lists of int or None, "bases_covered", "read_count": int64 arrays, "stats": the step counters, the BED's rows and
+    the breakpoints, "status": how the BAM stream ended}.  index: BAI / CSI bytes narrowing the scan of a region query; max_blocks: BAM blocks
+    per batch, bed_max_blocks: BED blocks per result batch."""
+    ctx, bctx = Context(device), None
+    try:
+        ctx.open(src)
+        ctx.bgzf_index()
+        ctx.bam_open()
+        if region is not None:
+            if not ctx.set_regions(region):
+                raise DhtsError(f"No reads found for region(s): {region}")
+            if index is not None:
+                ctx.load_index(index)
+        bctx = Context(device)
+        bctx.open(bed)
+        bctx.L.dhts_bgzf_index(bctx.h)
+        bctx._chk(bctx.L.dhts_bed_open(bctx.h))
+        ctx.bam_bedcov_open(bctx, min_mapq, require_flags, exclude_flags, include_flags, count_deletions, count_ref_skips)
+        status = ctx.bam_bedcov_scan(max_blocks)
+        parts = []
+        while True:
+            cols, st = ctx.bam_bedcov_next(bctx, bed_max_blocks)
+            parts.append(cols)
+            if st != 0:
+                break
+        out = {}
+        for k in BEDCOV_COLUMNS:
+            vals = [p[k] for p in parts if k in p]
+            out[k] = np.concatenate(vals) if k in ("bases_covered", "read_count") else [x for v in vals for x in v]
+        out["n_rows"] = sum(p["n_rows"] for p in parts)
+        out["stats"] = {k: v for k, v in ctx.bam_bedcov_stats().items() if k.startswith("n_")}
+        out["status"] = status
+        return out
+    finally:
+        if bctx is not None:
+            bctx.close()
         ctx.close()
 
 

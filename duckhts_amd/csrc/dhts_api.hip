@@ -17,6 +17,7 @@
 #include "fasta_nuc.hip"
 #include "seq_udf.hip"
 #include "bam_bins.hip"
+#include "bam_bedcov.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -207,6 +208,14 @@ struct BinsState {
     uint64_t win_b0 = 0, win_rows = 0, win_done = 0; uint32_t win_n = 0; std::vector<dhts_col> out;
     DevBuf counts, steps, carry, bin_base, ref_len, zero_ok, step, word, vis, rank, src, keep, krank, ones, cols[DHTS_BINS_COL_COUNT];
 };
+// bam_bedcov (bam_bedcov.hip, dhts_bam_bedcov.inc): the parameters, the breakpoints (X, with base[t] in front of every contig) and the indices
+// ks / ke of every BED row's start and end among them, the counters (four 64-bit words per breakpoint index) and their prefix sums, the step
+// counters, per-batch scratch, and the position of the second pass over the BED context
+struct BedcovState {
+    bool open = false, sums_ready = false, started = false; dhts_bedcov_params P; int32_t n_ref = 0, status = 0;
+    uint64_t n_points = 0, n_bed = 0, row_next = 0; std::vector<dhts_col> out;
+    DevBuf cnt, sums, partial, steps, base, X, ks, ke, step, rlen, nseg, bases, reads, ones;
+};
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
 struct UdfState {
@@ -251,6 +260,7 @@ struct dhts_ctx {
     BedState bed;
     NucState nuc;
     BinsState bins;
+    BedcovState cov;
     UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
@@ -342,6 +352,8 @@ struct dhts_ctx {
     int shard_rank = 0, shard_world = 1;
     bool range_cut = false;               // dhts_bam_set_shard / _set_block_range / _set_file_shard left less than the whole file (the windows of a region query are no such cut)
     int64_t next_block = 0; bool stream_done = false; bool first_batch = true;
+    uint64_t last_batch_first = 0;        // (and the stream offset of its first record)
+    int64_t last_batch_rows = -1;         // rows of the batch dhts_bam_next_batch returned last: its stream, record offsets and CIGAR locations are still in HBM (bam_bedcov)
     int64_t halo_limit = 0;
     // timing
     bool timing = false;
@@ -480,8 +492,8 @@ static void stop_stager(dhts_ctx *c) {
 }
 static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
-    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->bins.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
-    c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->range_cut = false; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
+    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->bins.open = false; c->cov.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
+    c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->range_cut = false; c->last_batch_rows = -1; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     memset(c->tile_stats, 0, sizeof(c->tile_stats));
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
@@ -537,6 +549,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_tabix_scan.inc"
 #include "dhts_fasta_nuc.inc"
 #include "dhts_bam_bins.inc"
+#include "dhts_bam_bedcov.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

@@ -386,7 +386,9 @@ static int fastq_record_start(dhts_ctx *c, int64_t i, uint64_t &off);
 int dhts_bam_next_batch(dhts_ctx *c, int64_t max_blocks, uint32_t colmask, dhts_bam_batch *out) {
     if (!c || !out) return -1;
     for (;;) {
+        c->last_batch_rows = -1;
         if (bam_next_batch_one(c, max_blocks, colmask, out)) return -1;
+        c->last_batch_rows = out->n_rows; c->last_batch_first = out->first_rec_uoff;
         // a region query with several index windows: the end of one window is the start of the next, not the end of the scan
         if (out->status == 1 && c->win_cur + 1 < c->wins.size()) {
             enter_window(c, c->win_cur + 1);

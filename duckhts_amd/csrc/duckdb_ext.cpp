@@ -1,7 +1,7 @@
 // duckdb_ext.cpp -- DuckDB C-API extension surface (outer drop-in boundary) over the MI355X scan path.
 //
 // The table functions live in the parts included below, one per reader family, over the shared helpers of duckdb_surface.h:
-//   duckdb_bam.inc read_bam, duckdb_bins.inc bam_bin_counts, duckdb_bcf.inc read_bcf, duckdb_seq.inc read_fastq / read_fasta, duckdb_interval.inc read_bed / fasta_nuc,
+//   duckdb_bam.inc read_bam, duckdb_bins.inc bam_bin_counts, duckdb_bedcov.inc bam_bedcov, duckdb_bcf.inc read_bcf, duckdb_seq.inc read_fastq / read_fasta, duckdb_interval.inc read_bed / fasta_nuc,
 //   duckdb_tabix.inc read_tabix / read_gtf / read_gff, duckdb_udf.inc the k-mer family; duckdb_tools.cpp (its own translation unit) the writers.
 // The htslib calls underneath are replaced by include/duckhts_amd.h (HIP kernels); DuckDB is reached only
 // through the function-pointer table returned by access->get_api(info, "v1.2.0").
@@ -37,6 +37,7 @@ static double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); r
 #include "duckdb_bcf.inc"
 #include "duckdb_seq.inc"
 #include "duckdb_interval.inc"
+#include "duckdb_bedcov.inc"
 #include "duckdb_tabix.inc"
 #include "duckdb_udf.inc"
 
@@ -67,7 +68,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     // read_tabix, read_gtf, read_gff close the list (src/duckhts.c:67-69), opt-in: DHTS_TABIX_FUNCTIONS=1
     if (const char *e = getenv("DHTS_TABIX_FUNCTIONS")) if (atoi(e) == 1) { register_read_tabix_function(conn); register_read_gtf_function(conn); register_read_gff_function(conn); }
     // bam_bin_counts is not in src/duckhts.c (the reference plans it: .github/PLAN.md, Phase 10): last, behind a variable of its own, DHTS_COVERAGE_FUNCTIONS=1
-    if (const char *e = getenv("DHTS_COVERAGE_FUNCTIONS")) if (atoi(e) == 1) register_bam_bin_counts_function(conn);
+    // bam_bedcov (PLAN.md 10.7.3) comes behind it under the same variable at the value 2: the set a host gets with 1 stays what it was
+    if (const char *e = getenv("DHTS_COVERAGE_FUNCTIONS")) { const int v = atoi(e); if (v == 1 || v == 2) register_bam_bin_counts_function(conn); if (v == 2) register_bam_bedcov_function(conn); }
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);
     return true;
 }

@@ -555,6 +555,83 @@ int dhts_bam_bins_next(dhts_ctx *, int64_t max_rows, dhts_bins_batch *out);
 uint64_t dhts_bam_bins_batch_host_bytes(const dhts_bins_batch *b);
 int dhts_bam_bins_batch_fetch(dhts_ctx *, const dhts_bins_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- bam_bedcov ------------------------------------------------------------------------------
+ * For every interval of a BED file the summed per-base depth and the number of reads that overlap it (what `samtools bedcov [-c] [-j]`
+ * prints), accumulated on the device from the fixed-width columns and the binary CIGARs a read_bam batch leaves in HBM: no row crosses
+ * PCIe.  The reference has only a plan for it (.github/PLAN.md, Phase 10, 10.6.1 / 10.7.3; its SQL equivalent is a range join of read_bam
+ * with read_bed plus CIGAR arithmetic per pair), so this is the specification.
+ *   Input: the rows of the context's read_bam scan in file order, i.e. what dhts_bam_open reads after the device region filter, and the rows
+ *     of a BED file as read_bed returns them (its line rules; a line with fewer than three fields is its error).  BED row i is
+ *     (chrom_i, s_i, e_i), 0-based half-open; chrom_i is resolved against the BAM header (the first @SQ of a name listed twice).
+ *   Each read falls out at exactly one step, and every step has a 64-bit counter:
+ *     1. flags -> n_flag_filtered: the three-mask rule of bam_bin_counts
+ *     2. placement -> n_unplaced: tid < 0, tid >= n_ref or pos0 < 0.  Positions are not compared with ref_len.
+ *     3. MAPQ -> n_low_mapq: mapq < min_mapq
+ *     4. counted -> n_counted
+ *     n_rows = the sum of the four counters.
+ *   A counted read has
+ *     the read interval [pos0, pos0 + max(1, rlen)): rlen = the reference length of the effective CIGAR (the CG tag's when the record has
+ *       one), 0 when FLAG & 4 is set -- bam_endpos, as the region filter computes it;
+ *     depth segments: the maximal runs of reference positions its CIGAR covers by M, = and X, by D when count_deletions is on and by N
+ *       when count_ref_skips is on.  A read with FLAG & 4, or without such an operation, has none; with both options on there is at most
+ *       one, [pos0, pos0 + rlen).
+ *   Result: one row per BED row, in BED file order.  chrom, start, end, name, score, strand are read_bed's columns with its types and NULLs;
+ *     bases_covered BIGINT = the sum over the segments [a, b) on the row's contig of max(0, min(b, e) - max(a, s));
+ *     read_count BIGINT = the counted reads on that contig with pos0 < e and read_end > s.
+ *     Both are 0, not NULL, for a row with e <= s, a NULL start or end, or a chrom the header lacks.  Overlapping, nested and repeated
+ *     rows are each answered independently.
+ *   Parameters: min_mapq 0..255; require_flags, exclude_flags, include_flags 0..65535; count_deletions, count_ref_skips 0 or 1.  This ABI
+ *     takes the masks as given; the table function and the Python function default exclude_flags to 0x704 (UNMAP, SECONDARY, QCFAIL, DUP:
+ *     samtools' default) and both options to on.
+ *   Limits: more than 2^27 BED rows is an error that states the count.  A batch with status < 0 has its rows counted and the result carries
+ *     that status.  A shard or a block range other than the whole file is refused.
+ *   Not in this contract: depth thresholds (-d), several BAM files, reference / CRAM, a region on the BED side.  A region and an index on
+ *     the BAM side work as in bam_bin_counts: they restrict which reads are scanned, and nothing else.
+ *   Method: the counters are O(breakpoints) -- the distinct starts and ends of the BED rows per contig -- not O(genome); a segment costs a
+ *     constant number of atomics, and the result is a 64-bit prefix sum over the breakpoints (csrc/bam_bedcov.hip).
+ * Every call on a context in the wrong state fails with a dhts_error that names what is missing.  The kernels are timed as DHTS_K_BCF_CHECK. */
+enum { DHTS_BEDCOV_CHROM = 0, DHTS_BEDCOV_START, DHTS_BEDCOV_END, DHTS_BEDCOV_NAME, DHTS_BEDCOV_SCORE, DHTS_BEDCOV_STRAND, DHTS_BEDCOV_BASES_COVERED,
+       DHTS_BEDCOV_READ_COUNT, DHTS_BEDCOV_COL_COUNT };
+typedef struct {
+    int32_t min_mapq;        /* 0..255                                                                        */
+    int32_t require_flags, exclude_flags, include_flags;   /* 0..65535                                        */
+    int32_t count_deletions, count_ref_skips;              /* 0 or 1                                          */
+} dhts_bedcov_params;
+typedef struct {
+    uint64_t n_rows, n_flag_filtered, n_unplaced, n_low_mapq, n_counted;
+    uint64_t n_bed_rows;     /* rows of the BED file                                                           */
+    uint64_t n_breakpoints;  /* distinct (contig, position) pairs among the starts and ends of its valid rows   */
+    int32_t status;          /* the status of the last batch that had one: 0 = the scan has not ended, 1 = clean end, < 0 = the stream
+                                ended on an error after the counted rows                                       */
+    int32_t reserved;
+} dhts_bedcov_stats;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows follow, 1 = the last batch                                                                   */
+    int32_t n_cols;          /* DHTS_BEDCOV_COL_COUNT, in that order                                                                       */
+    const dhts_col *cols;    /* host array of descriptors, DEVICE pointers inside: valid[n_rows]; BIGINT (start, end, bases_covered,
+                                read_count) in fixed (8 bytes, 0 where NULL), VARCHAR in off[n_rows + 1] / bytes                           */
+} dhts_bedcov_batch;
+/* after dhts_bam_open on `bam` (and the optional dhts_bam_set_regions / dhts_bam_load_index).  `bed` is a second context on the same device,
+ * prepared as for read_bed (dhts_bed_open).  One pass over it collects contig, start and end of every row; the breakpoints go to the device
+ * and the counters are zeroed.  A second open starts a new count.  The projection of `bed` belongs to bam_bedcov from here on. */
+int dhts_bam_bedcov_open(dhts_ctx *bam, dhts_ctx *bed, const dhts_bedcov_params *params);
+/* the batch dhts_bam_next_batch returned LAST on this context: the binary CIGARs are read where the scan left them (the inflated stream and the
+ * record offsets of a batch stay in HBM until the next one is made), so the scan needs no string column.  Starts a result over. */
+int dhts_bam_bedcov_accumulate(dhts_ctx *bam, const dhts_bam_batch *batch);
+/* dhts_bam_next_batch (<= max_blocks blocks each, no string column) + accumulate to the end of the stream.  Returns the status the stream
+ * ended on: 1, or its negative status (the rows are counted; dhts_bedcov_stats.status repeats it); a call that failed returns < 0 with
+ * dhts_error set and leaves dhts_bedcov_stats.status 0. */
+int dhts_bam_bedcov_scan(dhts_ctx *bam, int64_t max_blocks);
+int dhts_bam_bedcov_stats(dhts_ctx *bam, dhts_bedcov_stats *out);
+/* the result for the rows of the next batch of `bed` (<= max_blocks blocks of it, 0 = default): a second pass over the BED context, whose six
+ * passthrough columns are followed by the two result columns for the same rows.  The first call after open or accumulate rewinds `bed` and
+ * takes the prefix sums. */
+int dhts_bam_bedcov_next(dhts_ctx *bam, dhts_ctx *bed, int64_t max_blocks, dhts_bedcov_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst */
+uint64_t dhts_bam_bedcov_batch_host_bytes(const dhts_bedcov_batch *b);
+int dhts_bam_bedcov_batch_fetch(dhts_ctx *bam, const dhts_bedcov_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
 /* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
  * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and
  * uncompressed text are read.  Bind is dhts_tabix_set_conf + dhts_tabix_sniff + dhts_tabix_resolve_schema + dhts_tabix_set_schema;

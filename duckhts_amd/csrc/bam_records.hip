@@ -33,22 +33,25 @@ __device__ __forceinline__ uint32_t ldu32(const uint8_t *p) { uint32_t v; __buil
 // bam_cigar_type (htslib/sam.h:139-148): bit0 = consumes query
 #define CIG_QUERY(op) ((0x3C1A7u >> ((op) << 1)) & 1u)
 
+// bytes of a fixed-size auxiliary value by type byte (htslib sam.c aux_type2size): A c C -> 1, s S -> 2, i I f -> 4, d -> 8, everything
+// else 0.  One bit-field extract instead of a switch (which compiled to a compare tree with an exec-mask group per case): a 3-bit code per
+// letter (size = (1 << code) >> 1) indexed by t & 31, one 64-bit word per letter case; bytes outside 64..127 have no size.
 __device__ __forceinline__ int aux_size(uint8_t t) {
-    switch (t) {
-    case 'A': case 'c': case 'C': return 1;
-    case 's': case 'S': return 2;
-    case 'i': case 'I': case 'f': return 4;
-    case 'd': return 8;
-    default: return 0;
-    }
+    const uint64_t UP = (1ull << (3 * 1)) | (1ull << (3 * 3)) | (3ull << (3 * 9)) | (2ull << (3 * 19));                              // A C I S
+    const uint64_t LO = (1ull << (3 * 3)) | (4ull << (3 * 4)) | (3ull << (3 * 6)) | (3ull << (3 * 9)) | (2ull << (3 * 19));          // c d f i s
+    uint32_t sh = (t & 31u) * 3u; sh = sh < 61u ? sh : 61u;                          // letters 20..31 of a case: bits 60..63 are clear
+    const uint32_t code = (uint32_t)(((t & 0x20u) ? LO : UP) >> sh) & 7u;
+    return (t & 0xc0u) == 0x40u ? (int)((1u << code) >> 1) : 0;
 }
-struct RecInfo {
+// O: the type offsets are computed in (bam_tiles_lds.hip: 64-bit offsets in the batch buffer, or 32-bit offsets relative to a staged tile)
+template <class O> struct RecInfoT {
     uint32_t block_len, l_qname, n_cigar, flag, mapq;
     int32_t tid, pos, l_seq, mtid, mpos, tlen;
-    uint64_t cig_off;      // absolute offset of the effective CIGAR (CG-swapped if needed)
+    O cig_off;             // offset of the effective CIGAR (CG-swapped if needed)
     uint32_t n_cigar_eff;
-    uint64_t cg_beg, cg_end;   // spliced-out CG tag, or (0,0)
+    O cg_beg, cg_end;      // spliced-out CG tag, or (0,0)
 };
+typedef RecInfoT<uint64_t> RecInfo;
 
 // (the bam_read1 checks themselves live in bam_tiles_lds.hip: rec_check_t / rec_hop)
 struct TileOut {

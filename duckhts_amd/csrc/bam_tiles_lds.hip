@@ -19,9 +19,17 @@
 #define TR_F_HEAP 2ull                   /* a string arena is too small */
 #define TR_F_TIMEOUT 4ull                /* look-back wait expired (bam_tile_rows; internal error) */
 
+// The record helpers below (find_nul_t .. rec_check_t) are templates over an accessor S.  S::off is the type they compute offsets in,
+// S::none() the "no such offset" value (NONE64 narrowed to S::off), s.lim(st) the number of valid bytes in the accessor's offset space
+// and s.abs(o) the offset in the batch buffer.  GSrc and PSrc take absolute 64-bit offsets; WSrc takes 32-bit offsets relative to the
+// tile, so that a record inside the staged window is checked and walked in single VALU instructions instead of 64-bit pairs.
 // global-memory accessor (records that do not fit the staged window)
 struct GSrc {
+    typedef uint64_t off;
     const uint8_t *g;
+    static __device__ __forceinline__ uint64_t none() { return NONE64; }
+    __device__ __forceinline__ uint64_t lim(const BamStream &st) const { return st.ulen; }
+    __device__ __forceinline__ uint64_t abs(uint64_t o) const { return o; }
     __device__ __forceinline__ uint8_t u8(uint64_t o) const { return g[o]; }
     __device__ __forceinline__ uint32_t u32(uint64_t o) const { return ldu32(g + o); }
     __device__ __forceinline__ uint64_t u64(uint64_t o) const { uint64_t v; __builtin_memcpy(&v, g + o, 8); return v; }   // buffers are padded
@@ -31,134 +39,143 @@ struct LSrc { const uint8_t *g; const uint8_t *l; uint64_t base; uint32_t len; }
 // direct accessor into the staged window: every offset touched must lie inside it (checked by the caller once per record).
 // Kept as (LDS pointer, 32-bit index) so the compiler emits ds_read, not flat loads.
 struct PSrc {
+    typedef uint64_t off;
     const uint8_t *l; uint64_t base;
+    static __device__ __forceinline__ uint64_t none() { return NONE64; }
+    __device__ __forceinline__ uint64_t lim(const BamStream &st) const { return st.ulen; }
+    __device__ __forceinline__ uint64_t abs(uint64_t o) const { return o; }
     __device__ __forceinline__ uint8_t u8(uint64_t o) const { return l[(uint32_t)(o - base)]; }
     __device__ __forceinline__ uint32_t u32(uint64_t o) const { uint32_t v; __builtin_memcpy(&v, l + (uint32_t)(o - base), 4); return v; }
     __device__ __forceinline__ uint64_t u64(uint64_t o) const { uint64_t v; __builtin_memcpy(&v, l + (uint32_t)(o - base), 8); return v; }   // window is padded by 16 B
 };
+// the staged window by 32-bit offsets relative to the tile's first byte (the row passes, for a record that lies inside the window:
+// every offset of such a record is below TL_TILE + TL_HALO + 16, so no sum below can wrap)
+struct WSrc {
+    typedef uint32_t off;
+    const uint8_t *l; uint64_t base; uint32_t len;              // len: valid bytes of the window
+    static __device__ __forceinline__ uint32_t none() { return 0xffffffffu; }
+    __device__ __forceinline__ uint32_t lim(const BamStream &) const { return len; }
+    __device__ __forceinline__ uint64_t abs(uint32_t o) const { return base + o; }
+    __device__ __forceinline__ uint8_t u8(uint32_t o) const { return l[o]; }
+    __device__ __forceinline__ uint32_t u32(uint32_t o) const { uint32_t v; __builtin_memcpy(&v, l + o, 4); return v; }
+    __device__ __forceinline__ uint64_t u64(uint32_t o) const { uint64_t v; __builtin_memcpy(&v, l + o, 8); return v; }   // window is padded by 16 B
+};
 
 // first q in [p, end) with byte q == 0, or end: eight bytes per step (one LDS / global read instead of eight dependent ones).
 // (v - 0x01..) & ~v & 0x80..: the LOWEST set bit marks the first zero byte exactly; bytes at or past `end` are ignored.
-template <class S> __device__ __forceinline__ uint64_t find_nul_t(const S &s, uint64_t p, uint64_t end) {
+template <class S> __device__ __forceinline__ typename S::off find_nul_t(const S &s, typename S::off p, typename S::off end) {
+    typedef typename S::off O;
     while (p < end) {
         const uint64_t v = s.u64(p), z = (v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull;
-        if (z) { const uint64_t q = p + (uint64_t)((__ffsll((unsigned long long)z) - 1) >> 3); return q < end ? q : end; }
+        if (z) { const O q = p + (O)((__ffsll((unsigned long long)z) - 1) >> 3); return q < end ? q : end; }
         p += 8;
     }
     return end;
 }
 
-template <class S> __device__ __forceinline__ uint64_t aux_skip_t(const S &s, uint64_t p, uint64_t end) {
-    if (p >= end) return end;
-    uint8_t t = s.u8(p); ++p;
-    if (t == 'Z' || t == 'H') {
-        p = find_nul_t(s, p, end);
-        return p < end ? p + 1 : end;
-    }
-    if (t == 'B') {
-        if (end - p < 5) return NONE64;
-        uint8_t sub = s.u8(p);
-        int sz = aux_size(sub); if (sub == 'Z' || sub == 'H' || sub == 'B') sz = sub;
-        ++p;
-        uint64_t n = s.u32(p); p += 4;
-        if (sz == 0 || end - p < (uint64_t)sz * n) return NONE64;
-        return p + (uint64_t)sz * n;
-    }
-    int sz = aux_size(t);
-    if (sz == 0) return NONE64;
-    if (end - p < (uint64_t)sz) return NONE64;
-    return p + sz;
-}
-
-// aux_skip_t for a field whose type byte (and the byte after it) have already been read
-template <class S> __device__ __forceinline__ uint64_t aux_skip_known(const S &s, uint64_t p, uint64_t end, uint8_t t, uint8_t nxt) {
+// One hop over the auxiliary field whose type byte `t` lies at p (`nxt` = the byte after it: the B sub-type): the offset behind the
+// field, `end` for a Z/H value without NUL, none() for an unknown type, a truncated field or a B payload that overruns the record
+// (htslib sam.c skip_aux).  The fixed-size types are straight-line code (aux_size is a bit-field extract); only Z/H (the NUL search)
+// and B (the count) are predicated sections.
+template <class S> __device__ __forceinline__ typename S::off aux_skip_known(const S &s, typename S::off p, typename S::off end, uint8_t t, uint8_t nxt) {
+    typedef typename S::off O;
     if (p >= end) return end;
     ++p;
+    const O sz = (O)aux_size(t);
+    O e = (sz != 0 && end - p >= sz) ? p + sz : S::none();
     if (t == 'Z' || t == 'H') {
-        p = find_nul_t(s, p, end);
-        return p < end ? p + 1 : end;
+        const O q = find_nul_t(s, p, end);
+        e = q < end ? q + 1 : end;
+    } else if (t == 'B') {
+        e = S::none();
+        if (end - p >= 5) {
+            const uint32_t bsz = (nxt == 'Z' || nxt == 'H' || nxt == 'B') ? (uint32_t)nxt : (uint32_t)aux_size(nxt);   // (aux_type2size returns the byte itself for these three)
+            const uint64_t bytes = (uint64_t)bsz * s.u32(p + 1);
+            if (bsz != 0 && (uint64_t)(end - (p + 5)) >= bytes) e = p + 5 + (O)bytes;
+        }
     }
-    if (t == 'B') {
-        if (end - p < 5) return NONE64;
-        const uint8_t sub = nxt;
-        int sz = aux_size(sub); if (sub == 'Z' || sub == 'H' || sub == 'B') sz = sub;
-        ++p;
-        uint64_t n = s.u32(p); p += 4;
-        if (sz == 0 || end - p < (uint64_t)sz * n) return NONE64;
-        return p + (uint64_t)sz * n;
-    }
-    int sz = aux_size(t);
-    if (sz == 0) return NONE64;
-    if (end - p < (uint64_t)sz) return NONE64;
-    return p + sz;
+    return e;
+}
+// the same for a field whose type byte has not been read yet
+template <class S> __device__ __forceinline__ typename S::off aux_skip_t(const S &s, typename S::off p, typename S::off end) {
+    if (p >= end) return end;
+    const uint8_t t = s.u8(p);
+    const uint8_t nxt = (t == 'B' && end - (p + 1) >= 5) ? s.u8(p + 1) : (uint8_t)0;
+    return aux_skip_known(s, p, end, t, nxt);
 }
 
 // (one 4-byte read per field: tag, type and the byte after the type -- the walk is a chain of dependent LDS reads)
-template <class S> __device__ __forceinline__ uint64_t aux_find_t(const S &s, uint64_t aux, uint64_t end, uint8_t t0, uint8_t t1, bool *bad, uint64_t skip_beg, uint64_t skip_end) {
+template <class S> __device__ __forceinline__ typename S::off aux_find_t(const S &s, typename S::off aux, typename S::off end, uint8_t t0, uint8_t t1, bool *bad,
+                                                                        typename S::off skip_beg, typename S::off skip_end) {
+    typedef typename S::off O;
     *bad = false;
-    uint64_t eff_len = (end - aux) - (skip_end - skip_beg);
-    if (eff_len <= 2) return NONE64;
-    uint64_t p = aux;
+    O eff_len = (end - aux) - (skip_end - skip_beg);
+    if (eff_len <= 2) return S::none();
+    O p = aux;
     if (p == skip_beg) p = skip_end;
     p += 2;
     for (;;) {
         const uint32_t x = s.u32(p - 2);                      // tag[0] tag[1] type next   (reads <= 1 byte past `end`: buffers are padded)
         const uint8_t ty = (uint8_t)(x >> 16);
-        const uint64_t e = aux_skip_known(s, p, end, ty, (uint8_t)(x >> 24));
+        const O e = aux_skip_known(s, p, end, ty, (uint8_t)(x >> 24));
         if ((uint8_t)x == t0 && (uint8_t)(x >> 8) == t1) {
-            if (e == NONE64) { *bad = true; return NONE64; }
-            if ((ty == 'Z' || ty == 'H') && s.u8(e - 1) != 0) { *bad = true; return NONE64; }
+            if (e == S::none()) { *bad = true; return S::none(); }
+            if ((ty == 'Z' || ty == 'H') && s.u8(e - 1) != 0) { *bad = true; return S::none(); }
             return p;
         }
-        uint64_t nx = e;
-        if (nx == NONE64) { *bad = true; return NONE64; }
+        O nx = e;
+        if (nx == S::none()) { *bad = true; return S::none(); }
         if (nx == skip_beg) nx = skip_end;
-        if (end - nx <= 2) return NONE64;
+        if (end - nx <= 2) return S::none();
         p = nx + 2;
     }
 }
 
-// same predicates as rec_check (bam_records.hip), reading through the accessor
-template <class S> __device__ __forceinline__ int rec_check_t(const BamStream &st, const S &s, uint64_t o, RecInfo &r, bool full) {
-    if (st.ulen - o < 4) return REC_INCOMPLETE;
+// same predicates as rec_check (bam_records.hip), reading through the accessor.  Sizes are summed in 32 bits: n_cigar * 4 + l_qname +
+// (l_seq + 1) / 2 + l_seq is below 2^18 + 2^8 + 3 * 2^30, and once it has been found <= block_len - 32 every offset of the record is
+// below o + 2^31.
+template <class S> __device__ __forceinline__ int rec_check_t(const BamStream &st, const S &s, typename S::off o, RecInfoT<typename S::off> &r, bool full) {
+    typedef typename S::off O;
+    const O ulen = s.lim(st);
+    if (ulen - o < 4) return REC_INCOMPLETE;
     int32_t block_len = (int32_t)s.u32(o);
     if (block_len < 32) return REC_INVALID;
-    if (st.ulen - o - 4 < 32) return REC_INCOMPLETE;
+    if (ulen - o - 4 < 32) return REC_INCOMPLETE;
     r.block_len = (uint32_t)block_len;
     r.tid = (int32_t)s.u32(o + 4); r.pos = (int32_t)s.u32(o + 8);
     uint32_t x2 = s.u32(o + 12), x3 = s.u32(o + 16);
     r.mapq = (x2 >> 8) & 0xff; r.l_qname = x2 & 0xff;
     r.flag = x3 >> 16; r.n_cigar = x3 & 0xffff;
     r.l_seq = (int32_t)s.u32(o + 20); r.mtid = (int32_t)s.u32(o + 24); r.mpos = (int32_t)s.u32(o + 28); r.tlen = (int32_t)s.u32(o + 32);
-    uint64_t body = (uint64_t)r.block_len - 32;
+    const uint32_t body = r.block_len - 32u;
     if (r.l_seq < 0 || r.l_qname < 1) return REC_INVALID;
-    if (((uint64_t)r.n_cigar << 2) + r.l_qname + (((uint64_t)r.l_seq + 1) >> 1) + (uint64_t)r.l_seq > body) return REC_INVALID;
+    const uint32_t core = (r.n_cigar << 2) + r.l_qname + (((uint32_t)r.l_seq + 1u) >> 1) + (uint32_t)r.l_seq;
+    if (core > body) return REC_INVALID;
     if (!full) {
         // speculation filter (not part of exactness; a wrong rejection only costs a repair round).  The header-range and
         // aux-size tests come BEFORE the "body runs past the buffer" exit, so a hop that lands on garbage with a huge
         // block_len is rejected instead of being mistaken for the incomplete last record of the batch.
         if (r.tid < -1 || r.tid >= st.n_ref || r.mtid < -1 || r.mtid >= st.n_ref) return REC_INVALID;
-        uint64_t core = ((uint64_t)r.n_cigar << 2) + r.l_qname + (((uint64_t)r.l_seq + 1) >> 1) + (uint64_t)r.l_seq;
-        if (body - core > 8 * core + 65536) return REC_INVALID;
-        if (st.ulen - o - 36 < body) return REC_INCOMPLETE;
+        if ((uint64_t)(body - core) > 8ull * core + 65536) return REC_INVALID;
+        if (ulen - o - 36 < body) return REC_INCOMPLETE;
         if (s.u8(o + 36 + r.l_qname - 1) != 0) return REC_INVALID;
         return REC_OK;
     }
-    if (st.ulen - o - 36 < body) return REC_INCOMPLETE;
+    if (ulen - o - 36 < body) return REC_INCOMPLETE;
     r.cig_off = o + 36 + r.l_qname; r.n_cigar_eff = r.n_cigar; r.cg_beg = r.cg_end = 0;
-    uint64_t end = o + 4 + r.block_len;
-    uint64_t aux = r.cig_off + 4ull * r.n_cigar + (((uint64_t)r.l_seq + 1) >> 1) + (uint64_t)r.l_seq;
+    const O end = o + 4 + r.block_len;
+    const O aux = o + 36 + core;
     if (r.n_cigar > 0 && s.u32(r.cig_off) == (4u | ((uint32_t)r.l_seq << 4)) && r.tid >= 0 && r.pos >= 0) {
-        bool bad; uint64_t cg = aux_find_t(s, aux, end, 'C', 'G', &bad, 0, 0);
-        if (cg == NONE64 && bad) return REC_INVALID;
-        if (cg != NONE64 && s.u8(cg) == 'B' && (s.u8(cg + 1) == 'I' || s.u8(cg + 1) == 'i')) {
+        bool bad; const O cg = aux_find_t(s, aux, end, 'C', 'G', &bad, (O)0, (O)0);
+        if (cg == S::none() && bad) return REC_INVALID;
+        if (cg != S::none() && s.u8(cg) == 'B' && (s.u8(cg + 1) == 'I' || s.u8(cg + 1) == 'i')) {
             uint32_t cgl = s.u32(cg + 2);
-            if (cgl >= r.n_cigar && cgl < (1u << 29)) { r.cig_off = cg + 6; r.n_cigar_eff = cgl; r.cg_beg = cg - 2; r.cg_end = cg + 6 + 4ull * cgl; }
+            if (cgl >= r.n_cigar && cgl < (1u << 29)) { r.cig_off = cg + 6; r.n_cigar_eff = cgl; r.cg_beg = cg - 2; r.cg_end = cg + 6 + (O)(4u * cgl); }
         }
     }
     if (r.n_cigar_eff > 0) {
         int64_t qlen = 0;
-        for (uint32_t k = 0; k < r.n_cigar_eff; k++) { uint32_t c = s.u32(r.cig_off + 4ull * k); if (CIG_QUERY(c & 0xf)) qlen += c >> 4; }
+        for (uint32_t k = 0; k < r.n_cigar_eff; k++) { uint32_t c = s.u32(r.cig_off + (O)(4u * k)); if (CIG_QUERY(c & 0xf)) qlen += c >> 4; }
         if (r.l_seq > 0 && !(r.flag & 4) && qlen != r.l_seq) return REC_INVALID;
     }
     if (r.tid >= st.n_ref || r.tid < -1 || r.mtid >= st.n_ref || r.mtid < -1) return REC_INVALID;
@@ -387,57 +404,60 @@ bam_spec_next(BamStream st, uint64_t from, SpecSkip sk, uint64_t *out) {
 
 // The @RG dictionary as unpack_one reads it: in HBM (DictG), or -- when it is small, as it nearly always is -- in a copy the workgroup made
 // in LDS (DictL).  Two types with the same members so that each instantiation keeps its address space (a pointer that may be either
-// becomes a flat access, and flat accesses to LDS fault on this system).  The comparison loop is a chain of dependent byte loads per
+// becomes a flat access.  Flat accesses to LDS do work here -- bam_tile_strings read its window through them for a long time -- but each
+// pays the address-space select in VALU and counts on vmcnt and lgkmcnt at once, so it waits for every store in flight).  The comparison loop is a chain of dependent byte loads per
 // record: out of HBM that was three ~600-cycle round trips per record of a file with one three-letter read group.
 struct DictG { const uint32_t *off; const uint8_t *bytes; int32_t n; };
 struct DictL { const uint32_t *off; const uint8_t *bytes; int32_t n; };
 #define RGL_N 32
 #define RGL_BYTES 256
-template <class S, class D> __device__ __forceinline__ bool unpack_one(const BamStream &st, const S &s, const D &dict, uint64_t o, int64_t row,
+template <class S, class D> __device__ __forceinline__ bool unpack_one(const BamStream &st, const S &s, const D &dict, typename S::off o, int64_t row,
                                                          uint32_t *rec_off, uint8_t *rg_flag, const BamCols &c) {
-    RecInfo r; const int rcv = rec_check_t(st, s, o, r, true);
+    typedef typename S::off O;                              // (WSrc: every offset below is a 32-bit offset into the staged window)
+    RecInfoT<O> r; const int rcv = rec_check_t(st, s, o, r, true);
     if (row < 0) return rcv == REC_OK;                      // filtered out by the region predicate: still validated (the iterator reads it)
-    rec_off[row] = (uint32_t)o;
-    if (rcv != REC_OK) {          // first such row ends the scan (bam_reader.c:754-766); keep the column slots defined
-        c.len_qname[row] = 0; c.len_cigar[row] = 0; c.len_seq[row] = 0; c.len_qual[row] = 0; c.len_rg[row] = 0;
-        c.cig_rel[row] = 0; c.ncig_eff[row] = 0; c.rg_rel[row] = 0; c.rg_idx[row] = -1; rg_flag[row] = 0;
-        return false;
-    }
-    c.flag[row] = (uint16_t)r.flag;
-    c.pos[row] = (int64_t)r.pos + 1;
-    c.mapq[row] = (int32_t)r.mapq;
-    c.pnext[row] = (int64_t)r.mpos + 1;
-    c.tlen[row] = (int64_t)r.tlen;
-    c.tid[row] = r.tid; c.mtid[row] = r.mtid;
-    const uint32_t ql = (uint32_t)(find_nul_t(s, o + 36, o + 36 + r.l_qname) - (o + 36));
-    c.len_qname[row] = ql;
-    uint32_t cl = 0;
-    for (uint32_t j = 0; j < r.n_cigar_eff; j++) cl += ndigits(s.u32(r.cig_off + 4ull * j) >> 4) + 1;
-    c.len_cigar[row] = r.n_cigar_eff ? cl : 1;
-    c.cig_rel[row] = (uint32_t)(r.cig_off - o); c.ncig_eff[row] = r.n_cigar_eff;
-    const uint64_t seq = o + 36 + r.l_qname + 4ull * r.n_cigar;
-    const uint64_t qual = seq + (((uint64_t)r.l_seq + 1) >> 1);
-    c.len_seq[row] = r.l_seq > 0 ? (st.seq_packed ? ((uint32_t)r.l_seq + 1u) >> 1 : (uint32_t)r.l_seq) : 1;
-    c.len_qual[row] = (r.l_seq > 0 && s.u8(qual) != 255) ? (uint32_t)r.l_seq : 1;
-    const uint64_t aux = qual + (uint64_t)r.l_seq, end = o + 4ull + r.block_len;
-    // (bam_read1 does not look at the auxiliary fields: the walk serves the two read-group columns only -- a chain of dependent reads per
-    //  record that a projection without them does not pay)
-    bool bad = false; const uint64_t rg = st.want_rg ? aux_find_t(s, aux, end, 'R', 'G', &bad, r.cg_beg, r.cg_end) : NONE64;
-    uint32_t rl = 0; int32_t rgi = -1; uint8_t rgv = 0;
-    if (rg != NONE64 && (s.u8(rg) == 'Z' || s.u8(rg) == 'H')) {
-        rgv = 1;
-        rl = (uint32_t)(find_nul_t(s, rg + 1, end) - (rg + 1));      // aux_find_t proved the value is NUL-terminated inside the record
-        for (int32_t q = 0; q < dict.n; q++) {
-            const uint32_t a = dict.off[q], b = dict.off[q + 1];
-            if (b - a != rl) continue;
-            bool eq = true;
-            for (uint32_t j = 0; j < rl; j++) if (dict.bytes[a + j] != s.u8(rg + 1 + j)) { eq = false; break; }
-            if (eq) { rgi = q; break; }
+    rec_off[row] = (uint32_t)s.abs(o);
+    // One store site for the string lengths and the string pass's scratch, whether the row is valid or not (a row that fails validation ends
+    // the scan, bam_reader.c:754-766, and keeps its slots defined: zeros).  With the stores of the two cases in separate branches the compiler
+    // merged them behind a select of two BamCols members' addresses, which sent the kernel argument through scratch memory and two of the
+    // columns through flat stores behind a vmcnt(0) wait.
+    uint32_t ql = 0, cl = 0, ls = 0, lq = 0, rl = 0, cig_rel = 0, ne = 0, rg_rel = 0; int32_t rgi = -1; uint8_t rgv = 0;
+    const bool ok = rcv == REC_OK;
+    if (ok) {
+        c.flag[row] = (uint16_t)r.flag;
+        c.pos[row] = (int64_t)r.pos + 1;
+        c.mapq[row] = (int32_t)r.mapq;
+        c.pnext[row] = (int64_t)r.mpos + 1;
+        c.tlen[row] = (int64_t)r.tlen;
+        c.tid[row] = r.tid; c.mtid[row] = r.mtid;
+        ql = (uint32_t)(find_nul_t(s, o + 36, o + 36 + r.l_qname) - (o + 36));
+        for (uint32_t j = 0; j < r.n_cigar_eff; j++) cl += ndigits(s.u32(r.cig_off + (O)(4u * j)) >> 4) + 1;
+        if (!r.n_cigar_eff) cl = 1;
+        cig_rel = (uint32_t)(r.cig_off - o); ne = r.n_cigar_eff;
+        const O seq = o + 36 + r.l_qname + 4u * r.n_cigar;
+        const O qual = seq + (((uint32_t)r.l_seq + 1u) >> 1);
+        ls = r.l_seq > 0 ? (st.seq_packed ? ((uint32_t)r.l_seq + 1u) >> 1 : (uint32_t)r.l_seq) : 1;
+        lq = (r.l_seq > 0 && s.u8(qual) != 255) ? (uint32_t)r.l_seq : 1;
+        const O aux = qual + (uint32_t)r.l_seq, end = o + 4 + r.block_len;
+        // (bam_read1 does not look at the auxiliary fields: the walk serves the two read-group columns only -- a chain of dependent reads per
+        //  record that a projection without them does not pay)
+        bool bad = false; const O rg = st.want_rg ? aux_find_t(s, aux, end, 'R', 'G', &bad, r.cg_beg, r.cg_end) : S::none();
+        if (rg != S::none() && (s.u8(rg) == 'Z' || s.u8(rg) == 'H')) {
+            rgv = 1;
+            rl = (uint32_t)(find_nul_t(s, rg + 1, end) - (rg + 1));      // aux_find_t proved the value is NUL-terminated inside the record
+            for (int32_t q = 0; q < dict.n; q++) {
+                const uint32_t a = dict.off[q], b = dict.off[q + 1];
+                if (b - a != rl) continue;
+                bool eq = true;
+                for (uint32_t j = 0; j < rl; j++) if (dict.bytes[a + j] != s.u8(rg + 1 + j)) { eq = false; break; }
+                if (eq) { rgi = q; break; }
+            }
+            rg_rel = (uint32_t)(rg + 1 - o);
         }
-        c.rg_rel[row] = (uint32_t)(rg + 1 - o);
-    } else c.rg_rel[row] = 0;
-    c.len_rg[row] = rl; c.rg_idx[row] = rgi; rg_flag[row] = rgv;
-    return true;
+    }
+    c.len_qname[row] = ql; c.len_cigar[row] = cl; c.len_seq[row] = ls; c.len_qual[row] = lq; c.len_rg[row] = rl;
+    c.cig_rel[row] = cig_rel; c.ncig_eff[row] = ne; c.rg_rel[row] = rg_rel; c.rg_idx[row] = rgi; rg_flag[row] = rgv;
+    return ok;
 }
 
 // One wave per tile: rebuild the record list in LDS, then one lane per record writes the fixed-width columns, the
@@ -474,6 +494,7 @@ bam_tile_unpack(BamStream st, BamDict dict, int64_t ntiles, TileOut out, const u
     DictL dl; dl.off = rg_lo; dl.bytes = rg_lb; dl.n = dict.n_rg;
     LSrc s; tile_stage(st, tb, buf, s, lane);
     PSrc ls; ls.l = buf; ls.base = tb;
+    WSrc ws; ws.l = buf; ws.base = tb; ws.len = s.len;
     GSrc gs; gs.g = st.u;
     if (tile_recs_first[t] == first) {
         // record starts left by bam_tile_scan's walk from this same `first` (one coalesced load instead of a serial chain of hops)
@@ -495,8 +516,8 @@ bam_tile_unpack(BamStream st, BamDict dict, int64_t ntiles, TileOut out, const u
         // with a region filter: row_map[row] = compacted row if kept (map[row+1] > map[row]), rows are validated either way
         int64_t dst = row;
         if (row_map) dst = (row_map[row + 1] > row_map[row]) ? (int64_t)row_map[row] : -1;
-        const bool good = fast ? (dict_lds ? unpack_one(st, ls, dl, o, dst, rec_off, rg_flag, c) : unpack_one(st, ls, dg, o, dst, rec_off, rg_flag, c))
-                               : unpack_one(st, gs, dg, o, dst, rec_off, rg_flag, c);
+        const bool good = fast ? (dict_lds ? unpack_one(st, ws, dl, (uint32_t)rel, dst, rec_off, rg_flag, c) : unpack_one(st, ws, dg, (uint32_t)rel, dst, rec_off, rg_flag, c))
+                               : unpack_one(st, gs, dg, o, dst, rec_off, rg_flag, c);   // (kept inline: as a __noinline__ call this pass took 0.914 instead of 0.64 ms)
         if (!good) atomicMin(bad_row, (unsigned long long)row);
     }
 }
@@ -506,11 +527,16 @@ bam_tile_unpack(BamStream st, BamDict dict, int64_t ntiles, TileOut out, const u
 // offsets and parses its core); SEQ and QUAL are then written by CHUNK: the 16-byte output chunks of all rows of the group are
 // numbered consecutively (wave prefix sum, chunk -> row map in LDS) and dealt to the lanes 64 at a time, so every lane converts
 // and stores 16 bytes per step whatever the read length, and consecutive lanes store consecutive heap bytes.  QNAME, the RG
-// value and the CIGAR text are short and written by the row's own lane.  Fields longer than TS_LONG bytes are streamed by the
-// whole wave from HBM afterwards.  Same bytes as seq_to_string / qual_to_string / cigar_to_kstring (src/bam_reader.c:560-640).
+// value and the CIGAR text are short and written by the row's own lane.  Fields longer than TS_LONG bytes, and SEQ / QUAL of a row
+// that does not lie inside the staged window, are streamed by the whole wave from HBM afterwards.  Same bytes as seq_to_string / qual_to_string / cigar_to_kstring (src/bam_reader.c:560-640).
 #define TS_LONG 512u
 #define TS_MAPN (64u * (TS_LONG / 16u))
+// bam_tile_strings decides ONCE PER ROW whether the record lies inside the staged window and then reads it through WSrc (LDS, 32-bit
+// offsets relative to the tile) or GSrc (HBM): two types, so every access is a ds_read or a global_load.  TsSrc below makes that choice
+// per access behind one pointer, which the compiler turns into flat loads (address-space select per access, and a wait on vmcnt and
+// lgkmcnt together, i.e. on every heap store in flight, in front of each use); only the fused row pass (bam_tile_rows.hip) still uses it.
 struct TsSrc {                 // bytes of the inflated stream by absolute offset: LDS inside the staged window, HBM outside
+    typedef uint64_t off;
     const uint8_t *l, *g; uint64_t base; uint32_t len;
     __device__ __forceinline__ uint64_t u64(uint64_t o) const {
         uint64_t v; const uint64_t rel = o - base;
@@ -523,8 +549,9 @@ struct TsSrc {                 // bytes of the inflated stream by absolute offse
         return v;
     }
 };
-__device__ __forceinline__ void ts_seq_chunk(const TsSrc &src, uint64_t seq, uint32_t l_seq, uint32_t k, uint8_t *d, int packed) {
-    const uint64_t p = src.u64(seq + 8ull * k);
+// (the last chunk of a field reads up to 15 bytes past its end, so up to 15 bytes past the record: the HBM buffer and the window are padded)
+template <class S> __device__ __forceinline__ void ts_seq_chunk(const S &src, typename S::off seq, uint32_t l_seq, uint32_t k, uint8_t *d, int packed) {
+    const uint64_t p = src.u64(seq + (typename S::off)(8u * k));
     if (packed) {                                           // the 8 source bytes of this chunk as they are (16 bases)
         const uint32_t nb = ((l_seq + 1u) >> 1) - 8u * k, w[4] = {(uint32_t)p, (uint32_t)(p >> 32), 0u, 0u};
         store_n16(d + 8u * k, w, nb < 8u ? nb : 8u);
@@ -534,8 +561,8 @@ __device__ __forceinline__ void ts_seq_chunk(const TsSrc &src, uint64_t seq, uin
     store_n16(d + 16u * k, w, l_seq - 16u * k);
 }
 // returns the index of the first byte that became NUL (absolute in the field) or 0xffffffff
-__device__ __forceinline__ uint32_t ts_qual_chunk(const TsSrc &src, uint64_t qual, uint32_t l_seq, uint32_t k, uint8_t *d) {
-    const uint64_t a = src.u64(qual + 16ull * k), b = src.u64(qual + 16ull * k + 8);
+template <class S> __device__ __forceinline__ uint32_t ts_qual_chunk(const S &src, typename S::off qual, uint32_t l_seq, uint32_t k, uint8_t *d) {
+    const uint64_t a = src.u64(qual + (typename S::off)(16u * k)), b = src.u64(qual + (typename S::off)(16u * k) + 8);
     uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
     const uint32_t n = l_seq - 16u * k < 16u ? l_seq - 16u * k : 16u;
     uint32_t fz = 0xffffffffu;
@@ -550,6 +577,41 @@ __device__ __forceinline__ uint32_t ts_qual_chunk(const TsSrc &src, uint64_t qua
     store_n16(d + 16u * k, w, n);
     return fz;
 }
+// what the string pass needs of a row's core: l_seq (0 for a row that failed validation), where SEQ starts in the record, and whether QUAL is "*"
+template <class S> __device__ __forceinline__ void ts_core(const S &src, typename S::off o, bool ok, uint32_t &l_seq, uint32_t &seq_rel, bool &star) {
+    const uint32_t x2 = src.u32(o + 12), x3 = src.u32(o + 16);
+    const int32_t l_seq_raw = (int32_t)src.u32(o + 20);
+    l_seq = (ok && l_seq_raw > 0) ? (uint32_t)l_seq_raw : 0u;
+    seq_rel = 36u + (x2 & 0xff) + 4u * (x3 & 0xffff);
+    star = !(l_seq > 0 && (uint8_t)src.u32(o + seq_rel + ((l_seq + 1u) >> 1)) != 255);
+}
+// QNAME, the RG value and the CIGAR text of one row, written by the row's own lane
+struct TsRow { uint32_t len_qn, rl, rg_rel, ne, cig_rel, off_qn, off_rg, off_cig; };
+template <class S> __device__ __forceinline__ void ts_row_fields(const S &src, typename S::off o, const TsRow &q, const BamStrOut &s, bool w_qn, bool w_rg, bool w_cig) {
+    for (uint32_t b = 0; w_qn && b < q.len_qn; b += 16) {
+        const uint64_t a = src.u64(o + 36 + b), e = src.u64(o + 36 + b + 8);
+        const uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)e, (uint32_t)(e >> 32)};
+        store_n16(s.qname + q.off_qn + b, w, q.len_qn - b);
+    }
+    for (uint32_t b = 0; w_rg && b < q.rl; b += 16) {
+        const uint64_t a = src.u64(o + q.rg_rel + b), e = src.u64(o + q.rg_rel + b + 8);
+        const uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)e, (uint32_t)(e >> 32)};
+        store_n16(s.rg + q.off_rg + b, w, q.rl - b);
+    }
+    uint8_t *dc = s.cigar + q.off_cig;
+    if (w_cig && q.ne == 0) dc[0] = '*';
+    uint32_t p = 0;
+    for (uint32_t k = 0; w_cig && k < q.ne; k++) {
+        const uint32_t op = src.u32(o + q.cig_rel + 4u * k);
+        uint32_t ol = op >> 4; const uint32_t nd = ndigits(ol);
+        for (uint32_t z = 0; z < nd; z++) { dc[p + nd - 1 - z] = (uint8_t)('0' + ol % 10); ol /= 10; }
+        // sam.h:112 BAM_CIGAR_STR "MIDNSHP=XB", '?' beyond; byte gather with v_perm_b32
+        const uint32_t C0 = 0x4e44494du, C1 = 0x3d504853u, C2 = 0x3f3f4258u, C3 = 0x3f3f3f3fu;
+        const uint32_t oc = op & 0xf, selb = (oc & 7u) | 0x0c0c0c00u;
+        dc[p + nd] = (uint8_t)((oc & 8u) ? __builtin_amdgcn_perm(C3, C2, selb) : __builtin_amdgcn_perm(C1, C0, selb));
+        p += nd + 1;
+    }
+}
 // Two waves per tile: wave 0 owns the rows (offsets, the short per-row fields), both waves share the SEQ/QUAL chunks; the tile is
 // latency-bound, so a second wave on the same LDS image is nearly free occupancy.
 #define TS_THREADS 128
@@ -558,7 +620,7 @@ bam_tile_strings(BamStream st, int64_t ntiles, TileOut out, const uint32_t *rowb
                  const uint32_t *rec_off, const uint32_t *row_map, BamCols c, BamStrOut s, uint32_t colmask) {
     // colmask: projection pushdown (bit = read_bam column id): heaps of columns that are not projected are not written
     const bool w_qn = colmask & (1u << 0), w_cig = colmask & (1u << 5), w_seq = colmask & (1u << 9), w_qual = colmask & (1u << 10), w_rg = colmask & (1u << 11);
-    __shared__ __attribute__((aligned(16))) uint8_t buf[TL_TILE + TL_HALO];
+    __shared__ __attribute__((aligned(16))) uint8_t buf[TL_TILE + TL_HALO + 16];     // +16: the 16-byte chunk reads may run past the last record
     __shared__ uint32_t r_seq[64], r_lseq[64], r_oseq[64], r_oqual[64], r_c0[64], r_nul[64];
     __shared__ uint8_t cmap[TS_MAPN];
     __shared__ uint32_t sT;
@@ -590,7 +652,8 @@ bam_tile_strings(BamStream st, int64_t ntiles, TileOut out, const uint32_t *rowb
     RowIn ri; memset(&ri, 0, sizeof(ri));
     if (w0) ri = row_in(d0 + lane < d1 ? d0 + lane : d0);
     LSrc ss; tile_stage(st, tb, buf, ss, tid, TS_THREADS);
-    TsSrc src; src.l = buf; src.g = st.u; src.base = tb; src.len = ss.len;
+    WSrc ws; ws.l = buf; ws.base = tb; ws.len = ss.len;
+    GSrc gs; gs.g = st.u;
 
     for (int64_t g0 = d0; g0 < d1; g0 += 64) {
         const int64_t d = g0 + lane;
@@ -601,20 +664,21 @@ bam_tile_strings(BamStream st, int64_t ntiles, TileOut out, const uint32_t *rowb
         const uint32_t len_seq = ri.len_seq, len_qn = ri.len_qn, rl = ri.rl, rg_rel = ri.rg_rel, ne = ri.ne, cig_rel = ri.cig_rel;
         const uint32_t off_qn = ri.off_qn, off_rg = ri.off_rg, off_cig = ri.off_cig, off_seq = ri.off_seq, off_qual = ri.off_qual;
         const bool ok = act && len_seq != 0;                       // rows that failed validation reserve nothing
-        bool star = true, lng = false; uint32_t l_seq = 0; uint64_t seq = 0;
+        // inw: the whole record lies inside the staged window (decided here, once per row: nearly every row of a short-read file).  Its
+        // fields are read out of LDS by offsets relative to the tile; the chunk reads may touch up to 15 bytes behind the record, which the
+        // window's padding covers.  A row that crosses the window's end is read from HBM only: its short fields by its own lane, SEQ and
+        // QUAL with the long rows.
+        bool star = true, lng = false, inw = false; uint32_t l_seq = 0, seq_rel = 0;
+        const uint64_t rel64 = o - tb; const uint32_t rel = (uint32_t)rel64;
         if (w0) {
-            const uint32_t x2 = src.u32(o + 12), x3 = src.u32(o + 16);
-            const int32_t l_seq_raw = (int32_t)src.u32(o + 20);
-            l_seq = (ok && l_seq_raw > 0) ? (uint32_t)l_seq_raw : 0u;
-            seq = o + 36 + (x2 & 0xff) + 4ull * (x3 & 0xffff);
-            const uint64_t qual = seq + (((uint64_t)l_seq + 1) >> 1);
-            star = !(l_seq > 0 && (uint8_t)src.u32(qual) != 255);
-            lng = l_seq > TS_LONG;
+            if (rel64 + 4 <= (uint64_t)ws.len) { const uint32_t bl = ws.u32(rel); inw = bl <= ws.len - rel - 4u; }
+            if (inw) ts_core(ws, rel, ok, l_seq, seq_rel, star); else ts_core(gs, o, ok, l_seq, seq_rel, star);
+            lng = l_seq > TS_LONG || !inw;
             const uint32_t nch = (ok && !lng && (w_seq || w_qual)) ? (l_seq + 15u) >> 4 : 0u;
             const uint32_t cinc = wave_incl_scan(nch, lane);
             const uint32_t c0 = cinc - nch;
             if (lane == 63) sT = cinc;
-            r_seq[lane] = (uint32_t)(seq - tb); r_lseq[lane] = star ? (l_seq | 0x80000000u) : l_seq; r_oseq[lane] = off_seq; r_oqual[lane] = off_qual;
+            r_seq[lane] = rel + seq_rel; r_lseq[lane] = star ? (l_seq | 0x80000000u) : l_seq; r_oseq[lane] = off_seq; r_oqual[lane] = off_qual;
             r_c0[lane] = c0; r_nul[lane] = 0xffffffffu;
             for (uint32_t k = 0; k < nch; k++) cmap[c0 + k] = (uint8_t)lane;
         }
@@ -625,10 +689,10 @@ bam_tile_strings(BamStream st, int64_t ntiles, TileOut out, const uint32_t *rowb
             const uint32_t ch = cb + (uint32_t)tid;
             if (ch < T) {
                 const uint32_t j = cmap[ch], k = ch - r_c0[j], ls = r_lseq[j], lq = ls & 0x7fffffffu;
-                const uint64_t sq = tb + r_seq[j];
-                if (w_seq) ts_seq_chunk(src, sq, lq, k, s.seq + r_oseq[j], st.seq_packed);
+                const uint32_t sq = r_seq[j];                              // (only rows inside the window have chunks here)
+                if (w_seq) ts_seq_chunk(ws, sq, lq, k, s.seq + r_oseq[j], st.seq_packed);
                 if (w_qual && !(ls >> 31)) {
-                    const uint32_t fz = ts_qual_chunk(src, sq + (((uint64_t)lq + 1) >> 1), lq, k, s.qual + r_oqual[j]);
+                    const uint32_t fz = ts_qual_chunk(ws, sq + ((lq + 1u) >> 1), lq, k, s.qual + r_oqual[j]);
                     if (fz != 0xffffffffu) atomicMin(&r_nul[j], fz);
                 }
             }
@@ -637,41 +701,20 @@ bam_tile_strings(BamStream st, int64_t ntiles, TileOut out, const uint32_t *rowb
         if (ok) {
             if (w_seq && l_seq == 0) s.seq[off_seq] = st.seq_packed ? 0 : '*';
             if (w_qual && star) s.qual[off_qual] = '*';
-            for (uint32_t b = 0; w_qn && b < len_qn; b += 16) {
-                const uint64_t a = src.u64(o + 36 + b), e = src.u64(o + 36 + b + 8);
-                const uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)e, (uint32_t)(e >> 32)};
-                store_n16(s.qname + off_qn + b, w, len_qn - b);
-            }
-            for (uint32_t b = 0; w_rg && b < rl; b += 16) {
-                const uint64_t a = src.u64(o + rg_rel + b), e = src.u64(o + rg_rel + b + 8);
-                const uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)e, (uint32_t)(e >> 32)};
-                store_n16(s.rg + off_rg + b, w, rl - b);
-            }
-            uint8_t *dc = s.cigar + off_cig;
-            if (w_cig && ne == 0) dc[0] = '*';
-            uint32_t p = 0;
-            for (uint32_t q = 0; w_cig && q < ne; q++) {
-                const uint32_t op = src.u32(o + cig_rel + 4ull * q);
-                uint32_t ol = op >> 4; const uint32_t nd = ndigits(ol);
-                for (uint32_t z = 0; z < nd; z++) { dc[p + nd - 1 - z] = (uint8_t)('0' + ol % 10); ol /= 10; }
-                // sam.h:112 BAM_CIGAR_STR "MIDNSHP=XB", '?' beyond; byte gather with v_perm_b32
-                const uint32_t C0 = 0x4e44494du, C1 = 0x3d504853u, C2 = 0x3f3f4258u, C3 = 0x3f3f3f3fu;
-                const uint32_t oc = op & 0xf, selb = (oc & 7u) | 0x0c0c0c00u;
-                dc[p + nd] = (uint8_t)((oc & 8u) ? __builtin_amdgcn_perm(C3, C2, selb) : __builtin_amdgcn_perm(C1, C0, selb));
-                p += nd + 1;
-            }
+            const TsRow q = {len_qn, rl, rg_rel, ne, cig_rel, off_qn, off_rg, off_cig};
+            if (inw) ts_row_fields(ws, rel, q, s, w_qn, w_rg, w_cig); else ts_row_fields(gs, o, q, s, w_qn, w_rg, w_cig);
         }
-        // ---- long fields: wave 0 streams one row at a time ----
+        // ---- long fields and rows that leave the window: wave 0 streams one row at a time from HBM ----
         if (w0) {
-            uint64_t LM = __ballot(ok && lng && (w_seq || w_qual));
+            uint64_t LM = __ballot(ok && lng && l_seq > 0 && (w_seq || w_qual));
             while (LM) {
                 const int i = __ffsll((unsigned long long)LM) - 1; LM &= LM - 1;
                 const uint32_t lq = RDLANE(l_seq, i), st_i = RDLANE((uint32_t)star, i), os = RDLANE(off_seq, i), oq = RDLANE(off_qual, i);
-                const uint64_t sq = ((uint64_t)RDLANE((uint32_t)(seq >> 32), i) << 32) | RDLANE((uint32_t)seq, i);
+                const uint64_t sq = tb + RDLANE(rel + seq_rel, i);
                 uint32_t fzm = 0xffffffffu;
                 for (uint32_t k = lane; k < (lq + 15u) >> 4; k += 64) {
-                    if (w_seq) ts_seq_chunk(src, sq, lq, k, s.seq + os, st.seq_packed);
-                    if (w_qual && !st_i) { const uint32_t fz = ts_qual_chunk(src, sq + (((uint64_t)lq + 1) >> 1), lq, k, s.qual + oq); fzm = fz < fzm ? fz : fzm; }
+                    if (w_seq) ts_seq_chunk(gs, sq, lq, k, s.seq + os, st.seq_packed);
+                    if (w_qual && !st_i) { const uint32_t fz = ts_qual_chunk(gs, sq + (((uint64_t)lq + 1) >> 1), lq, k, s.qual + oq); fzm = fz < fzm ? fz : fzm; }
                 }
                 if (fzm != 0xffffffffu) atomicMin(&r_nul[i], fzm);
             }

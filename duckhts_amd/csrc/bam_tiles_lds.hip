@@ -244,13 +244,49 @@ __device__ __forceinline__ int spec_check_lds(const BamStream &st, const PSrc &l
     return REC_OK;
 }
 
-__device__ __forceinline__ void tile_stage(const BamStream &st, uint64_t tb, uint8_t *buf, LSrc &s, int lane, uint32_t nthr = 64u) {
-    uint64_t left = st.ulen - tb;
-    uint32_t avail = left < (uint64_t)(TL_TILE + TL_HALO) ? (uint32_t)left : (TL_TILE + TL_HALO);
-    uint32_t pad = (avail + 15u) & ~15u;                      // the inflated buffer carries >= 256 bytes of padding
-    for (uint32_t k = (uint32_t)lane * 16u; k < pad; k += nthr * 16u) { uint4 v = *(const uint4 *)(st.u + tb + k); *(uint4 *)(buf + k) = v; }
-    s.g = st.u; s.l = buf; s.base = tb; s.len = avail;
+// Six wave-uniform values loaded from tables, pinned in scalar registers at this point of the program.  Without it the compiler sinks each
+// load behind the early return that guards its first use (a chain of s_load / s_waitcnt pairs, one memory round trip each), and narrows the
+// 64-bit load of a word that is only tested against a small mask into a 32-bit VECTOR load, whose vmcnt(0) wait drains the tile's loads.
+// (not volatile: a statement with side effects counts as a store, and the loads behind it would no longer be scalar)
+#define TL_LOADED_HERE6(a, b, c, d, e, f) asm("" : "+s"(a), "+s"(b), "+s"(c), "+s"(d), "+s"(e), "+s"(f))
+// Staging a tile (+ halo) into LDS, in two halves: tile_load issues EVERY 16-byte load of the window before anything waits (nine per lane
+// at 64 threads, five at 128), tile_store writes them to LDS and publishes the window behind a barrier.  As one loop of load / wait / store
+// with a run-time trip count the window cost nine dependent HBM round trips per tile, and no byte of it was looked at before the last one
+// returned.  For the loads to stay together the LDS stores must be unconditional: behind `if (k < pad)` the compiler sinks each
+// load into its store's block.  So every piece is stored; a piece at or past the stream's padded end is loaded from the tile's first bytes
+// instead (the address is clamped, never formed past tb + pad), and lands behind `len`, where no accessor reads.  With 128 threads the fifth
+// piece exists for the first 64 only; the other 64 load and store their own first piece again.
+template <uint32_t NTHR> struct TileLoad {
+    static constexpr uint32_t WIN = TL_TILE + TL_HALO, N = (WIN + NTHR * 16u - 1u) / (NTHR * 16u);
+    uint4 v[N]; uint32_t avail;
+};
+template <uint32_t NTHR> __device__ __forceinline__ uint32_t tile_piece(uint32_t i, int tid) {
+    const uint32_t k = (i * NTHR + (uint32_t)tid) * 16u;
+    if ((i + 1u) * NTHR * 16u <= TL_TILE + TL_HALO) return k;                  // a whole round of pieces (i is a constant after unrolling)
+    return k < TL_TILE + TL_HALO ? k : (uint32_t)tid * 16u;
+}
+template <uint32_t NTHR> __device__ __forceinline__ void tile_load(const BamStream &st, uint64_t tb, TileLoad<NTHR> &r, int tid) {
+    static_assert(NTHR * 16u <= TL_TILE + TL_HALO, "every thread has a first piece inside the window");
+    const uint64_t left = st.ulen - tb;
+    r.avail = left < (uint64_t)(TL_TILE + TL_HALO) ? (uint32_t)left : (TL_TILE + TL_HALO);
+    const uint32_t pad = (r.avail + 15u) & ~15u;              // the inflated buffer carries >= 256 bytes of padding
+    const uint8_t *src = st.u + tb;
+    if (pad) {
+#pragma unroll
+        for (uint32_t i = 0; i < TileLoad<NTHR>::N; i++) { const uint32_t k = tile_piece<NTHR>(i, tid); r.v[i] = *(const uint4 *)(src + (k < pad ? k : 0u)); }
+    } else {                                                  // an empty stream: nothing to read
+#pragma unroll
+        for (uint32_t i = 0; i < TileLoad<NTHR>::N; i++) r.v[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+template <uint32_t NTHR> __device__ __forceinline__ void tile_store(const BamStream &st, uint64_t tb, const TileLoad<NTHR> &r, uint8_t *buf, LSrc &s, int tid) {
+#pragma unroll
+    for (uint32_t i = 0; i < TileLoad<NTHR>::N; i++) *(uint4 *)(buf + tile_piece<NTHR>(i, tid)) = r.v[i];
+    s.g = st.u; s.l = buf; s.base = tb; s.len = r.avail;
     __syncthreads();
+}
+template <uint32_t NTHR> __device__ __forceinline__ void tile_stage(const BamStream &st, uint64_t tb, uint8_t *buf, LSrc &s, int tid) {
+    TileLoad<NTHR> r; tile_load<NTHR>(st, tb, r, tid); tile_store<NTHR>(st, tb, r, buf, s, tid);
 }
 
 // One wave per tile: speculate the first record start (64 candidates per step), walk the chain.
@@ -263,7 +299,7 @@ bam_tile_scan(BamStream st, uint64_t start0, int64_t ntiles, TileOut out, uint16
     if (t >= ntiles) return;
     const uint64_t tb = (uint64_t)t * TL_TILE;
     uint64_t te = tb + TL_TILE; if (te > st.ulen) te = st.ulen;
-    LSrc s; tile_stage(st, tb, buf, s, lane);
+    LSrc s; tile_stage<64>(st, tb, buf, s, lane);
     PSrc ls; ls.l = buf; ls.base = tb;                        // valid for offsets inside the staged window only
     GSrc gs; gs.g = st.u;
     uint64_t first = NONE64;
@@ -472,31 +508,36 @@ bam_tile_unpack(BamStream st, BamDict dict, int64_t ntiles, TileOut out, const u
     __shared__ uint8_t rg_lb[RGL_BYTES];
     const int lane = threadIdx.x;
     const int64_t t = blockIdx.x;
-    if (t >= ntiles || (uint64_t)t > res[3]) return;
+    if (t >= ntiles) return;
+    const uint64_t tb = (uint64_t)t * TL_TILE;
+    // The tile's loads go out first (their addresses need t and ulen only), then the loads of the per-tile tables, all of them in front of
+    // the first test: one wait instead of one dependent round trip per early return.  Every table holds an entry for every t < ntiles, so
+    // reading ahead of the tests is in bounds; a tile that returns early has loaded for nothing.
+    TileLoad<64> tl; tile_load<64>(st, tb, tl, lane);
+    uint64_t t_last = res[3], nrows_dev = res[0], first = out.first[t], recs_first = tile_recs_first[t];
+    uint32_t n = out.count[t], row0 = rowbase[t];
+    TL_LOADED_HERE6(t_last, nrows_dev, first, recs_first, n, row0);
+    if ((uint64_t)t > t_last) return;
     // nrows < 0: the host has not seen the row count yet (the batch runs without a round trip in between): it is res[0], and the row arrays
     // hold -nrows - 1 rows (sized from the previous batches); a batch that needs more raises TR_F_ROWS in res[14] and writes nothing
     if (nrows < 0) {
-        const int64_t cap = -nrows - 1; nrows = (int64_t)res[0];
+        const int64_t cap = -nrows - 1; nrows = (int64_t)nrows_dev;
         if (nrows > cap) { if (t == 0 && lane == 0) atomicOr((unsigned long long *)res + 14, TR_F_ROWS); return; }
     }
-    const uint64_t first = out.first[t];
-    const uint32_t n = out.count[t];
     if (first == NONE64 || n == 0) return;
-    const uint32_t row0 = rowbase[t];
     if ((int64_t)row0 >= nrows) return;
-    const uint64_t tb = (uint64_t)t * TL_TILE;
     const bool dict_lds = st.want_rg && dict.n_rg > 0 && dict.n_rg <= RGL_N && dict.n_bytes <= RGL_BYTES;
-    if (dict_lds) {                                             // (visible behind tile_stage's barrier)
+    if (dict_lds) {                                             // (visible behind tile_store's barrier)
         for (int k = lane; k <= dict.n_rg; k += 64) rg_lo[k] = dict.rg_off[k];
         for (int k = lane; k < dict.n_bytes; k += 64) rg_lb[k] = dict.rg_bytes[k];
     }
     DictG dg; dg.off = dict.rg_off; dg.bytes = dict.rg_bytes; dg.n = dict.n_rg;
     DictL dl; dl.off = rg_lo; dl.bytes = rg_lb; dl.n = dict.n_rg;
-    LSrc s; tile_stage(st, tb, buf, s, lane);
+    LSrc s; tile_store<64>(st, tb, tl, buf, s, lane);
     PSrc ls; ls.l = buf; ls.base = tb;
     WSrc ws; ws.l = buf; ws.base = tb; ws.len = s.len;
     GSrc gs; gs.g = st.u;
-    if (tile_recs_first[t] == first) {
+    if (recs_first == first) {
         // record starts left by bam_tile_scan's walk from this same `first` (one coalesced load instead of a serial chain of hops)
         for (uint32_t k = lane; k < n && k < TL_RECS; k += 64) recs[k] = (uint32_t)(tb + tile_recs[(size_t)t * TL_RECS + k]);
     } else {   // the tile was re-walked by a repair round: walk again (the chain was validated by the scan / fix kernels)
@@ -627,21 +668,26 @@ bam_tile_strings(BamStream st, int64_t ntiles, TileOut out, const uint32_t *rowb
     const int tid = threadIdx.x, lane = tid & 63;
     const bool w0 = tid < 64;
     const int64_t t = blockIdx.x;
-    if (t >= ntiles || (uint64_t)t > res[3]) return;
+    if (t >= ntiles) return;
+    const uint64_t tb = (uint64_t)t * TL_TILE;
+    // as in bam_tile_unpack: the tile's loads first, the tables' loads together, the early returns behind one wait
+    TileLoad<TS_THREADS> tl; tile_load<TS_THREADS>(st, tb, tl, tid);
+    uint64_t t_last = res[3], rflags = res[14], nrows_dev = res[0], first = out.first[t];
+    uint32_t n = out.count[t], rowb = rowbase[t];
+    TL_LOADED_HERE6(t_last, rflags, nrows_dev, first, n, rowb);
+    const int64_t row0 = rowb;
+    if ((uint64_t)t > t_last) return;
     if (nrows_all < 0) {          // the row count is on the device (see bam_tile_unpack); rows_guard has said whether everything fits
-        if (res[14] & (TR_F_ROWS | TR_F_HEAP)) return;
-        nrows_all = nrows = (int64_t)res[0];
+        if (rflags & (TR_F_ROWS | TR_F_HEAP)) return;
+        nrows_all = nrows = (int64_t)nrows_dev;
     }
-    const uint32_t n = out.count[t];
-    if (out.first[t] == NONE64 || n == 0) return;
-    const int64_t row0 = rowbase[t];
+    if (first == NONE64 || n == 0) return;
     if (row0 >= nrows_all) return;
     int64_t row1 = row0 + n; if (row1 > nrows_all) row1 = nrows_all;
     int64_t d0 = row_map ? (int64_t)row_map[row0] : row0, d1 = row_map ? (int64_t)row_map[row1] : row1;
     if (d1 > nrows) d1 = nrows;
     if (d0 >= d1) return;
-    const uint64_t tb = (uint64_t)t * TL_TILE;
-    // the first row group's offsets are requested before the tile is staged: both HBM round trips overlap
+    // the first row group's offsets are requested before the tile's loads are waited for: both HBM round trips overlap
     struct RowIn { uint32_t o, len_seq, len_qn, rl, rg_rel, ne, cig_rel, off_qn, off_rg, off_cig, off_seq, off_qual; };
     auto row_in = [&](int64_t r) {
         RowIn q; q.o = rec_off[r];
@@ -651,7 +697,7 @@ bam_tile_strings(BamStream st, int64_t ntiles, TileOut out, const uint32_t *rowb
     };
     RowIn ri; memset(&ri, 0, sizeof(ri));
     if (w0) ri = row_in(d0 + lane < d1 ? d0 + lane : d0);
-    LSrc ss; tile_stage(st, tb, buf, ss, tid, TS_THREADS);
+    LSrc ss; tile_store<TS_THREADS>(st, tb, tl, buf, ss, tid);
     WSrc ws; ws.l = buf; ws.base = tb; ws.len = ss.len;
     GSrc gs; gs.g = st.u;
 
@@ -683,6 +729,14 @@ bam_tile_strings(BamStream st, int64_t ntiles, TileOut out, const uint32_t *rowb
             for (uint32_t k = 0; k < nch; k++) cmap[c0 + k] = (uint8_t)lane;
         }
         __syncthreads();
+        // One explicit vmcnt(0) here: wave 0 has just waited for its row loads and wave 1 has none in flight, so it costs nothing on the first
+        // row group.  Without it the compiler cannot prove that no load is pending on the registers the chunk loop reuses, and puts
+        // `s_waitcnt vmcnt(0)` in front of the tile reads of the SEQ part, of the QUAL part and of the QNAME / RG reads below -- on gfx9 that
+        // also waits for every heap store in flight, about five store drains per three chunk iterations (TS_NO_DRAIN_WAIT builds
+        // the kernel without it for the A/B run).
+#ifndef TS_NO_DRAIN_WAIT
+        __builtin_amdgcn_s_waitcnt(0x0f70);                       // vmcnt(0), expcnt and lgkmcnt left alone
+#endif
         const uint32_t T = sT;
         // ---- SEQ / QUAL by chunk, both waves ----
         for (uint32_t cb = 0; cb < T; cb += TS_THREADS) {

@@ -80,7 +80,7 @@ bcf_tile_scan(BcfStream st, uint64_t start0, int64_t ntiles, TileOut out, uint64
     const uint64_t tb = (uint64_t)t * TL_TILE;
     uint64_t te = tb + TL_TILE; if (te > st.ulen) te = st.ulen;
     BamStream bs; bs.u = st.u; bs.ulen = st.ulen; bs.n_ref = 0; bs.final_batch = st.final_batch;
-    LSrc s; tile_stage(bs, tb, buf, s, lane);
+    LSrc s; tile_stage<64>(bs, tb, buf, s, lane);
     PSrc ls; ls.l = buf; ls.base = tb;
     GSrc gs; gs.g = st.u;
     uint64_t first = NONE64;

@@ -208,6 +208,9 @@ def lib():
         L.dhts_debug_fastq_records.restype = C.c_int64
         L.dhts_debug_fastq_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64)]
         L.dhts_debug_tile_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        if hasattr(L, "dhts_debug_tile_scan"):            # (absent from a DHTS_LIB variant built from older sources)
+            L.dhts_debug_tile_scan.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int64]
+            L.dhts_debug_tile_scan.restype = C.c_int64
         L.dhts_bam_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dhts_bam_set_block_range.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int]
         L.dhts_shard_cut.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -436,6 +439,17 @@ class Context:
         out = (C.c_uint64 * 8)()
         self._chk(self.L.dhts_debug_tile_stats(self.h, out))
         return {k: int(out[i]) for i, k in enumerate(self.TILE_STATS)}
+
+    def debug_tile_scan(self, kernel, ulen):
+        """one tile-scan kernel alone ("wave" or "lanes") over the inflated batch the context holds (`ulen` bytes or fewer), before any
+        repair round: {first, end_next, count, err, recs_first: arrays per tile; recs: [ntiles, 256] record starts relative to the tile,
+        entries k >= min(count, 256) masked to 0xeeee} (include/duckhts_amd_debug.h: dhts_debug_tile_scan)"""
+        import numpy as np
+        cap = max(1, (int(ulen) + 8191) // 8192)
+        t = {"first": np.zeros(cap, np.uint64), "end_next": np.zeros(cap, np.uint64), "count": np.zeros(cap, np.uint32), "err": np.zeros(cap, np.int32),
+             "recs_first": np.zeros(cap, np.uint64), "recs": np.zeros((cap, 256), np.uint16)}
+        n = self._chk(self.L.dhts_debug_tile_scan(self.h, {"wave": 0, "lanes": 1}[kernel], *[t[k].ctypes.data for k in ("first", "end_next", "count", "err", "recs_first", "recs")], cap))
+        return {k: v[:n] for k, v in t.items()}
 
     def debug_fastq_records(self):
         """the BAM records the device encoder made of the last FASTQ / FASTA batch: (bytes, number of records)"""

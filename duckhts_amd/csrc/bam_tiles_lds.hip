@@ -407,6 +407,131 @@ bam_tile_scan(BamStream st, uint64_t start0, int64_t ntiles, TileOut out, uint16
     for (uint32_t k = lane; k < cnt && k < TL_RECS; k += 64) tile_recs[(size_t)t * TL_RECS + k] = rl[k];
 }
 
+// ---- bam_tile_scan, one LANE per tile (tiles t >= 1), no LDS --------------------------------------------------------------
+// The wave form above stages 9 KiB per tile and then walks the chain wave-uniformly: 63 of 64 lanes idle behind ~1,000 scalar instructions
+// and ~77 dependent LDS round trips.  What the result needs is the bytes in front of the first record and one block_size word per record.
+// Here a lane reads its tile's 128-byte lines in order (eight 16-byte loads in flight, into statically indexed registers, never a line
+// twice), drops nearly every candidate offset of a line with a branch-free PREFILTER and runs the full filter -- rec_check_t<GSrc>,
+// three deep, the wave form's rule -- on the survivors only; then it walks block_size words straight from HBM.
+//
+// The prefilter is made of conjuncts of rec_check_t(full = false) == REC_OK alone: block_size >= 32, tid and mtid in [-1, n_ref),
+// l_seq >= 0, l_qname >= 1.  A candidate it drops cannot pass the filter; survivors are tested in ascending order; so the offset chosen is
+// the one the wave form chooses.  It may look at bytes behind the stream's end (padding, or a clamped piece): a survivor made of those is
+// turned down by the full filter, which tests the stream's length first.
+//
+// LS_X(D, q, r): the dword at byte 4q + r of the window D (dwords of the line and of the next line's first 28 bytes); q, r constants
+// after unrolling, so this is one v_alignbit (none for r = 0).
+#define LS_LINE 128u
+// (written as the builtin for the device: the compiler turns the plain 64-bit shift of two neighbouring array elements into an 8-byte load of
+//  the array, which then lives in scratch memory)
+#ifdef __HIP_DEVICE_COMPILE__
+#define LS_X(D, q, r) ((r) == 0 ? (D)[(q)] : (uint32_t)__builtin_amdgcn_alignbyte((D)[(q) + 1], (D)[(q)], (r)))
+#else
+#define LS_X(D, q, r) ((r) == 0 ? (D)[(q)] : (uint32_t)(((((uint64_t)(D)[(q) + 1]) << 32) | (uint64_t)(D)[(q)]) >> (8 * (r))))
+#endif
+// the line's eight pieces; a piece at or past the stream's padded end is read from the tile's first bytes instead (as tile_load does)
+__device__ __forceinline__ void lane_line_load(const uint8_t *src, uint32_t k0, uint32_t pad, uint4 (&v)[8]) {
+#pragma unroll
+    for (uint32_t i = 0; i < 8; i++) { const uint32_t k = k0 + 16u * i; v[i] = *(const uint4 *)(src + (k < pad ? k : 0u)); }
+}
+// Survivors of the line whose 32 dwords are D[0..31] (D[32..38]: the next 28 bytes): S[r] bit q = candidate at byte 4q + r passes.
+// Per byte phase r the 38 dwords X(q) are each classified once in their four possible roles (block_size, a reference id, l_seq, the
+// word whose low byte is l_qname) into bit masks over q; a candidate's five tests are then one AND of shifted masks.  The last candidate
+// (q = 31, r = 3) reads mtid from X(37), bytes 151..154 of the window: 39 dwords.
+__device__ __forceinline__ void lane_prefilter(const uint32_t (&D)[39], uint32_t n_ref1, uint32_t (&S)[4]) {
+#pragma unroll
+    for (uint32_t r = 0; r < 4; r++) {
+        uint64_t mb = 0, mr = 0, ms = 0, mq = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 38; q++) {
+            const uint32_t x = LS_X(D, q, r);
+            if (q < 32) mb |= (uint64_t)((int32_t)x >= 32) << q;                       // block_size >= 32
+            if (q >= 1) mr |= (uint64_t)(x + 1u < n_ref1) << q;                          // -1 <= id < n_ref   (n_ref1 = n_ref + 1)
+            if (q >= 3 && q < 35) mq |= (uint64_t)((x & 0xffu) != 0u) << q;              // l_qname >= 1
+            if (q >= 5 && q < 37) ms |= (uint64_t)((int32_t)x >= 0) << q;                // l_seq >= 0
+        }
+        S[r] = (uint32_t)(mb & (mr >> 1) & (mq >> 3) & (ms >> 5) & (mr >> 6));
+    }
+}
+// the speculation rule of bam_tile_scan for one candidate, out of HBM
+__device__ __forceinline__ bool lane_spec3(const BamStream &st, const GSrc &gs, uint64_t o) {
+    RecInfo r;
+    if (rec_check_t(st, gs, o, r, false) != REC_OK) return false;
+    uint64_t o2 = o + 4ull + r.block_len;
+    for (int k = 0; k < 2; k++) {
+        RecInfo r2;
+        const int rc = rec_check_t(st, gs, o2, r2, false);
+        if (rc == REC_INVALID) return false;
+        if (rc == REC_INCOMPLETE) break;
+        o2 += 4ull + r2.block_len;
+    }
+    return true;
+}
+// what one lane does for tile t >= 1: writes exactly what bam_tile_scan writes for the tile
+__device__ __forceinline__ void tile_scan_lane(const BamStream &st, int64_t t, const TileOut &out, uint16_t *tile_recs, uint64_t *tile_recs_first) {
+    const uint64_t tb = (uint64_t)t * TL_TILE;
+    if (tb >= st.ulen) return;                                 // (no such tile: ntiles = ceil(ulen / TL_TILE))
+    const uint64_t left64 = st.ulen - tb;
+    const uint32_t left = left64 > 0xffffffffull ? 0xffffffffu : (uint32_t)left64;      // bytes of the stream from the tile's first byte on
+    const uint32_t lim = left < TL_TILE ? left : TL_TILE;      // te - tb
+    const uint32_t avail = left < TL_TILE + TL_HALO ? left : TL_TILE + TL_HALO;
+    const uint32_t pad = (avail + 15u) & ~15u;                 // the inflated buffer carries >= 256 bytes of padding
+    const uint8_t *src = st.u + tb;
+    GSrc gs; gs.g = st.u;
+    const uint32_t n_ref1 = (uint32_t)st.n_ref + 1u;
+    uint32_t first = 0xffffffffu;                              // relative to the tile
+    uint4 cur[8], nxt[8];
+    lane_line_load(src, 0u, pad, cur);
+    for (uint32_t lb = 0; lb < lim && first == 0xffffffffu; lb += LS_LINE) {
+        lane_line_load(src, lb + LS_LINE, pad, nxt);           // (the last line's successor is the halo's first line)
+        uint32_t D[39], S[4];
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++) { D[4 * i] = cur[i].x; D[4 * i + 1] = cur[i].y; D[4 * i + 2] = cur[i].z; D[4 * i + 3] = cur[i].w; }
+        D[32] = nxt[0].x; D[33] = nxt[0].y; D[34] = nxt[0].z; D[35] = nxt[0].w; D[36] = nxt[1].x; D[37] = nxt[1].y; D[38] = nxt[1].z;
+        lane_prefilter(D, n_ref1, S);
+        uint32_t any = S[0] | S[1] | S[2] | S[3];
+        while (any != 0u && first == 0xffffffffu) {            // ascending: dword q, then byte phase r
+            const uint32_t q = (uint32_t)__ffs((int)any) - 1u;
+            any &= any - 1u;
+            uint32_t ph = ((S[0] >> q) & 1u) | (((S[1] >> q) & 1u) << 1) | (((S[2] >> q) & 1u) << 2) | (((S[3] >> q) & 1u) << 3);   // (S stays in registers: constant indices only)
+            while (ph != 0u && first == 0xffffffffu) {
+                const uint32_t rel = lb + 4u * q + ((uint32_t)__ffs((int)ph) - 1u);
+                ph &= ph - 1u;
+                // (rel < lim: the search is over [tb, te), as in the wave kernel.  lim < TL_TILE only where the stream ends inside the tile, and a
+                //  candidate at or past the end gets "incomplete" from rec_check_t anyway: the test is for the reader, and saves those calls)
+                if (rel < lim && lane_spec3(st, gs, tb + rel)) first = rel;
+            }
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++) cur[i] = nxt[i];
+    }
+    // the light walk of bam_tile_scan's default build (block_size only; same order of outcomes).  Its `general` branch is entered only when
+    // fewer than four bytes of the stream are left, where rec_hop answers "incomplete" at once: one path here.
+    uint64_t en = NONE64; uint32_t cnt = 0; int err = 0;
+    if (first != 0xffffffffu) {
+        uint32_t rel = first;
+        while (rel < lim) {
+            if (left - rel < 4u) { if (st.final_batch) err = 1; break; }                  // incomplete
+            const int32_t b = (int32_t)ldu32(src + rel);
+            if (b < 32) { err = 1; break; }
+            if (left - rel - 4u < (uint32_t)b) { if (st.final_batch) err = 1; break; }     // the record runs past the stream: incomplete
+            if (cnt < TL_RECS) tile_recs[(size_t)t * TL_RECS + cnt] = (uint16_t)rel;
+            cnt++; rel += 4u + (uint32_t)b;
+        }
+        en = tb + rel;
+    }
+    const uint64_t f = first != 0xffffffffu ? tb + first : NONE64;
+    out.first[t] = f; out.end_next[t] = en; out.count[t] = cnt; out.err[t] = err;
+    tile_recs_first[t] = f;
+}
+// the kernel: lane i of the grid takes tile 1 + i   (tools/hostsim/run_scan.sh cuts the per-lane text above out for a host build, up to this line)
+extern "C" __global__ void __launch_bounds__(64)
+bam_tile_scan_lanes(BamStream st, int64_t ntiles, TileOut out, uint16_t *tile_recs, uint64_t *tile_recs_first) {
+    const int64_t t = 1 + (int64_t)blockIdx.x * 64 + threadIdx.x;                         // tile 0 stays with bam_tile_scan
+    if (t >= ntiles) return;
+    tile_scan_lane(st, t, out, tile_recs, tile_recs_first);
+}
+
 // The retry of a speculated shard start: tile 0's search of bam_tile_scan (same filter, three deep, first hit from `from` on) as one wave
 // over global memory, passing over the members of failed chains.  *out = the candidate or NONE64.
 extern "C" __global__ void __launch_bounds__(64)

@@ -290,7 +290,7 @@ struct dhts_ctx {
     int64_t pool_per_block = 65536 + 4096;         // room per block in the packed scratch (a retry after DHTS_BLK_ERR_SCRATCH uses the full 152 KiB)
     DevBuf sg_cnt, sg_base, sg_cand, sg_hits;      // block discovery scratch
     // index writer
-    std::vector<uint8_t> built_index; DevBuf ix_end; BamStream last_stream;   // last_stream: the inflated buffer of the latest batch
+    std::vector<uint8_t> built_index; DevBuf ix_end; BamStream last_stream{};   // last_stream: the inflated buffer of the latest batch
     // interval overlap join
     bool ov_active = false; int64_t ov_n = 0;
     DevBuf ov_beg, ov_end, ov_pmax, ov_bmax, ov_id, ov_first, ov_cnt, ov_off, ov_ids;
@@ -495,6 +495,7 @@ static void reset_file_state(dhts_ctx *c) {
     c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->bins.open = false; c->cov.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->range_cut = false; c->last_batch_rows = -1; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     memset(c->tile_stats, 0, sizeof(c->tile_stats));
+    c->last_stream = BamStream{};                             // (dhts_debug_tile_scan and the passes that read the latest batch refuse until a batch of the new file has been read)
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
 }
 

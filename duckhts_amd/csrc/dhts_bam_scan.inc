@@ -286,6 +286,62 @@ extern "C" int dhts_debug_tile_stats(dhts_ctx *c, uint64_t out[8]) {
 static bool rows_deferred_on() { static const bool on = !(getenv("DHTS_ROWS") && !strcmp(getenv("DHTS_ROWS"), "sync")); return on; }
 static bool rows_fused_on() { static const bool on = getenv("DHTS_ROWS") && !strcmp(getenv("DHTS_ROWS"), "fused"); return on; }
 static int rows_exp() { static const int e = getenv("DHTS_ROWS_EXP") ? (atoi(getenv("DHTS_ROWS_EXP")) & 2) : 0; return e; }   // timing experiments (tools/dbg/time_rows.py)
+// DHTS_TILE_SCAN=wave|lanes|auto: which kernel speculates and walks tiles t >= 1 (tile 0 is always bam_tile_scan's: it carries start0, spec_from
+// and a search that may run through the whole batch).  lanes = bam_tile_scan_lanes, one lane per tile straight from HBM; wave = one wave per
+// tile out of LDS.  auto (the default) takes the lane kernel from TILE_SCAN_LANES_MIN tiles on: a lane's tile is a chain of ~30 dependent
+// HBM reads, which only a grid with many waves per CU hides.  Measured at 256 / 1,024 / 4,096 / 19,813 blocks per batch
+// (tools/dbg/time_tile_scan.py, DESIGN §5h): the tile pass takes 0.030 / 0.051 / 0.139 / 0.606 ms with the wave kernel and 0.060 / 0.063 /
+// 0.090 / 0.303 ms with the lane kernel; 4,096 full blocks (32,640 tiles) is the smallest size measured from which the lane kernel wins.
+// Read per batch, so that one process can run both (the kernels are each other's cross-check).
+#define TILE_SCAN_LANES_MIN 32640
+static int tile_scan_mode() {                                 // 0 auto, 1 wave, 2 lanes; a value that is none of the three is reported once and read as auto
+    const char *e = getenv("DHTS_TILE_SCAN");
+    if (!e || !strcmp(e, "auto")) return 0;
+    if (!strcmp(e, "wave")) return 1;
+    if (!strcmp(e, "lanes")) return 2;
+    static std::atomic<bool> warned{false};
+    if (!warned.exchange(true)) fprintf(stderr, "[dhts] DHTS_TILE_SCAN=%s is not wave, lanes or auto: using auto\n", e);
+    return 0;
+}
+static bool tile_scan_lanes_on(int64_t ntiles) { const int m = tile_scan_mode(); return m == 2 || (m == 0 && ntiles >= TILE_SCAN_LANES_MIN); }
+// the tile pass's first kernel: every tile's speculated first record, chain exit, count, error flag and record list
+static void tile_scan_launch(dhts_ctx *c, bool lanes, const BamStream &st, uint64_t start0, int64_t ntiles, const TileOut &to, uint16_t *recs, uint64_t *recs_first, uint64_t spec_from) {
+    if (lanes && ntiles > 1) {
+        hipLaunchKernelGGL(bam_tile_scan, dim3(1), dim3(64), 0, c->stream, st, start0, ntiles, to, recs, recs_first, spec_from);
+        hipLaunchKernelGGL(bam_tile_scan_lanes, dim3((unsigned)((ntiles - 1 + 63) / 64)), dim3(64), 0, c->stream, st, ntiles, to, recs, recs_first);
+    } else
+        hipLaunchKernelGGL(bam_tile_scan, dim3((unsigned)ntiles), dim3(64), 0, c->stream, st, start0, ntiles, to, recs, recs_first, spec_from);
+}
+// One scan kernel alone over the inflated batch the context holds (c->last_stream), its six tables copied to the host before any repair
+// round: kernel 0 = bam_tile_scan on every tile, 1 = bam_tile_scan_lanes (tile 0 by bam_tile_scan).  Tile 0 starts at offset 0 where that
+// is a record boundary, so compare tiles t >= 1.  recs holds TL_RECS entries per tile.  Returns the number of tiles, or -1.
+extern "C" int64_t dhts_debug_tile_scan(dhts_ctx *c, int kernel, uint64_t *first, uint64_t *end_next, uint32_t *count, int32_t *err, uint64_t *recs_first,
+                                        uint16_t *recs, int64_t ntiles_cap) {
+    if (!c) return -1;
+    if (kernel != 0 && kernel != 1) return fail(c, "dhts_debug_tile_scan: kernel is 0 (wave) or 1 (lanes)");
+    const BamStream st = c->last_stream;
+    if (!st.u) return fail(c, "dhts_debug_tile_scan: no batch has been read");
+    HIPCHK(c, hipSetDevice(c->device));
+    int64_t ntiles = (int64_t)((st.ulen + TILE_BYTES - 1) / TILE_BYTES); if (ntiles < 1) ntiles = 1;
+    if (ntiles > ntiles_cap) return fail(c, "dhts_debug_tile_scan: the tables are too small");
+    DevBuf d_first, d_end, d_count, d_err, d_rf, d_recs;
+    ENSURE(c, d_first, ntiles * 8); ENSURE(c, d_end, ntiles * 8); ENSURE(c, d_count, ntiles * 4); ENSURE(c, d_err, ntiles * 4);
+    ENSURE(c, d_rf, ntiles * 8 + 64); ENSURE(c, d_recs, (size_t)ntiles * TL_RECS * 2 + 64);
+    HIPCHK(c, hipMemsetAsync(d_first.p, 0xee, ntiles * 8, c->stream)); HIPCHK(c, hipMemsetAsync(d_end.p, 0xee, ntiles * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_count.p, 0xee, ntiles * 4, c->stream)); HIPCHK(c, hipMemsetAsync(d_err.p, 0xee, ntiles * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_rf.p, 0xee, ntiles * 8, c->stream)); HIPCHK(c, hipMemsetAsync(d_recs.p, 0xee, (size_t)ntiles * TL_RECS * 2, c->stream));
+    TileOut to; to.first = (uint64_t *)d_first.p; to.end_next = (uint64_t *)d_end.p; to.count = (uint32_t *)d_count.p; to.err = (int32_t *)d_err.p;
+    tile_scan_launch(c, kernel == 1, st, 0, ntiles, to, (uint16_t *)d_recs.p, (uint64_t *)d_rf.p, 0);
+    HIPCHK(c, hipGetLastError());
+    if (first) HIPCHK(c, hipMemcpyAsync(first, d_first.p, ntiles * 8, hipMemcpyDeviceToHost, c->stream));
+    if (end_next) HIPCHK(c, hipMemcpyAsync(end_next, d_end.p, ntiles * 8, hipMemcpyDeviceToHost, c->stream));
+    if (count) HIPCHK(c, hipMemcpyAsync(count, d_count.p, ntiles * 4, hipMemcpyDeviceToHost, c->stream));
+    if (err) HIPCHK(c, hipMemcpyAsync(err, d_err.p, ntiles * 4, hipMemcpyDeviceToHost, c->stream));
+    if (recs_first) HIPCHK(c, hipMemcpyAsync(recs_first, d_rf.p, ntiles * 8, hipMemcpyDeviceToHost, c->stream));
+    if (recs) HIPCHK(c, hipMemcpyAsync(recs, d_recs.p, (size_t)ntiles * TL_RECS * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ntiles;
+}
 struct RowsQueued { BamCols bc; RowsStr so; };
 // Queues the row pass of the batch behind its tile pass: row arrays and string arenas are sized from the hints the previous batches left
 // (or from the batch's inflated size) and guarded on the device; the pass reports what it needed in res[8..14].
@@ -474,7 +530,7 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
         uint32_t nfh[2] = {0, 0}, bst[4] = {NONE32, 0, NONE32, 0};
         {
             KTimer tm(c, DHTS_K_TILES);
-            hipLaunchKernelGGL(bam_tile_scan, dim3((unsigned)ntiles), dim3(64), 0, c->stream, st, start_eff, ntiles, to, (uint16_t *)c->t_recs.p, (uint64_t *)c->t_recs_first.p, spec_from);
+            tile_scan_launch(c, tile_scan_lanes_on(ntiles), st, start_eff, ntiles, to, (uint16_t *)c->t_recs.p, (uint64_t *)c->t_recs_first.p, spec_from);
             // two repair rounds are queued unconditionally (a 30x BAM converges in two; a round that finds nothing to repair copies the table)
             uint32_t *nf = (uint32_t *)c->d_nfixed.p;
             (void)hipMemsetAsync(nf, 0, 8, c->stream);

@@ -457,6 +457,7 @@ int dhts_bam_rewind(dhts_ctx *c) {
     if (!c->wins.empty()) enter_window(c, 0);
     c->next_block = c->shard_b0; c->carry_len = 0; c->stream_done = c->rg_empty_window; c->first_batch = true; c->ucur = 0;
     c->huff_b0 = c->huff_nb = 0;            // a new pass redoes phase A (nothing is cached across scans)
+    c->last_stream = BamStream{};           // no batch of the new pass has been read yet
     memset(c->tile_stats, 0, sizeof(c->tile_stats));
     skip_header_blocks(c);
     return 0;

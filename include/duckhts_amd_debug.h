@@ -48,6 +48,12 @@ int dhts_debug_deflate_codes(dhts_ctx *, const uint32_t *counts, uint32_t nsym, 
  * records the full validation refused (bam_validate_rows / bcf_rec_check); out[5] batches where no candidate was left and the first
  * attempt's result was restored; out[6], out[7] zero. */
 int dhts_debug_tile_stats(dhts_ctx *, uint64_t out[8]);
+/* tests, tools/dbg: one tile-scan kernel alone over the inflated batch the context holds (the latest dhts_bam_next_batch), before any repair
+ * round: kernel 0 = bam_tile_scan (one wave per tile), 1 = bam_tile_scan_lanes (one lane per tile; tile 0 by bam_tile_scan).  Tile 0 is
+ * started at offset 0.  Host tables of ntiles_cap entries each, recs of ntiles_cap * 256 (entries k < min(count, 256) of a tile are
+ * written; the rest keep 0xeeee).  Any table may be NULL.  Returns the number of tiles, or -1. */
+int64_t dhts_debug_tile_scan(dhts_ctx *, int kernel, uint64_t *first, uint64_t *end_next, uint32_t *count, int32_t *err, uint64_t *recs_first,
+                             uint16_t *recs, int64_t ntiles_cap);
 /* (diagnostic builds only: -DDHTS_DIAG dhts_debug_diag, -DHW_DIAG dhts_debug_hw_diag, -DTR_DIAG dhts_debug_tr_diag: per-phase cycle counters) */
 int dhts_debug_diag(dhts_ctx *, unsigned long long *out8);
 int dhts_debug_hw_diag(dhts_ctx *, unsigned long long *out16, int reset);

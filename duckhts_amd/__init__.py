@@ -96,6 +96,16 @@ class BedcovStats(C.Structure):
                 ("n_bed_rows", C.c_uint64), ("n_breakpoints", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CoverageParams(C.Structure):
+    _fields_ = [("min_read_len", C.c_int64), ("min_depth", C.c_int64), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32),
+                ("require_flags", C.c_int32), ("exclude_flags", C.c_int32), ("include_flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CoverageStats(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_flag_filtered", C.c_uint64), ("n_unplaced", C.c_uint64), ("n_short", C.c_uint64), ("n_low_mapq", C.c_uint64),
+                ("n_outside", C.c_uint64), ("n_counted", C.c_uint64), ("n_target_rows", C.c_uint64), ("table_bytes", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TabixMap(C.Structure):
     _fields_ = [("pair_off", C.c_void_p), ("valid", C.c_void_p), ("n_pairs", C.c_uint64), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p), ("key_nbytes", C.c_uint64),
                 ("val_off", C.c_void_p), ("val_bytes", C.c_void_p), ("val_nbytes", C.c_uint64)]
@@ -152,6 +162,9 @@ BINS_COLUMNS = ["chrom", "start", "end", "bin_id", "count_total", "count_fwd", "
 BINS_DEDUP = {"none": 0, "adjacent": 1}
 BEDCOV_COLUMNS = ["chrom", "start", "end", "name", "score", "strand", "bases_covered", "read_count"]
 BEDCOV_INT_COLUMNS = (1, 2, 6, 7)
+COVERAGE_COLUMNS = ["chrom", "start", "end", "numreads", "covbases", "coverage", "meandepth", "meanbaseq", "meanmapq", "sum_depth", "sum_baseq", "sum_mapq"]
+COVERAGE_DOUBLE_COLUMNS = (5, 6, 7, 8)
+COVERAGE_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4)              # FLAG, RNAME, POS, MAPQ: no string column (CIGAR and QUAL are read in their binary form)
 BEDCOV_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4)                # FLAG, RNAME, POS, MAPQ: no string column (the CIGARs are read in their binary form)
 BINS_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 7)        # FLAG, RNAME, POS, MAPQ, PNEXT: no string column
 
@@ -172,6 +185,7 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_nuc_open_region", "dhts_nuc_open", "dhts_nuc_set_region", "dhts_nuc_set_projection", "dhts_nuc_next_bins", "dhts_nuc_next_bed", "dhts_nuc_intervals", "dhts_nuc_batch_host_bytes", "dhts_nuc_batch_fetch",
            "dhts_bam_bins_open", "dhts_bam_bins_accumulate", "dhts_bam_bins_scan", "dhts_bam_bins_stats", "dhts_bam_bins_next", "dhts_bam_bins_batch_host_bytes", "dhts_bam_bins_batch_fetch",
            "dhts_bam_bedcov_open", "dhts_bam_bedcov_accumulate", "dhts_bam_bedcov_scan", "dhts_bam_bedcov_stats", "dhts_bam_bedcov_next", "dhts_bam_bedcov_batch_host_bytes", "dhts_bam_bedcov_batch_fetch",
+           "dhts_bam_coverage_open", "dhts_bam_coverage_accumulate", "dhts_bam_coverage_scan", "dhts_bam_coverage_stats", "dhts_bam_coverage_next", "dhts_bam_coverage_batch_host_bytes", "dhts_bam_coverage_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
            "dhts_udf_upload", "dhts_udf_apply", "dhts_udf_result_host_bytes", "dhts_udf_fetch", "dhts_udf_seq_kmers", "dhts_udf_kmers_host_bytes", "dhts_udf_kmers_fetch"]
@@ -285,6 +299,16 @@ def lib():
         L.dhts_bam_bedcov_batch_host_bytes.restype = C.c_uint64
         L.dhts_bam_bedcov_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_bam_bedcov_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_bam_coverage_open.argtypes = [C.c_void_p, C.POINTER(CoverageParams)]
+        L.dhts_bam_coverage_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
+        L.dhts_bam_coverage_scan.argtypes = [C.c_void_p, C.c_int64]
+        L.dhts_bam_coverage_stats.argtypes = [C.c_void_p, C.POINTER(CoverageStats)]
+        L.dhts_bam_coverage_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
+        L.dhts_bam_coverage_batch_host_bytes.restype = C.c_uint64
+        L.dhts_bam_coverage_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
+        L.dhts_bam_coverage_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_debug_coverage_max_table_bytes.restype = None
+        L.dhts_debug_coverage_max_table_bytes.argtypes = [C.c_uint64]
         L.dhts_debug_bedcov_max_rows.restype = None
         L.dhts_debug_bedcov_max_rows.argtypes = [C.c_uint64]
         L.dhts_tabix_open.argtypes = [C.c_void_p, C.c_int]
@@ -772,6 +796,48 @@ class Context:
         out = {"n_rows": n}
         for i in range(b.n_cols):
             out[BINS_COLUMNS[host[i].col]] = np.ctypeslib.as_array(C.cast(host[i].fixed, C.POINTER(C.c_int64)), (n,)).copy() if n else np.zeros(0, np.int64)
+        return out, int(b.status)
+
+    # ---- bam_coverage (the batch has dhts_bed_batch's layout) ----
+    def bam_coverage_open(self, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0, min_depth=1):
+        """after bam_open and the optional set_regions / load_index: the target rows, the depth table and the counters, zeroed.  The
+        parameters are taken as given (the C ABI's rule)."""
+        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
+        p = CoverageParams(clip(min_read_len, 63), clip(min_depth, 63), clip(min_mapq, 31), clip(min_baseq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31), 0)
+        self._chk(self.L.dhts_bam_coverage_open(self.h, C.byref(p)))
+
+    def bam_coverage_accumulate(self, b):
+        """b: the batch next_batch returned last on this context"""
+        self._chk(self.L.dhts_bam_coverage_accumulate(self.h, C.byref(b)))
+
+    def bam_coverage_scan(self, max_blocks=0):
+        """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
+        rc = self.L.dhts_bam_coverage_scan(self.h, max_blocks)
+        if rc < 0:
+            msg = self.L.dhts_error(self.h).decode()
+            if self.bam_coverage_stats()["status"] == 0:                  # a call failed (a stream that ended on an error has set its status)
+                raise DhtsError(msg)
+        return rc
+
+    def bam_coverage_stats(self):
+        st = CoverageStats()
+        self._chk(self.L.dhts_bam_coverage_stats(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in CoverageStats._fields_ if k != "reserved"}
+
+    def bam_coverage_next(self, max_rows=0):
+        """the next rows of the result: ({"n_rows", column: int64 array (chrom = the contig's id), float64 for the four means}, status)"""
+        b = BedBatch()
+        self._chk(self.L.dhts_bam_coverage_next(self.h, max_rows, C.byref(b)))
+        need = int(self.L.dhts_bam_coverage_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        self._chk(self.L.dhts_bam_coverage_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
+        n = int(b.n_rows)
+        out = {"n_rows": n}
+        for i in range(b.n_cols):
+            dt = np.float64 if host[i].col in COVERAGE_DOUBLE_COLUMNS else np.int64
+            vals = np.ctypeslib.as_array(C.cast(host[i].fixed, C.POINTER(C.c_int64)), (n,)).copy() if n else np.zeros(0, np.int64)
+            out[COVERAGE_COLUMNS[host[i].col]] = vals.view(dt)
         return out, int(b.status)
 
     # ---- bam_bedcov (the batch has dhts_bed_batch's layout) ----
@@ -1906,6 +1972,42 @@ def bam_bedcov(src, bed, min_mapq=0, require_flags=0, exclude_flags=0x704, inclu
     finally:
         if bctx is not None:
             bctx.close()
+        ctx.close()
+
+
+def bam_coverage(src, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0x704, min_depth=1, region=None, index=None,
+                 device=0, max_blocks=0, max_rows=0):
+    """bam_coverage(path, region :=, index_path :=, min_read_len :=, min_mapq :=, min_baseq :=, include_flags :=, require_flags :=, exclude_flags :=,
+    min_depth :=): per contig, or per region given, what `samtools coverage` prints, accumulated on the device (the contract:
+    include/duckhts_amd.h).  {"n_rows", "chrom": list of bytes, "start", "end", "numreads", "covbases": int64 arrays, "coverage", "meandepth",
+    "meanbaseq", "meanmapq": float64 arrays, "sum_depth", "sum_baseq", "sum_mapq": int64 arrays, "stats": the step counters, "status": how the
+    stream ended}.  index: BAI / CSI bytes narrowing the scan of a region query."""
+    ctx = Context(device)
+    try:
+        ctx.open(src)
+        ctx.bgzf_index()
+        hdr = ctx.bam_open()
+        if region is not None:
+            if not ctx.set_regions(region):
+                raise DhtsError(f"No reads found for region(s): {region}")
+            if index is not None:
+                ctx.load_index(index)
+        ctx.bam_coverage_open(min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, min_depth)
+        status = ctx.bam_coverage_scan(max_blocks)
+        parts = []
+        while True:
+            cols, st = ctx.bam_coverage_next(max_rows)
+            parts.append(cols)
+            if st != 0:
+                break
+        out = {k: np.concatenate([p[k] for p in parts]) for k in COVERAGE_COLUMNS}
+        names = [n.encode() if isinstance(n, str) else bytes(n) for n in hdr["ref_names"]]
+        out["chrom"] = [names[t] for t in out["chrom"]]
+        out["n_rows"] = len(out["chrom"])
+        out["stats"] = {k: v for k, v in ctx.bam_coverage_stats().items() if k.startswith("n_") and k != "n_target_rows"}
+        out["status"] = status
+        return out
+    finally:
         ctx.close()
 
 

@@ -18,6 +18,7 @@
 #include "seq_udf.hip"
 #include "bam_bins.hip"
 #include "bam_bedcov.hip"
+#include "bam_coverage.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -216,6 +217,15 @@ struct BedcovState {
     uint64_t n_points = 0, n_bed = 0, row_next = 0; std::vector<dhts_col> out;
     DevBuf cnt, sums, partial, steps, base, X, ks, ke, step, rlen, nseg, bases, reads, ones;
 };
+// bam_coverage (bam_coverage.hip, dhts_bam_coverage.inc): the parameters, the target rows in the order they are answered in (o_k: a row's
+// index among the sorted non-empty rows, -1 for an empty one), the sorted rows on the device with their spans of the difference table, the
+// per-row words and the step counters, per-batch scratch, the per-tile values of a result, and the result's columns on the host
+struct CoverageState {
+    bool open = false, res_ready = false; dhts_coverage_params P; int32_t n_ref = 0, status = 0;
+    uint64_t n_sorted = 0, slots = 0, row_next = 0; std::vector<dhts_col> out;
+    std::vector<int32_t> o_tid; std::vector<int64_t> o_beg, o_end, o_k, h_cols[DHTS_COVERAGE_COL_COUNT];
+    DevBuf diff, words, steps, tid_first, rbeg, rend, rbase, tile_row, step, rlen, k0, k1, tsum, tcov, tdepth, res, ones, cols[DHTS_COVERAGE_COL_COUNT];
+};
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
 struct UdfState {
@@ -261,6 +271,7 @@ struct dhts_ctx {
     NucState nuc;
     BinsState bins;
     BedcovState cov;
+    CoverageState dep;
     UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
@@ -325,6 +336,8 @@ struct dhts_ctx {
     // region filter (row A11)
     bool rg_active = false, rg_all = false, rg_nocoor = false;
     std::vector<int64_t> rg_beg, rg_end; std::vector<uint32_t> rg_tid_first;
+    struct RegionGiven { int32_t tid; int64_t beg, end; std::string tok; };
+    std::vector<RegionGiven> rg_given;     // the regions that name a contig, as given: unmerged and in their order (bam_coverage answers one row each)
     DevBuf d_rg_beg, d_rg_end, d_rg_first, c_keep, c_rowmap;
     bool rg_empty_window = false;          // the index shows no chunk for the regions: the scan yields nothing
     // the chunk list of a region query (hts_itr_multi_bam / reg2intervals, hts.c:3597-3739, 3299-3354) as disjoint scan windows in file
@@ -492,7 +505,7 @@ static void stop_stager(dhts_ctx *c) {
 }
 static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
-    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->bins.open = false; c->cov.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
+    c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->bins.open = false; c->cov.open = false; c->dep.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->range_cut = false; c->last_batch_rows = -1; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
     memset(c->tile_stats, 0, sizeof(c->tile_stats));
     c->last_stream = BamStream{};                             // (dhts_debug_tile_scan and the passes that read the latest batch refuse until a batch of the new file has been read)
@@ -551,6 +564,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_fasta_nuc.inc"
 #include "dhts_bam_bins.inc"
 #include "dhts_bam_bedcov.inc"
+#include "dhts_bam_coverage.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

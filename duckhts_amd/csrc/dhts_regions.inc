@@ -75,7 +75,7 @@ int dhts_bam_set_regions(dhts_ctx *c, const char *regions) {
     if (c->fastq && regions && regions[0]) return fail(c, "read_bam: region queries on FASTQ/FASTA text are not supported (%s)", FASTQ_SEQ_ONLY);
     if (c->sam_text && regions && regions[0]) return fail(c, "read_bam: region queries on SAM text are not supported (%s; the reference needs a .tbi / .csi index for them)", SAM_SEQ_ONLY);
     HIPCHK(c, hipSetDevice(c->device));
-    c->rg_active = false; c->rg_all = false; c->rg_nocoor = false; c->rg_empty_window = false; c->rg_beg.clear(); c->rg_end.clear(); c->rg_tid_first.clear();
+    c->rg_active = false; c->rg_all = false; c->rg_nocoor = false; c->rg_empty_window = false; c->rg_beg.clear(); c->rg_end.clear(); c->rg_tid_first.clear(); c->rg_given.clear();
     c->wins.clear(); c->win_cur = 0; c->scan_end_uoff = ~0ull;
     c->scan_first_uoff = c->first_rec_uoff; c->shard_b0 = 0; c->shard_b1 = c->n_blocks; c->shard_rank = 0; c->shard_world = 1; c->range_cut = false;
     if (!regions || !*regions) return dhts_bam_rewind(c);
@@ -93,6 +93,7 @@ int dhts_bam_set_regions(dhts_ctx *c, const char *regions) {
         int tid; int64_t b, e;
         if (!parse_region_token(c->ref_name, tok, tid, b, e)) continue;
         per[tid].push_back({b, e}); usable++;
+        c->rg_given.push_back({(int32_t)tid, b, e, tok});
     }
     if (ntok == 0) return dhts_bam_rewind(c);               // a string of commas only: the reference's strtok split yields no region at all (bam_reader.c:319-345) => plain scan
     if (!usable) return 1;

@@ -632,6 +632,89 @@ int dhts_bam_bedcov_next(dhts_ctx *bam, dhts_ctx *bed, int64_t max_blocks, dhts_
 uint64_t dhts_bam_bedcov_batch_host_bytes(const dhts_bedcov_batch *b);
 int dhts_bam_bedcov_batch_fetch(dhts_ctx *bam, const dhts_bedcov_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- bam_coverage ----------------------------------------------------------------------------
+ * Per contig or region: numreads, covbases, coverage, meandepth, meanbaseq, meanmapq (what `samtools coverage` prints), accumulated on the
+ * device from the fixed-width columns, the binary CIGARs and the QUAL bytes a read_bam batch leaves in HBM: nothing but one row per contig
+ * leaves the device.  The reference has only a plan for it (.github/PLAN.md, Phase 10, 10.4 / 10.7.3; its SQL equivalent is read_bam with
+ * CIGAR and QUAL plus a per-base expansion), so this is the specification.
+ *   Input: the rows of the context's read_bam scan in file order, i.e. what dhts_bam_open reads after the device region filter.
+ *   Target rows: without regions one row per @SQ in header order, [0, ref_len).  With regions (dhts_bam_set_regions, and an index as in
+ *     bam_bin_counts) one row per region that names a contig, in the order given: [beg, end), 0-based half-open, clipped to ref_len ('.' and
+ *     '*' name no row; with nothing but them the rows are the @SQ's).  Regions on one contig that overlap each other are refused at open
+ *     with an error that names the two; adjacent ones are fine.  A row of length 0 is emitted with all-zero results.
+ *   Each read falls out at exactly one step, and every step has a 64-bit counter:
+ *     1. flags -> n_flag_filtered: the three-mask rule of bam_bin_counts
+ *     2. placement -> n_unplaced: tid < 0, tid >= n_ref or pos0 < 0
+ *     3. length -> n_short: l_seq < min_read_len                               (samtools' order: length before MAPQ)
+ *     4. MAPQ -> n_low_mapq: mapq < min_mapq
+ *     5. overlaps no target row -> n_outside: the read interval is bam_bedcov's, [pos0, pos0 + max(1, rlen)), rlen from the effective CIGAR
+ *        (the CG tag's when the record has one), 0 with FLAG & 4
+ *     6. counted -> n_counted
+ *     n_rows = the sum of the six counters.
+ *   A counted read adds 1 to numreads and its MAPQ to sum_mapq of every row its interval overlaps.
+ *   Counted bases: a reference position x of the read counts iff it is covered by an M, = or X operation (D, N and P never count), x lies
+ *     inside the row, and with q the query index of that base q >= l_seq or qual[q] >= min_baseq.  QUAL bytes are taken as they are (0xff is
+ *     255).  Each counted base adds 1 to depth[x] and qual[q] (0 when q >= l_seq) to the row's sum_baseq; q >= l_seq covers SEQ = * and a
+ *     CIGAR longer than l_seq.  A read with FLAG & 4 has no counted bases.  There is no mate-overlap handling and no hidden flag mask.
+ *   Result per row: chrom (here: the contig's id), start, end, numreads, covbases = # positions with depth >= min_depth (BIGINT);
+ *     coverage = 100 * covbases / (end - start), meandepth = sum_depth / (end - start), meanbaseq = sum_baseq / sum_depth,
+ *     meanmapq = sum_mapq / numreads (DOUBLE: one IEEE division of the two 64-bit integers converted to double, 0.0 for a zero
+ *     denominator); behind these nine the BIGINT sums sum_depth, sum_baseq, sum_mapq.  min_depth affects covbases and coverage only.
+ *   Parameters: min_read_len >= 0; min_mapq, min_baseq 0..255; the three masks 0..65535; min_depth >= 1.  This ABI takes them as given; the
+ *     table function and the Python function default exclude_flags to 0x704, min_depth to 1 and the rest to 0.
+ *   Limits: depth per position is 32-bit.  The depth table takes 4 bytes per position of every target row (each row's span rounded up to
+ *     1,024 slots); beyond the cap (16 GiB; a human genome needs 12.4 GB) open fails with an error that states the bytes needed and the cap.
+ *     A batch with status < 0 has its rows counted and the result carries that status.  A shard or a block range other than the whole file
+ *     is refused.
+ *   Not in this contract: bam_list (several files), reference / CRAM, the depth histogram, and max_depth (htslib's pileup cap depends on the
+ *     order reads arrive in: it has no order-free definition).
+ *   Method: a 32-bit difference table, two atomics per maximal run of counted bases; QUAL is read in aligned 16-byte pieces by eight lanes
+ *     per read; the result is a scan of the table reduced per tile and summed per row (csrc/bam_coverage.hip).
+ * Every call on a context in the wrong state fails with a dhts_error that names what is missing.  The kernels are timed as DHTS_K_BCF_CHECK. */
+enum { DHTS_COVERAGE_CHROM = 0, DHTS_COVERAGE_START, DHTS_COVERAGE_END, DHTS_COVERAGE_NUMREADS, DHTS_COVERAGE_COVBASES, DHTS_COVERAGE_COVERAGE,
+       DHTS_COVERAGE_MEANDEPTH, DHTS_COVERAGE_MEANBASEQ, DHTS_COVERAGE_MEANMAPQ, DHTS_COVERAGE_SUM_DEPTH, DHTS_COVERAGE_SUM_BASEQ, DHTS_COVERAGE_SUM_MAPQ,
+       DHTS_COVERAGE_COL_COUNT };
+typedef struct {
+    int64_t min_read_len;    /* >= 0                                                                          */
+    int64_t min_depth;       /* >= 1                                                                          */
+    int32_t min_mapq;        /* 0..255                                                                        */
+    int32_t min_baseq;       /* 0..255                                                                        */
+    int32_t require_flags, exclude_flags, include_flags;   /* 0..65535                                        */
+    int32_t reserved;
+} dhts_coverage_params;
+typedef struct {
+    uint64_t n_rows, n_flag_filtered, n_unplaced, n_short, n_low_mapq, n_outside, n_counted;
+    uint64_t n_target_rows;  /* rows of the result                                                             */
+    uint64_t table_bytes;    /* bytes of the depth table                                                       */
+    int32_t status;          /* the status of the last batch that had one: 0 = the scan has not ended, 1 = clean end, < 0 = the stream
+                                ended on an error after the counted rows                                       */
+    int32_t reserved;
+} dhts_coverage_stats;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows follow, 1 = the last batch                                                                   */
+    int32_t n_cols;          /* DHTS_COVERAGE_COL_COUNT, in that order                                                                     */
+    const dhts_col *cols;    /* host array of descriptors, DEVICE pointers inside: valid[n_rows] (all 1), fixed = 8 bytes per row: BIGINT,
+                                or the bits of a DOUBLE (coverage .. meanmapq)                                                             */
+} dhts_coverage_batch;
+/* after dhts_bam_open and the optional dhts_bam_set_regions / dhts_bam_load_index: the target rows, the depth table and the counters, zeroed.
+ * A second open starts a new count. */
+int dhts_bam_coverage_open(dhts_ctx *, const dhts_coverage_params *params);
+/* the batch dhts_bam_next_batch returned LAST on this context: CIGAR and QUAL are read where the scan left them (the inflated stream and the
+ * record offsets of a batch stay in HBM until the next one is made), so the scan needs no string column.  Starts a result over. */
+int dhts_bam_coverage_accumulate(dhts_ctx *, const dhts_bam_batch *batch);
+/* dhts_bam_next_batch (<= max_blocks blocks each, no string column) + accumulate to the end of the stream.  Returns the status the stream
+ * ended on: 1, or its negative status (the rows are counted; dhts_coverage_stats.status repeats it); a call that failed returns < 0 with
+ * dhts_error set and leaves dhts_coverage_stats.status 0. */
+int dhts_bam_coverage_scan(dhts_ctx *, int64_t max_blocks);
+int dhts_bam_coverage_stats(dhts_ctx *, dhts_coverage_stats *out);
+/* the next <= max_rows result rows (0 = default).  The first call after open or accumulate takes the result from the table, which stays as
+ * it is: a later accumulate adds to intact counters and the result is taken again. */
+int dhts_bam_coverage_next(dhts_ctx *, int64_t max_rows, dhts_coverage_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst */
+uint64_t dhts_bam_coverage_batch_host_bytes(const dhts_coverage_batch *b);
+int dhts_bam_coverage_batch_fetch(dhts_ctx *, const dhts_coverage_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
 /* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
  * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and
  * uncompressed text are read.  Bind is dhts_tabix_set_conf + dhts_tabix_sniff + dhts_tabix_resolve_schema + dhts_tabix_set_schema;

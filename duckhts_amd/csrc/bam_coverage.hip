@@ -44,7 +44,8 @@ struct DepArgs {
     uint8_t *step; long long *rlen; uint32_t *k0, *k1;                      // per read
 };
 
-__global__ void __launch_bounds__(256) bam_depth_classify(DepArgs a) {
+// DEL: a D operation is walked as well (bam_depth's include_deletions); the kernel bam_coverage launches is the body without it
+template <bool DEL> __device__ __forceinline__ void dep_classify_body(const DepArgs &a) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= a.n) return;
     const uint32_t f = a.flag[i];
@@ -63,7 +64,7 @@ __global__ void __launch_bounds__(256) bam_depth_classify(DepArgs a) {
             for (uint32_t j = 0; j < ne; j++) {
                 const uint32_t op = cov_ldu32(cig + 4ull * j), code = op & 15u, len = op >> 4;
                 if (!((COV_REF_OPS >> code) & 1u) || len == 0) continue;
-                if ((DEP_M_OPS >> code) & 1u) walk = true;
+                if (((DEP_M_OPS >> code) & 1u) || (DEL && code == 2u)) walk = true;
                 rl += len;
             }
         }
@@ -76,6 +77,7 @@ __global__ void __launch_bounds__(256) bam_depth_classify(DepArgs a) {
     a.step[i] = (uint8_t)(s | (walk && s == DEP_STEP_COUNTED ? DEP_WALK : 0u));
     a.rlen[i] = rl; a.k0[i] = k0; a.k1[i] = k1;
 }
+__global__ void __launch_bounds__(256) bam_depth_classify(DepArgs a) { dep_classify_body<false>(a); }
 
 __device__ __forceinline__ uint32_t dep_byte_mask(uint32_t bits4) {           // bit b of bits4 -> byte b all ones
     return (bits4 & 1u) * 0xffu | ((bits4 >> 1) & 1u) * 0xff00u | ((bits4 >> 2) & 1u) * 0xff0000u | ((bits4 >> 3) & 1u) * 0xff000000u;
@@ -100,25 +102,41 @@ __device__ __forceinline__ uint32_t dep_ge_mask(const uint32_t (&w)[4], uint32_t
 // One read against one row [beg, end), as seen by lane `sub` of the read's eight: the difference entries of its runs go to dp (the row's span),
 // the return value is this lane's share of the counted bases' qualities.  qual = the read's QUAL (lseq bytes of it lie in the record; a query
 // index at or behind lseq passes every threshold and adds 0); ub = the stream's address rounded down to 16 bytes, mis = what was cut off.
-template <bool BQ> __device__ __forceinline__ uint64_t dep_walk_row(const uint8_t *__restrict__ ub, uint32_t mis, uint64_t qoff, long long lseq, uint32_t min_baseq,
-                                                                  const uint8_t *__restrict__ cig, uint32_t ne, long long p0, long long beg, long long end, int32_t *__restrict__ dp, uint32_t sub) {
+// DEL (bam_depth's include_deletions): every position of a D operation inside the row is a counted position without a quality, so a run goes on
+// through it (20M3D20M with passing bases around the D is one run, two atomics); the first lane of the eight sets what a D starts and ends.
+// SUM = false: nobody wants the quality sum; without min_baseq the pieces are then not read at all.
+template <bool BQ, bool DEL = false, bool SUM = true>
+__device__ __forceinline__ uint64_t dep_walk_row(const uint8_t *__restrict__ ub, uint32_t mis, uint64_t qoff, long long lseq, uint32_t min_baseq,
+                                                 const uint8_t *__restrict__ cig, uint32_t ne, long long p0, long long beg, long long end, int32_t *__restrict__ dp, uint32_t sub) {
     const uint8_t *qual = ub + mis + qoff;
     const long long qbase = (long long)(mis + qoff);                         // position of query index 0 in the 16-byte grid
     auto pass = [&](long long q) -> bool { return !BQ || q >= lseq || (uint32_t)qual[q] >= min_baseq; };
     auto in_row = [&](long long x) -> bool { return x >= beg && x < end; };
     uint64_t sumq = 0;
-    long long x = p0, q = 0, last_q = 0; bool adj = false;                   // adj: the reference position before x is the base last_q of an M = X operation
+    long long x = p0, q = 0, last_q = 0; bool adj = false, del = false;      // adj: the reference position before x is the base last_q of an M = X operation; del (DEL): it is a D's
     for (uint32_t j = 0; j < ne; j++) {
         const uint32_t op = cov_ldu32(cig + 4ull * j), code = op & 15u; const long long len = (long long)(op >> 4);
         if (len == 0) continue;
+        if (DEL && code == 2u) {
+            const bool carry = in_row(x - 1) && (del || (adj && pass(last_q)));                     // c(x - 1)
+            const long long dlo = beg > x ? beg : x, dhi = end < x + len ? end : x + len;           // the operation's positions inside the row
+            if (sub == 0) {
+                if (dhi > dlo) {
+                    if (!(carry && dlo == x)) atomicAdd(dp + (dlo - beg), 1);
+                    if (dhi < x + len) atomicAdd(dp + (end - beg), -1);                             // the row ends inside the operation
+                } else if (carry) atomicAdd(dp + (x - beg), -1);                                    // (then x == end)
+            }
+            x += len; adj = false; del = true;
+            continue;
+        }
         if ((DEP_M_OPS >> code) & 1u) {
-            const bool carry = adj && in_row(x - 1) && pass(last_q);         // c(x - 1)
+            const bool carry = in_row(x - 1) && ((DEL && del) || (adj && pass(last_q)));            // c(x - 1)
             const long long jlo = beg > x ? beg - x : 0, jhi = end - x < len ? end - x : len;      // the operation's bases inside the row
             if (!in_row(x)) { if (sub == 0 && carry) atomicAdd(dp + (x - beg), -1); }               // (then x == end: the run stops at the row's end)
             if (jhi > jlo) {
                 const long long qlo = q + jlo, qhi = q + jhi;
                 const long long c_last = (qbase + qhi - 1) >> 4;
-                for (long long c = ((qbase + qlo) >> 4) + sub; c <= c_last; c += DEP_LANES) {
+                if (BQ || SUM) for (long long c = ((qbase + qlo) >> 4) + sub; c <= c_last; c += DEP_LANES) {
                     const long long qc0 = (c << 4) - qbase;                  // the query index of the piece's byte 0
                     const uint32_t lo_i = qlo > qc0 ? (uint32_t)(qlo - qc0) : 0u, hi_i = qhi - qc0 < 16 ? (uint32_t)(qhi - qc0) : 16u;
                     const uint32_t valid = ((1u << hi_i) - 1u) & ~((1u << lo_i) - 1u);
@@ -126,10 +144,10 @@ template <bool BQ> __device__ __forceinline__ uint64_t dep_walk_row(const uint8_
                     const uint32_t in_rec = nr <= 0 ? 0u : nr >= 16 ? 0xffffu : (1u << (uint32_t)nr) - 1u, real = valid & in_rec;
                     uint32_t w[4] = {0u, 0u, 0u, 0u};
                     if (real) { const uint4 v = *(const uint4 *)(ub + (c << 4)); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-                    if (!BQ) sumq += dep_byte_sum(w, real);
+                    if (!BQ) { if (SUM) sumq += dep_byte_sum(w, real); }
                     else {
                         const uint32_t m = (dep_ge_mask(w, min_baseq) & real) | (valid & ~in_rec);
-                        sumq += dep_byte_sum(w, m & real);
+                        if (SUM) sumq += dep_byte_sum(w, m & real);
                         const bool pred = qc0 + lo_i > qlo ? pass(qc0 + lo_i - 1) : (jlo == 0 && carry);
                         const uint32_t p = (m << 1) | ((pred ? 1u : 0u) << lo_i);
                         uint32_t st = m & ~p, en = ~m & p & valid;
@@ -143,13 +161,13 @@ template <bool BQ> __device__ __forceinline__ uint64_t dep_walk_row(const uint8_
                     if (jhi < len && pass(q + jhi - 1)) atomicAdd(dp + (end - beg), -1);          // the row ends inside the operation
                 }
             }
-            x += len; q += len; adj = true; last_q = q - 1;
+            x += len; q += len; adj = true; del = false; last_q = q - 1;
         } else if ((DEP_GAP_OPS >> code) & 1u) {
-            if (sub == 0 && adj && in_row(x - 1) && pass(last_q)) atomicAdd(dp + (x - beg), -1);
-            adj = false; x += len;
+            if (sub == 0 && in_row(x - 1) && ((DEL && del) || (adj && pass(last_q)))) atomicAdd(dp + (x - beg), -1);
+            adj = false; del = false; x += len;
         } else if ((DEP_Q_ONLY_OPS >> code) & 1u) q += len;
     }
-    if (sub == 0 && adj && in_row(x - 1) && pass(last_q)) atomicAdd(dp + (x - beg), -1);
+    if (sub == 0 && in_row(x - 1) && ((DEL && del) || (adj && pass(last_q)))) atomicAdd(dp + (x - beg), -1);
     return sumq;
 }
 
@@ -157,7 +175,10 @@ template <bool BQ> __device__ __forceinline__ uint64_t dep_walk_row(const uint8_
 // and takes part in every vote.  Round r is the r-th row a read overlaps (one, for all but the reads that hang over a row's edge into the
 // next).  The eight lanes' quality sums are folded, the eight reads of a wave moved to its first eight lanes, and cov_merge adds runs of one
 // row index once.  The step counters as in bam_cov_add.
-template <bool BQ> __global__ void __launch_bounds__(256) bam_depth_add(DepArgs a, int32_t *__restrict__ diff, unsigned long long *__restrict__ words, unsigned long long *__restrict__ steps) {
+// bam_depth's form: DEL as in dep_walk_row; WORDS = false drops the per-row words and their copies (words is not read): a counted read then
+// sets touched[tid] = 1 with a plain store instead (every writer stores the same value, so no atomic is needed).
+template <bool BQ, bool DEL, bool WORDS>
+__device__ __forceinline__ void dep_add_body(const DepArgs &a, int32_t *__restrict__ diff, unsigned long long *__restrict__ words, uint32_t *__restrict__ touched, unsigned long long *__restrict__ steps) {
     __shared__ unsigned long long block_steps[DEP_N_STEPS];
     const uint32_t lane = threadIdx.x & 63u, sub = threadIdx.x & (DEP_LANES - 1u), grp = threadIdx.x / DEP_LANES;
     if (threadIdx.x < DEP_N_STEPS) block_steps[threadIdx.x] = 0;
@@ -186,7 +207,8 @@ template <bool BQ> __global__ void __launch_bounds__(256) bam_depth_add(DepArgs 
             const bool on = k0 + r < k1;
             const uint32_t k = k0 + r;
             unsigned long long sumq = 0;
-            if (on && ne) sumq = dep_walk_row<BQ>(ub, mis, qoff, lseq, a.min_baseq, cig, ne, p0, a.rbeg[k], a.rend[k], diff + a.rbase[k], sub);
+            if (on && ne) sumq = dep_walk_row<BQ, DEL, WORDS>(ub, mis, qoff, lseq, a.min_baseq, cig, ne, p0, a.rbeg[k], a.rend[k], diff + a.rbase[k], sub);
+            if (!WORDS) continue;
             sumq += __shfl_xor(sumq, 1); sumq += __shfl_xor(sumq, 2); sumq += __shfl_xor(sumq, 4);
             const uint32_t idx = on ? DEP_WORD_IDX(k, blockIdx.x & (DEP_REPLICAS - 1u)) : COV_NO_IDX;
             const int src = (int)((lane & 7u) * DEP_LANES);
@@ -195,6 +217,7 @@ template <bool BQ> __global__ void __launch_bounds__(256) bam_depth_add(DepArgs 
             cov_merge<true, false>(idxc, mqc, lane, words, DEP_W_READS, DEP_W_MAPQ);
             cov_merge<true, false>(idxc, sqc, lane, words, DEP_W_SPARE, DEP_W_BASEQ);
         }
+        if (!WORDS && s == DEP_STEP_COUNTED && sub == 0) touched[a.tid[i]] = 1u;
         const uint32_t sv = sub == 0 ? s : (uint32_t)DEP_STEP_NONE;
 #pragma unroll
         for (uint32_t k = 0; k < DEP_N_STEPS; k++) { const unsigned long long m = __ballot(sv == k); if (lane == k) mine += (unsigned long long)__popcll(m); }
@@ -202,6 +225,9 @@ template <bool BQ> __global__ void __launch_bounds__(256) bam_depth_add(DepArgs 
     if (lane < DEP_N_STEPS && mine) atomicAdd(&block_steps[lane], mine);
     __syncthreads();
     if (threadIdx.x < DEP_N_STEPS && block_steps[threadIdx.x]) atomicAdd(&steps[threadIdx.x], block_steps[threadIdx.x]);
+}
+template <bool BQ> __global__ void __launch_bounds__(256) bam_depth_add(DepArgs a, int32_t *__restrict__ diff, unsigned long long *__restrict__ words, unsigned long long *__restrict__ steps) {
+    dep_add_body<BQ, false, true>(a, diff, words, nullptr, steps);
 }
 
 // ---- the result: depth = the inclusive scan of diff; nothing of it is written back ------------------------------------------------------

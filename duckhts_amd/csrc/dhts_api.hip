@@ -19,6 +19,7 @@
 #include "bam_bins.hip"
 #include "bam_bedcov.hip"
 #include "bam_coverage.hip"
+#include "bam_depth.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -220,11 +221,26 @@ struct BedcovState {
 // bam_coverage (bam_coverage.hip, dhts_bam_coverage.inc): the parameters, the target rows in the order they are answered in (o_k: a row's
 // index among the sorted non-empty rows, -1 for an empty one), the sorted rows on the device with their spans of the difference table, the
 // per-row words and the step counters, per-batch scratch, the per-tile values of a result, and the result's columns on the host
-struct CoverageState {
+// (DepLayout: what bam_coverage and bam_depth share -- the target rows and their spans of the difference table, made by dep_layout)
+struct DepLayout {
+    uint64_t n_sorted = 0, slots = 0;
+    std::vector<int32_t> o_tid; std::vector<int64_t> o_beg, o_end, o_k;
+    std::vector<int64_t> s_beg, s_end; std::vector<uint64_t> s_base; std::vector<int32_t> s_tid;   // the sorted rows on the host
+    DevBuf diff, tid_first, rbeg, rend, rbase, tile_row;
+};
+struct CoverageState : DepLayout {
     bool open = false, res_ready = false; dhts_coverage_params P; int32_t n_ref = 0, status = 0;
-    uint64_t n_sorted = 0, slots = 0, row_next = 0; std::vector<dhts_col> out;
-    std::vector<int32_t> o_tid; std::vector<int64_t> o_beg, o_end, o_k, h_cols[DHTS_COVERAGE_COL_COUNT];
-    DevBuf diff, words, steps, tid_first, rbeg, rend, rbase, tile_row, step, rlen, k0, k1, tsum, tcov, tdepth, res, ones, cols[DHTS_COVERAGE_COL_COUNT];
+    uint64_t row_next = 0; std::vector<dhts_col> out;
+    std::vector<int64_t> h_cols[DHTS_COVERAGE_COL_COUNT];
+    DevBuf words, steps, step, rlen, k0, k1, tsum, tcov, tdepth, res, ones, cols[DHTS_COVERAGE_COL_COUNT];
+};
+// bam_depth (bam_depth.hip, dhts_bam_depth.inc): the parameters, the layout, the touched contigs and the step counters, per-batch scratch, and
+// of a result the depth (tsum) and the result index (toff) in front of every tile, the result index in front of every sorted row (row_off),
+// where the next page starts (the row in answer order and the positions of it already taken) and the page's columns
+struct DepthState : DepLayout {
+    bool open = false, res_ready = false; dhts_depth_params P; int32_t n_ref = 0, status = 0;
+    uint64_t n_bed_skipped = 0, n_positions = 0, o_next = 0, o_within = 0; std::vector<uint64_t> row_off; std::vector<dhts_col> out;
+    DevBuf steps, touched, row_tid, step, rlen, k0, k1, tsum, toff, part, rowres, pagetiles, out_tid, out_pos, out_depth;
 };
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
@@ -272,6 +288,7 @@ struct dhts_ctx {
     BinsState bins;
     BedcovState cov;
     CoverageState dep;
+    DepthState dpt;
     UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
@@ -565,6 +582,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_bins.inc"
 #include "dhts_bam_bedcov.inc"
 #include "dhts_bam_coverage.inc"
+#include "dhts_bam_depth.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

@@ -19,31 +19,21 @@ static int bedcov_bed_ok(dhts_ctx *c, dhts_ctx *b) {
     return 0;
 }
 
-int dhts_bam_bedcov_open(dhts_ctx *c, dhts_ctx *b, const dhts_bedcov_params *p) {
-    if (!c || !p) return c ? fail(c, "bam_bedcov: no parameters") : -1;
-    BedcovState &S = c->cov;
-    S.open = false;
-    if (!c->bam_open) return fail(c, "bam_bedcov: dhts_bam_open not called");
-    if (bedcov_bed_ok(c, b)) return -1;
-    if (c->range_cut) return fail(c, BEDCOV_SHARDED);
-    if (p->min_mapq < 0 || p->min_mapq > 255) return fail(c, "bam_bedcov: min_mapq must be between 0 and 255");
-    if (p->include_flags < 0 || p->include_flags > 65535) return fail(c, "bam_bedcov: include_flags must be between 0 and 65535");
-    if (p->require_flags < 0 || p->require_flags > 65535) return fail(c, "bam_bedcov: require_flags must be between 0 and 65535");
-    if (p->exclude_flags < 0 || p->exclude_flags > 65535) return fail(c, "bam_bedcov: exclude_flags must be between 0 and 65535");
-    if ((p->count_deletions != 0 && p->count_deletions != 1) || (p->count_ref_skips != 0 && p->count_ref_skips != 1)) return fail(c, "bam_bedcov: count_deletions and count_ref_skips must be 0 or 1");
-    // ---- the first pass over the BED: contig, start and end of every row ----
+// One pass over the BED context b (after dhts_bed_open): contig, start and end of every row, for bam_bedcov and bam_depth.  tid[i] = the
+// contig's id in c's header (the first @SQ of a name listed twice), -1 for a name it lacks or a NULL chrom; a row whose start or end is NULL has
+// beg = end = 0.  Rows behind max_rows are counted in n_bed and not kept.  Errors of b become c's.
+static int bed_rows_read(dhts_ctx *c, dhts_ctx *b, uint64_t max_rows, std::vector<int32_t> &tid, std::vector<int64_t> &beg, std::vector<int64_t> &end, uint64_t &n_bed) {
     const int32_t proj[3] = {DHTS_BED_CHROM, DHTS_BED_START, DHTS_BED_END};
     if (dhts_bed_set_projection(b, proj, 3) || bed_rewind(b)) return fail(c, "%s", dhts_error(b));
     std::map<std::string, int32_t> tid_of;
     for (size_t t = 0; t < c->ref_name.size(); t++) tid_of.emplace(c->ref_name[t], (int32_t)t);   // (a name listed twice: the first @SQ, as sam_hdr_name2tid's hash keeps)
-    std::vector<int32_t> tid; std::vector<int64_t> beg, end;
-    uint64_t n_bed = 0; std::string last_name; int32_t last_tid = -1; bool have_last = false;
+    n_bed = 0; std::string last_name; int32_t last_tid = -1; bool have_last = false;
     std::vector<uint8_t> arena;
     for (;;) {
         dhts_bed_batch bb;
         if (dhts_bed_next_batch(b, 0, &bb)) return fail(c, "%s", dhts_error(b));
         const uint64_t n = (uint64_t)bb.n_rows;
-        if (n && n_bed + n <= g_bedcov_max_rows) {
+        if (n && n_bed + n <= max_rows) {
             dhts_col hc[3];
             arena.resize((size_t)dhts_bed_batch_host_bytes(&bb) + 8);
             if (dhts_bed_batch_fetch(b, &bb, arena.data(), arena.size(), hc)) return fail(c, "%s", dhts_error(b));
@@ -58,14 +48,33 @@ int dhts_bam_bedcov_open(dhts_ctx *c, dhts_ctx *b, const dhts_bedcov_params *p) 
                     }
                     t = last_tid;
                 }
-                const bool ok = t >= 0 && hc[1].valid[r] && hc[2].valid[r] && he[r] > hs[r];
-                tid.push_back(ok ? t : -1); beg.push_back(ok ? hs[r] : 0); end.push_back(ok ? he[r] : 0);
+                const bool have = hc[1].valid[r] && hc[2].valid[r];
+                tid.push_back(t); beg.push_back(have ? hs[r] : 0); end.push_back(have ? he[r] : 0);
             }
         }
         n_bed += n;
         if (bb.status < 0) return fail(c, "%s", dhts_error(b));
         if (bb.status != 0) break;
     }
+    return 0;
+}
+
+int dhts_bam_bedcov_open(dhts_ctx *c, dhts_ctx *b, const dhts_bedcov_params *p) {
+    if (!c || !p) return c ? fail(c, "bam_bedcov: no parameters") : -1;
+    BedcovState &S = c->cov;
+    S.open = false;
+    if (!c->bam_open) return fail(c, "bam_bedcov: dhts_bam_open not called");
+    if (bedcov_bed_ok(c, b)) return -1;
+    if (c->range_cut) return fail(c, BEDCOV_SHARDED);
+    if (p->min_mapq < 0 || p->min_mapq > 255) return fail(c, "bam_bedcov: min_mapq must be between 0 and 255");
+    if (p->include_flags < 0 || p->include_flags > 65535) return fail(c, "bam_bedcov: include_flags must be between 0 and 65535");
+    if (p->require_flags < 0 || p->require_flags > 65535) return fail(c, "bam_bedcov: require_flags must be between 0 and 65535");
+    if (p->exclude_flags < 0 || p->exclude_flags > 65535) return fail(c, "bam_bedcov: exclude_flags must be between 0 and 65535");
+    if ((p->count_deletions != 0 && p->count_deletions != 1) || (p->count_ref_skips != 0 && p->count_ref_skips != 1)) return fail(c, "bam_bedcov: count_deletions and count_ref_skips must be 0 or 1");
+    // ---- the first pass over the BED: contig, start and end of every row; a row without a contig of the header or with end <= start takes no part ----
+    std::vector<int32_t> tid; std::vector<int64_t> beg, end; uint64_t n_bed = 0;
+    if (bed_rows_read(c, b, g_bedcov_max_rows, tid, beg, end, n_bed)) return -1;
+    for (size_t i = 0; i < tid.size(); i++) if (tid[i] < 0 || end[i] <= beg[i]) { tid[i] = -1; beg[i] = 0; end[i] = 0; }
     if (n_bed > g_bedcov_max_rows) return fail(c, "bam_bedcov: the BED file has %llu rows; at most %llu are supported", (unsigned long long)n_bed, (unsigned long long)g_bedcov_max_rows);
     // ---- breakpoints: per contig the sorted distinct starts and ends of its valid rows, concatenated ----
     const size_t n_ref = c->ref_name.size();

@@ -14,6 +14,58 @@ static const uint32_t COVERAGE_COLMASK = (1u << DHTS_BAM_FLAG) | (1u << DHTS_BAM
 // tests: the most bytes the difference table may take (0: the contract's 16 GiB)
 void dhts_debug_coverage_max_table_bytes(uint64_t n) { g_coverage_max_table_bytes = n ? n : COVERAGE_MAX_TABLE_BYTES; }
 
+// The layout bam_coverage and bam_depth share.  S.o_tid / o_beg / o_end hold the target rows in the order they are answered in, clipped.  They
+// are sorted by (contig, start) with the empty ones left out (o_k: a row's index among the sorted ones, -1 for an empty one), neighbours on one
+// contig must not overlap (tok(i): what row i was given as, for the error), every sorted row gets a span of (end - beg) + 1 slots of the
+// difference table rounded up to the tile, and the rows, tid_first, tile_row and the zeroed table go to the device (queued on the stream).
+static int dep_layout(dhts_ctx *c, DepLayout &S, const char *fn, const std::function<const char *(size_t)> &tok) {
+    const size_t n_ref = c->ref_len.size(), n_out = S.o_tid.size();
+    std::vector<uint32_t> order;
+    for (size_t i = 0; i < n_out; i++) if (S.o_end[i] > S.o_beg[i]) order.push_back((uint32_t)i);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return S.o_tid[x] != S.o_tid[y] ? S.o_tid[x] < S.o_tid[y] : S.o_beg[x] < S.o_beg[y]; });
+    for (size_t j = 1; j < order.size(); j++) {
+        const uint32_t x = order[j - 1], y = order[j];
+        if (S.o_tid[x] == S.o_tid[y] && S.o_beg[y] < S.o_end[x]) {
+            const uint32_t first = x < y ? x : y, second = x < y ? y : x;
+            return fail(c, "%s: the regions '%s' and '%s' overlap (one row is answered per region: give disjoint regions)", fn, tok(first), tok(second));
+        }
+    }
+    const size_t R = order.size();
+    S.o_k.assign(n_out, -1);
+    std::vector<uint32_t> tid_first(n_ref + 1, 0);
+    S.s_beg.assign(R + 1, 0); S.s_end.assign(R + 1, 0); S.s_base.assign(R + 1, 0); S.s_tid.assign(R + 1, 0);
+    uint64_t slots = 0;
+    for (size_t k = 0; k < R; k++) {
+        const uint32_t i = order[k];
+        S.o_k[i] = (int64_t)k; S.s_beg[k] = S.o_beg[i]; S.s_end[k] = S.o_end[i]; S.s_base[k] = slots; S.s_tid[k] = S.o_tid[i];
+        tid_first[(size_t)S.o_tid[i] + 1]++;
+        slots += ((uint64_t)(S.s_end[k] - S.s_beg[k]) + 1u + DEP_TILE - 1u) / DEP_TILE * DEP_TILE;
+    }
+    S.s_base[R] = slots;
+    for (size_t t = 0; t < n_ref; t++) tid_first[t + 1] += tid_first[t];
+    if (slots * 4 > g_coverage_max_table_bytes)
+        return fail(c, "%s: the depth table needs %llu bytes (4 per position of every row); at most %llu are supported (fewer or shorter regions)",
+                    fn, (unsigned long long)(slots * 4), (unsigned long long)g_coverage_max_table_bytes);
+    const uint64_t ntiles = slots / DEP_TILE;
+    std::vector<uint32_t> tile_row((size_t)ntiles + 1, 0);
+    for (size_t k = 0; k < R; k++) for (uint64_t t = S.s_base[k] / DEP_TILE; t < S.s_base[k + 1] / DEP_TILE; t++) tile_row[(size_t)t] = (uint32_t)k;
+    HIPCHK(c, hipSetDevice(c->device));
+    ENSURE(c, S.tid_first, (n_ref + 1) * 4 + 64); ENSURE(c, S.rbeg, (R + 1) * 8 + 64); ENSURE(c, S.rend, (R + 1) * 8 + 64); ENSURE(c, S.rbase, (R + 1) * 8 + 64);
+    ENSURE(c, S.tile_row, (size_t)(ntiles + 1) * 4 + 64); ENSURE(c, S.diff, (size_t)slots * 4 + 64);
+    {
+        KTimer tm(c, DHTS_K_BCF_CHECK);
+        HIPCHK(c, hipMemsetAsync(S.diff.p, 0, (size_t)slots * 4 + 64, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(S.tid_first.p, tid_first.data(), (n_ref + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(S.rbeg.p, S.s_beg.data(), (R + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(S.rend.p, S.s_end.data(), (R + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(S.rbase.p, S.s_base.data(), (R + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(S.tile_row.p, tile_row.data(), (size_t)(ntiles + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the copies read vectors of this call)
+    S.n_sorted = R; S.slots = slots;
+    return 0;
+}
+
 int dhts_bam_coverage_open(dhts_ctx *c, const dhts_coverage_params *p) {
     if (!c || !p) return c ? fail(c, "bam_coverage: no parameters") : -1;
     CoverageState &S = c->dep;
@@ -38,52 +90,13 @@ int dhts_bam_coverage_open(dhts_ctx *c, const dhts_coverage_params *p) {
             S.o_tid.push_back(r.tid); S.o_beg.push_back(r.beg < L ? r.beg : L); S.o_end.push_back(r.end < L ? r.end : L); o_given.push_back(g);
         }
     } else for (size_t t = 0; t < n_ref; t++) { S.o_tid.push_back((int32_t)t); S.o_beg.push_back(0); S.o_end.push_back((int64_t)c->ref_len[t]); }
-    const size_t n_out = S.o_tid.size();
-    // sorted by (contig, start), the empty ones left out; neighbours on one contig must not overlap
-    std::vector<uint32_t> order;
-    for (size_t i = 0; i < n_out; i++) if (S.o_end[i] > S.o_beg[i]) order.push_back((uint32_t)i);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return S.o_tid[x] != S.o_tid[y] ? S.o_tid[x] < S.o_tid[y] : S.o_beg[x] < S.o_beg[y]; });
-    for (size_t j = 1; j < order.size(); j++) {
-        const uint32_t x = order[j - 1], y = order[j];
-        if (S.o_tid[x] == S.o_tid[y] && S.o_beg[y] < S.o_end[x]) {
-            const uint32_t first = x < y ? x : y, second = x < y ? y : x;
-            return fail(c, "bam_coverage: the regions '%s' and '%s' overlap (one row is answered per region: give disjoint regions)",
-                        c->rg_given[o_given[first]].tok.c_str(), c->rg_given[o_given[second]].tok.c_str());
-        }
-    }
-    const size_t R = order.size();
-    S.o_k.assign(n_out, -1);
-    std::vector<uint32_t> tid_first(n_ref + 1, 0); std::vector<int64_t> rbeg(R + 1, 0), rend(R + 1, 0); std::vector<uint64_t> rbase(R + 1, 0);
-    uint64_t slots = 0;
-    for (size_t k = 0; k < R; k++) {
-        const uint32_t i = order[k];
-        S.o_k[i] = (int64_t)k; rbeg[k] = S.o_beg[i]; rend[k] = S.o_end[i]; rbase[k] = slots;
-        tid_first[(size_t)S.o_tid[i] + 1]++;
-        slots += ((uint64_t)(rend[k] - rbeg[k]) + 1u + DEP_TILE - 1u) / DEP_TILE * DEP_TILE;
-    }
-    for (size_t t = 0; t < n_ref; t++) tid_first[t + 1] += tid_first[t];
-    if (slots * 4 > g_coverage_max_table_bytes)
-        return fail(c, "bam_coverage: the depth table needs %llu bytes (4 per position of every row); at most %llu are supported (fewer or shorter regions)",
-                    (unsigned long long)(slots * 4), (unsigned long long)g_coverage_max_table_bytes);
-    const uint64_t ntiles = slots / DEP_TILE;
-    std::vector<uint32_t> tile_row((size_t)ntiles + 1, 0);
-    for (size_t k = 0; k < R; k++) { const uint64_t t1 = (k + 1 < R ? rbase[k + 1] : slots) / DEP_TILE; for (uint64_t t = rbase[k] / DEP_TILE; t < t1; t++) tile_row[(size_t)t] = (uint32_t)k; }
-    HIPCHK(c, hipSetDevice(c->device));
-    ENSURE(c, S.steps, 64); ENSURE(c, S.tid_first, (n_ref + 1) * 4 + 64); ENSURE(c, S.rbeg, (R + 1) * 8 + 64); ENSURE(c, S.rend, (R + 1) * 8 + 64); ENSURE(c, S.rbase, (R + 1) * 8 + 64);
-    ENSURE(c, S.tile_row, (size_t)(ntiles + 1) * 4 + 64); ENSURE(c, S.words, (R + 1) * DEP_REPLICAS * 64 + 64); ENSURE(c, S.diff, (size_t)slots * 4 + 64);
+    if (dep_layout(c, S, "bam_coverage", [&](size_t i) { return c->rg_given[o_given[i]].tok.c_str(); })) return -1;
+    const size_t R = (size_t)S.n_sorted;
+    ENSURE(c, S.steps, 64); ENSURE(c, S.words, (R + 1) * DEP_REPLICAS * 64 + 64);
     HIPCHK(c, hipMemsetAsync(S.steps.p, 0, 64, c->stream));
     HIPCHK(c, hipMemsetAsync(S.words.p, 0, (R + 1) * DEP_REPLICAS * 64, c->stream));
-    {
-        KTimer tm(c, DHTS_K_BCF_CHECK);
-        HIPCHK(c, hipMemsetAsync(S.diff.p, 0, (size_t)slots * 4 + 64, c->stream));
-    }
-    HIPCHK(c, hipMemcpyAsync(S.tid_first.p, tid_first.data(), (n_ref + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(S.rbeg.p, rbeg.data(), (R + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(S.rend.p, rend.data(), (R + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(S.rbase.p, rbase.data(), (R + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(S.tile_row.p, tile_row.data(), (size_t)(ntiles + 1) * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    S.P = *p; S.n_ref = (int32_t)n_ref; S.status = 0; S.n_sorted = R; S.slots = slots; S.res_ready = false; S.row_next = 0;
+    S.P = *p; S.n_ref = (int32_t)n_ref; S.status = 0; S.res_ready = false; S.row_next = 0;
     S.open = true;
     return 0;
 }

@@ -39,6 +39,7 @@ static double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); r
 #include "duckdb_interval.inc"
 #include "duckdb_bedcov.inc"
 #include "duckdb_coverage.inc"
+#include "duckdb_depth.inc"
 #include "duckdb_tabix.inc"
 #include "duckdb_udf.inc"
 
@@ -73,6 +74,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     if (const char *e = getenv("DHTS_COVERAGE_FUNCTIONS")) { const int v = atoi(e); if (v == 1 || v == 2) register_bam_bin_counts_function(conn); if (v == 2) register_bam_bedcov_function(conn); }
     // bam_coverage (PLAN.md 10.4 / 10.7.3) closes the list behind a variable of its own, DHTS_DEPTH_FUNCTIONS=1: the sets under DHTS_COVERAGE_FUNCTIONS stay what they were
     if (const char *e = getenv("DHTS_DEPTH_FUNCTIONS")) if (atoi(e) == 1) register_bam_coverage_function(conn);
+    // bam_depth (PLAN.md 10.4 / 10.7.3) comes last, behind a variable of its own, DHTS_PERBASE_FUNCTIONS=1: no value of an existing variable changes its set
+    if (const char *e = getenv("DHTS_PERBASE_FUNCTIONS")) if (atoi(e) == 1) register_bam_depth_function(conn);
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);
     return true;
 }

@@ -715,6 +715,82 @@ int dhts_bam_coverage_next(dhts_ctx *, int64_t max_rows, dhts_coverage_batch *ou
 uint64_t dhts_bam_coverage_batch_host_bytes(const dhts_coverage_batch *b);
 int dhts_bam_coverage_batch_fetch(dhts_ctx *, const dhts_coverage_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- bam_depth -------------------------------------------------------------------------------
+ * Per position: chrom, pos, depth (what `samtools depth` prints), streamed page by page out of the depth table bam_coverage's add pass fills in
+ * HBM: the per-base result is never resident as a whole, on the device or on the host.  The reference has only a plan for it (.github/PLAN.md,
+ * Phase 10, 10.4 / 10.7.3), so this is the specification.
+ *   Input, the six steps with their 64-bit counters, the read interval, the effective CIGAR (the CG tag's) and the rule that a read with
+ *     FLAG & 4 has no counted base: exactly bam_coverage's.
+ *   Target rows without a BED: exactly bam_coverage's -- one per @SQ, or one per region in the order given, clipped to ref_len; regions that
+ *     overlap are refused with an error that names the two; empty rows are allowed (they emit nothing).
+ *   Target rows with a BED (a second context, as in dhts_bam_bedcov_open): the union of the BED's rows -- per contig in header order, sorted by
+ *     start, with overlapping, nested, duplicate and adjacent rows merged into maximal intervals, clipped to ref_len, empty ones dropped.  BED
+ *     rows that name a contig the header lacks are skipped and counted (n_bed_skipped).  A BED together with regions is refused by name.
+ *     Every merged interval costs at least 4 KiB of table: a row's span is padded to 1,024 slots, as in bam_coverage.
+ *   Counted bases: as in bam_coverage -- covered by M, = or X, inside a row, and q >= l_seq or qual[q] >= min_baseq.  With include_deletions
+ *     every reference position of a D operation inside a row counts as well, whatever min_baseq and the qualities of the bases around it are;
+ *     a leading or trailing D counts.  N and P never count.
+ *   Result: one row per emitted position: chrom (here: the contig's id, int32), pos (1-based, int64), depth (int32).  Order: the target rows
+ *     in result order (the order given for regions, sorted order otherwise), positions ascending inside a row.  all_positions:
+ *       0  positions with depth > 0
+ *       1  (-a) every position of every target row on a touched contig, positions with depth > 0 elsewhere (there are none, by construction).
+ *          A contig is touched iff at least one read reached step 6 (counted) against any of its target rows -- a counted read without a
+ *          counted base included.
+ *       2  (-aa) every position of every target row
+ *   Parameters: min_read_len >= 0; min_mapq, min_baseq 0..255; the three masks 0..65535; include_deletions 0..1; all_positions 0..2.  This ABI
+ *     takes them as given; the table function and the Python function default exclude_flags to 0x704 and the rest to 0.
+ *   Limits: bam_coverage's -- 32-bit depth, the table cap and its error (dhts_debug_coverage_max_table_bytes applies to both functions), a
+ *     shard or block range refused, a stream that ends on an error has its rows counted and its status carried.
+ *   Not in this contract: suppress_overlaps (mates are not paired on the device), several input files, reference / CRAM, max_depth, and a
+ *     run-length (bedGraph) form of the result.
+ *   Method: the add pass without the per-row words, a D joined to the runs around it; a carry in two levels for the depth and the result index
+ *     in front of every tile; a page is a window of result indices, emitted by the tiles that hold it (csrc/bam_depth.hip).
+ * All errors are prefixed "bam_depth:".  Every call on a context in the wrong state fails with a dhts_error that names what is missing. */
+enum { DHTS_DEPTH_CHROM = 0, DHTS_DEPTH_POS, DHTS_DEPTH_DEPTH, DHTS_DEPTH_COL_COUNT };
+typedef struct {
+    int64_t min_read_len;    /* >= 0                                                                          */
+    int32_t min_mapq;        /* 0..255                                                                        */
+    int32_t min_baseq;       /* 0..255                                                                        */
+    int32_t require_flags, exclude_flags, include_flags;   /* 0..65535                                        */
+    int32_t include_deletions;                             /* 0 or 1                                          */
+    int32_t all_positions;                                 /* 0, 1 (-a) or 2 (-aa)                            */
+    int32_t reserved;
+} dhts_depth_params;
+typedef struct {
+    uint64_t n_rows, n_flag_filtered, n_unplaced, n_short, n_low_mapq, n_outside, n_counted;
+    uint64_t n_target_rows;  /* target rows (regions, @SQ lines or merged BED intervals)                       */
+    uint64_t n_bed_skipped;  /* BED rows that name a contig the header lacks                                   */
+    uint64_t table_bytes;    /* bytes of the depth table                                                       */
+    uint64_t n_positions;    /* rows of the whole result: valid once a result was taken (dhts_bam_depth_next), 0 before */
+    int32_t status;          /* as in dhts_coverage_stats                                                      */
+    int32_t reserved;
+} dhts_depth_stats;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows follow, 1 = the last page                                                                    */
+    int32_t n_cols;          /* DHTS_DEPTH_COL_COUNT, in that order                                                                        */
+    const dhts_col *cols;    /* host array of descriptors, DEVICE pointers inside: fixed = int32 (chrom, depth) or int64 (pos) per row, a
+                                null pointer for a column colmask left out; no row is NULL and valid stays a null pointer                   */
+} dhts_depth_batch;
+/* after dhts_bam_open and the optional dhts_bam_set_regions / dhts_bam_load_index.  bed: NULL, or a second context on the same device prepared
+ * as for read_bed (dhts_bed_open); its projection belongs to bam_depth from here on.  The target rows, the depth table and the counters,
+ * zeroed.  A second open starts a new count. */
+int dhts_bam_depth_open(dhts_ctx *bam, const dhts_depth_params *params, dhts_ctx *bed);
+/* the batch dhts_bam_next_batch returned LAST on this context, as in dhts_bam_coverage_accumulate.  Starts a result over: the table and the
+ * counters stay intact, the next dhts_bam_depth_next returns the first page of the new result. */
+int dhts_bam_depth_accumulate(dhts_ctx *bam, const dhts_bam_batch *batch);
+/* dhts_bam_next_batch + accumulate to the end of the stream; returns as dhts_bam_coverage_scan does */
+int dhts_bam_depth_scan(dhts_ctx *bam, int64_t max_blocks);
+int dhts_bam_depth_stats(dhts_ctx *bam, dhts_depth_stats *out);
+/* the next <= max_rows rows of the result (0 = 1,048,576 rows: 16 MiB with all three columns).  colmask: bit DHTS_DEPTH_* set = the column is
+ * written and fetched; a query that reads depth alone moves 4 bytes per row.  The first call after open or accumulate counts the rows of the
+ * result from the table, which stays as it is.  The page's columns stay valid until the next call on the context. */
+int dhts_bam_depth_next(dhts_ctx *bam, int64_t max_rows, uint32_t colmask, dhts_depth_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst (null where the batch has none); the columns follow each other,
+ * each rounded up to 8 bytes */
+uint64_t dhts_bam_depth_batch_host_bytes(const dhts_depth_batch *b);
+int dhts_bam_depth_batch_fetch(dhts_ctx *bam, const dhts_depth_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
 /* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
  * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and
  * uncompressed text are read.  Bind is dhts_tabix_set_conf + dhts_tabix_sniff + dhts_tabix_resolve_schema + dhts_tabix_set_schema;

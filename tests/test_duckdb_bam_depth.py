@@ -1,0 +1,197 @@
+"""bam_depth through the DuckDB surface (tests/minihost, DHTS_PERBASE_FUNCTIONS=1): the three columns and their types, the defaults and every
+named parameter against the CPU model, both all_* flags, a BED, a region with an index, projection pushdown, a result longer than one chunk
+and than one page, every error string at bind, and the registration."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import bam_coverage_cases as K
+import bam_depth_cases as D
+import bam_depth_ref as M
+from conftest import GOLDEN, read_golden
+from test_duckdb_fasta_nuc import columns
+from test_duckdb_surface import HOST, run_host
+
+ON = {"DHTS_PERBASE_FUNCTIONS": "1"}
+BIGINT, VARCHAR = 5, 17
+SCHEMA = [("chrom", VARCHAR), ("pos", BIGINT), ("depth", BIGINT)]
+NAMED = ["all_positions", "all_reference_positions", "bed_path", "region", "index_path", "min_read_len", "min_mapq", "min_baseq", "include_deletions", "suppress_overlaps",
+         "include_flags", "require_flags", "exclude_flags"]
+
+
+def depth(path, named=(), proj=None, env=None):
+    return run_host(path, named=list(named), proj=proj, fn="bam_depth", env=dict(ON, **(env or {})))
+
+
+def as_dumped(exp, refs, names=("chrom", "pos", "depth")):
+    cols = {"chrom": [refs[t][0] for t in exp["tid"]], "pos": exp["pos"], "depth": exp["depth"]}
+    return [cols[k] for k in names]
+
+
+def model(data, rows=None, **kw):
+    kw.setdefault("exclude_flags", M.DEFAULT_EXCLUDE)                     # the table function's default
+    refs, reads = M.reads_from_bam(data)
+    return M.depth(reads, refs, rows=rows, **kw), refs
+
+
+def write(tmp_path, name, data):
+    fn = os.path.join(str(tmp_path), name)
+    open(fn, "wb").write(data)
+    return fn
+
+
+@pytest.fixture()
+def rng(tmp_path):
+    fn = os.path.join(str(tmp_path), "range.bam")
+    shutil.copy(os.path.join(GOLDEN, "range.bam"), fn)
+    shutil.copy(os.path.join(GOLDEN, "range.bam.bai"), fn + ".bai")
+    return fn, read_golden("range.bam")
+
+
+@pytest.mark.gpu
+def test_schema_and_values(rng):
+    fn, data = rng
+    rc, out, dump = depth(fn)
+    assert rc == 0 and "max_threads=1" in out, out
+    schema, sizes, cols = columns(dump)
+    assert schema == SCHEMA
+    exp, refs = model(data)
+    assert cols == as_dumped(exp, refs) and f"rows={exp['n_rows']} " in out and exp["n_rows"] > 2048
+    assert sizes[:-1] == [2048] * (len(sizes) - 1) and len(sizes) > 1                     # longer than one chunk
+    for named, kw in (([("min_mapq", "1"), ("exclude_flags", "16")], dict(min_mapq=1, exclude_flags=16)),
+                      ([("min_baseq", "30")], dict(min_baseq=30)),
+                      ([("include_deletions", "true"), ("min_baseq", "25")], dict(include_deletions=1, min_baseq=25)),
+                      ([("suppress_overlaps", "false"), ("min_read_len", "100"), ("require_flags", "64"), ("include_flags", "48")], dict(min_read_len=100, require_flags=64, include_flags=48))):
+        rc, out, dump = depth(fn, named=named)
+        assert rc == 0, out
+        assert columns(dump)[2] == as_dumped(*model(data, **kw))
+
+
+@pytest.mark.gpu
+def test_projection_and_pages(rng):
+    fn, data = rng
+    exp, refs = model(data)
+    rc, out, dump = depth(fn, proj=[2])
+    assert rc == 0 and columns(dump)[2] == as_dumped(exp, refs, ["depth"])
+    rc, out, dump = depth(fn, proj=[2, 0])
+    assert rc == 0 and columns(dump)[2] == as_dumped(exp, refs, ["depth", "chrom"])
+    # pages shorter than a chunk, and pages that are no multiple of it: the chunks stay full and the rows the same
+    for page in ("1000", "3000"):
+        rc, out, dump = depth(fn, env={"DHTS_DEPTH_PAGE_ROWS": page})
+        schema, sizes, cols = columns(dump)
+        assert rc == 0 and cols == as_dumped(exp, refs) and sizes[:-1] == [2048] * (len(sizes) - 1) and exp["n_rows"] > 3000
+
+
+@pytest.mark.gpu
+def test_both_all_flags(tmp_path):
+    data = D.bam(D.HAND_REFS, D.HAND_READS)
+    fn = write(tmp_path, "hand.bam", data)
+    base = [("min_mapq", "10"), ("min_baseq", "20"), ("min_read_len", "4")]
+    for named, rows in (([], D.HAND_ROWS), ([("include_deletions", "true")], D.HAND_ROWS_DEL), ([("all_positions", "true")], D.hand_rows_all(1)),
+                        ([("all_reference_positions", "true")], D.hand_rows_all(2)), ([("all_positions", "true"), ("all_reference_positions", "true")], D.hand_rows_all(2)),
+                        ([("all_positions", "false"), ("all_reference_positions", "false")], D.HAND_ROWS)):
+        rc, out, dump = depth(fn, named=base + named)
+        assert rc == 0, out
+        names = [n.encode() for n, _ in D.HAND_REFS]
+        assert columns(dump)[2] == [[names[t] for t, _, _ in rows], [p for _, p, _ in rows], [d for _, _, d in rows]]
+    # -a and -aa differ on an untouched contig
+    data = K.bam([("a", 40), ("b", 7)], [K.read(0, 0, 5, 30, "10M", 30)])
+    fn = write(tmp_path, "two.bam", data)
+    for named, kw in (([("all_positions", "true")], dict(all_positions=1)), ([("all_reference_positions", "true")], dict(all_positions=2))):
+        rc, out, dump = depth(fn, named=named)
+        exp, refs = model(data, **kw)
+        assert rc == 0 and columns(dump)[2] == as_dumped(exp, refs) and exp["n_rows"] == (40 if kw["all_positions"] == 1 else 47)
+
+
+@pytest.mark.gpu
+def test_bed_path(tmp_path):
+    reads = [K.read(0, 0, (i * 37) % 990, 30, ("30M", "10M5D10M", "4S26M", "12M3N12M")[i % 4], 30) for i in range(120)] + [K.read(0, 1, (i * 29) % 490, 30, "25M", 30) for i in range(40)]
+    data = K.bam(D.BED_REFS, reads)
+    fn, bed = write(tmp_path, "b.bam", data), write(tmp_path, "t.bed", D.bed_text(D.BED_ROWS))
+    refs, _ = M.reads_from_bam(data)
+    rows, _ = M.merge_bed(D.BED_ROWS, refs)
+    assert rows == D.BED_MERGED
+    for named, kw in (([], dict()), ([("all_reference_positions", "true"), ("include_deletions", "true")], dict(all_positions=2, include_deletions=1))):
+        rc, out, dump = depth(fn, named=[("bed_path", bed)] + named)
+        assert rc == 0, out
+        assert columns(dump)[2] == as_dumped(*model(data, rows=rows, **kw))
+
+
+@pytest.mark.gpu
+def test_region(rng):
+    import duckhts_amd
+    fn, data = rng
+    region = "CHROMOSOME_I:1001-1100,CHROMOSOME_I:901-1000"
+    scanned = duckhts_amd.read_bam(data, region=region, index=read_golden("range.bam.bai"))
+    refs, _ = M.reads_from_bam(data)
+    for named, kw in (([], dict()), ([("all_reference_positions", "true")], dict(all_positions=2))):
+        exp = M.depth(M.reads_from_cols(scanned), refs, rows=[(0, 1000, 1100), (0, 900, 1000)], exclude_flags=M.DEFAULT_EXCLUDE, **kw)
+        rc, out, dump = depth(fn, named=[("region", region)] + named)
+        assert rc == 0 and f"rows={exp['n_rows']} " in out, out
+        assert columns(dump)[2] == as_dumped(exp, refs)
+    rc, out, _ = depth(fn, named=[("region", "CHROMOSOME_I:1-1000,CHROMOSOME_I:900-1100")])
+    assert rc != 0 and M.err_overlap("CHROMOSOME_I:1-1000", "CHROMOSOME_I:900-1100") in out, out
+
+
+def test_bind_errors_without_a_device():
+    rc, out, _ = depth("")
+    assert rc == 3 and out == "ERROR bind: bam_depth requires a file path"
+    rc, out, _ = depth("/no/such/file.bam")
+    assert rc == 3 and out == "ERROR bind: Failed to open SAM/BAM/CRAM file: /no/such/file.bam"     # read_bam's own (bam_reader.c:446)
+    rc, out, _ = depth("x.bam", named=[("bogus", "1")])
+    assert rc == 3 and "unknown named parameter" in out
+    for k in NAMED:
+        rc, out, _ = depth("/no/such/file.bam", named=[(k, "false" if k in ("all_positions", "all_reference_positions", "include_deletions", "suppress_overlaps") else "1")])
+        assert "unknown named parameter" not in out
+    # the parameters are checked in front of the file
+    for named, msg in (([("min_mapq", "256")], M.err_range("min_mapq")), ([("min_mapq", "-1")], M.err_range("min_mapq")), ([("min_baseq", "256")], M.err_range("min_baseq")),
+                       ([("min_baseq", "-1")], M.err_range("min_baseq")), ([("include_flags", "65536")], M.err_range("include_flags")), ([("require_flags", "-1")], M.err_range("require_flags")),
+                       ([("exclude_flags", "65536")], M.err_range("exclude_flags")), ([("min_read_len", "-1")], M.ERR_READ_LEN), ([("suppress_overlaps", "true")], M.ERR_SUPPRESS),
+                       ([("bed_path", "/no/such.bed"), ("region", "c1:1-5")], M.ERR_BED_AND_REGION)):
+        rc, out, _ = depth("/no/such/file.bam", named=named)
+        assert rc == 3 and out == "ERROR bind: " + msg, out
+
+
+@pytest.mark.gpu
+def test_file_region_and_bed_errors_are_the_readers_own(rng, tmp_path):
+    fn, data = rng
+    rc, out, _ = depth(write(tmp_path, "bad.bam", b"not a bam file at all"))
+    assert rc == 3 and out == "ERROR bind: Failed to read SAM/BAM/CRAM header"
+    rc, out, _ = depth(fn, named=[("region", "nosuch:1-5")])
+    assert rc == 3 and out == "ERROR bind: No reads found for region(s): nosuch:1-5"
+    noidx = os.path.join(str(tmp_path), "noindex.bam")
+    shutil.copy(fn, noidx)
+    rc, out, _ = depth(noidx, named=[("region", "CHROMOSOME_I:1-1000")])
+    assert rc == 3 and out == "ERROR bind: Region query requires an index (.bai/.csi/.crai)"
+    rc, out, _ = depth(noidx, named=[("region", "CHROMOSOME_I:1-1000"), ("index_path", fn + ".bai"), ("all_reference_positions", "true")])
+    assert rc == 0 and "rows=1000 " in out, out
+    rc, out, _ = depth(fn, named=[("bed_path", "/no/such.bed")])
+    assert rc == 3 and out == "ERROR bind: read_bed: failed to open file: /no/such.bed"           # as bam_bedcov binds
+
+
+def test_registered_last_under_a_variable_of_its_own():
+    import duckhts_amd
+
+    def catalog(**kv):
+        env = {k: x for k, x in os.environ.items() if not (k.startswith("DHTS_") and k.endswith("_FUNCTIONS"))}
+        env.update(kv)
+        return subprocess.run([HOST, duckhts_amd.LIB_PATH, "--catalog", "-"], capture_output=True, text=True, env=env).stdout.splitlines()
+
+    default = catalog()
+    assert default and not any("bam_depth" in ln for ln in default)
+    # absent under every value of every existing variable, whose sets are what they were
+    assert catalog(DHTS_DEPTH_FUNCTIONS="1")[:-1] == default and catalog(DHTS_DEPTH_FUNCTIONS="1")[-1].startswith("TF bam_coverage ") and catalog(DHTS_DEPTH_FUNCTIONS="2") == default
+    existing = ("DHTS_SEQ_FUNCTIONS", "DHTS_INTERVAL_FUNCTIONS", "DHTS_NUC_FUNCTIONS", "DHTS_KMER_FUNCTIONS", "DHTS_TABIX_FUNCTIONS", "DHTS_COVERAGE_FUNCTIONS", "DHTS_DEPTH_FUNCTIONS")
+    for var in existing:
+        for v in ("0", "1", "2", "3"):
+            assert not any("bam_depth" in ln for ln in catalog(**{var: v})), (var, v)
+    for v in ("0", "2", "true"):
+        assert catalog(DHTS_PERBASE_FUNCTIONS=v) == default
+    line = ("TF bam_depth pushdown=1 bind=1 init=1 local_init=0 func=1 named=all_positions:1,all_reference_positions:1,bed_path:17,region:17,index_path:17,min_read_len:5,min_mapq:5,"
+            "min_baseq:5,include_deletions:1,suppress_overlaps:1,include_flags:5,require_flags:5,exclude_flags:5")
+    assert catalog(DHTS_PERBASE_FUNCTIONS="1") == default + [line]
+    others = dict(DHTS_DEPTH_FUNCTIONS="1", DHTS_COVERAGE_FUNCTIONS="2", DHTS_TABIX_FUNCTIONS="1", DHTS_KMER_FUNCTIONS="1")
+    both = catalog(DHTS_PERBASE_FUNCTIONS="1", **others)
+    assert both[-1] == line and both[:-1] == catalog(**others) and both[-2].startswith("TF bam_coverage ")

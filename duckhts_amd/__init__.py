@@ -189,7 +189,7 @@ ENC_PLAIN, ENC_CONTIG, ENC_DICT, ENC_SAMPLE, ENC_FLOAT_TEXT = 0, 1, 2, 3, 4
 EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy", "dhts_error", "dhts_open_path",
            "dhts_open_host", "dhts_open_tiled", "dhts_resident_bytes", "dhts_bgzf_index", "dhts_bgzf_table",
            "dhts_bgzf_inflate_to_host", "dhts_bam_open", "dhts_bam_header_get", "dhts_bam_set_shard", "dhts_bam_set_block_range", "dhts_shard_cut",
-           "dhts_bam_set_regions", "dhts_bam_load_index", "dhts_scan_window_stats", "dhts_bam_std_tag_count", "dhts_bam_std_tag_info", "dhts_bam_set_tag_columns", "dhts_bam_set_aux_map", "dhts_bam_set_overlap_intervals", "dhts_bam_set_overlap_bed", "dhts_bam_set_overlap_bed_path", "dhts_bam_build_index", "dhts_bam_index_bytes", "dhts_bam_rewind", "dhts_bam_next_batch", "dhts_memcpy_d2h", "dhts_sync", "dhts_kernel_time_ms",
+           "dhts_bam_set_regions", "dhts_bam_load_index", "dhts_scan_window_stats", "dhts_bgzf_repair_stats", "dhts_bam_std_tag_count", "dhts_bam_std_tag_info", "dhts_bam_set_tag_columns", "dhts_bam_set_aux_map", "dhts_bam_set_overlap_intervals", "dhts_bam_set_overlap_bed", "dhts_bam_set_overlap_bed_path", "dhts_bam_build_index", "dhts_bam_index_bytes", "dhts_bam_rewind", "dhts_bam_next_batch", "dhts_memcpy_d2h", "dhts_sync", "dhts_kernel_time_ms",
            "dhts_kernel_time_reset", "dhts_set_timing", "dhts_bcf_open", "dhts_bcf_info_get", "dhts_bcf_set_projection", "dhts_bcf_set_block_range", "dhts_bcf_set_region", "dhts_bcf_load_index",
            "dhts_bcf_rewind", "dhts_bcf_next_batch",
            "dhts_open_path_range", "dhts_open_path_shard", "dhts_bam_set_file_shard", "dhts_bam_header_bytes", "dhts_voffset",
@@ -447,6 +447,23 @@ class Context:
         self.L.dhts_scan_window_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         self._chk(self.L.dhts_scan_window_stats(self.h, C.byref(w), C.byref(b)))
         return w.value, b.value
+
+    REPAIR_STATS = ("replaced", "scratch_retries", "replaced_in_retry")
+
+    def bgzf_repair_stats(self):
+        """what the block table's corrections did on this context: {blocks re-placed from their decoded length in total, block ranges
+        decoded again after the packed scratch ran out, blocks re-placed during such a repeat} (dhts_bgzf_repair_stats)"""
+        out = (C.c_int64 * 3)()
+        self.L.dhts_bgzf_repair_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self._chk(self.L.dhts_bgzf_repair_stats(self.h, out))
+        return {k: int(out[i]) for i, k in enumerate(self.REPAIR_STATS)}
+
+    def tell(self, uoff):
+        """BGZF virtual offset of the byte at `uoff` of the inflated stream as this context numbers it (dhts_voffset): the block is the one
+        that holds the byte, which every context that reached it has decoded, so the value does not depend on ISIZE fields"""
+        self.L.dhts_voffset.restype = C.c_uint64
+        self.L.dhts_voffset.argtypes = [C.c_void_p, C.c_uint64]
+        return int(self.L.dhts_voffset(self.h, int(uoff)))
 
     def bgzf_table(self, n):
         coff = np.zeros(n, np.uint64)
@@ -1822,9 +1839,10 @@ def _concat_tables(parts, schema_cols):
     return out
 
 
-def read_bcf(src, tidy=False, columns=None, device=0, max_blocks=0, block_range=None, region=None, index=None, stats=None):
+def read_bcf(src, tidy=False, columns=None, device=0, max_blocks=0, block_range=None, region=None, index=None, stats=None, repair_stats=None):
     """Full sequential read_bcf scan (every record in file order); returns the canonical column table.
-    columns: optional projection (names or schema ids), like DuckDB's projection pushdown.  stats: a dict that receives Context.debug_tile_stats()."""
+    columns: optional projection (names or schema ids), like DuckDB's projection pushdown.  stats: a dict that receives Context.debug_tile_stats();
+    repair_stats: one that receives Context.bgzf_repair_stats()."""
     ctx = Context(device)
     try:
         ctx.open(src)
@@ -1853,6 +1871,8 @@ def read_bcf(src, tidy=False, columns=None, device=0, max_blocks=0, block_range=
                     break
         if stats is not None:
             stats.update(ctx.debug_tile_stats())
+        if repair_stats is not None:
+            repair_stats.update(ctx.bgzf_repair_stats())
         proj = [sc.schema[i] for i in sc.projection]
         cols = _concat_tables(parts, proj)
         if cols is None:
@@ -1896,10 +1916,10 @@ def std_tags():
 
 
 def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, std_tags_cols=None, aux_map=None, overlap=None, sparse=None, overlap_bed=None,
-             block_range=None, stats=None):
+             block_range=None, stats=None, repair_stats=None):
     """Full sequential scan (reference mode (i)): all rows in file order.
     block_range=(b0, b1, speculative): one shard of BGZF blocks (Context.set_block_range); the result carries first_rec_uoff / end_uoff.
-    stats: a dict that receives Context.debug_tile_stats().
+    stats: a dict that receives Context.debug_tile_stats(); repair_stats: one that receives Context.bgzf_repair_stats().
     region: the reference's region := string (rows filtered on the device); index: BAI bytes narrowing the scan window.
     sparse=(header_bytes, beg[], end[]) with a path: only the header blocks and those file ranges are staged (Context.region_segments)."""
     ctx = Context(device)
@@ -1949,6 +1969,8 @@ def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, s
         out = {"n_rows": sum(p["n_rows"] for p in parts), "status": status, "header": hdr, "first_rec_uoff": first_uoff, "end_uoff": end_uoff}
         if stats is not None:
             stats.update(ctx.debug_tile_stats())
+        if repair_stats is not None:
+            repair_stats.update(ctx.bgzf_repair_stats())
         if std_tags_cols is not None:
             out["tags"] = {"n_rows": out["n_rows"], "cols": _concat_tables(tparts, None) or []}
         if aux_map is not None:

@@ -314,6 +314,8 @@ struct dhts_ctx {
     DevBuf wg_lit[2], wg_tok[2], stg2_lit, stg2_tok;  // the workgroups' own literal / token areas ([1], stg2_*: fused launches on stream_b)
     DevBuf blk_off; bool huff_packed = false;      // packed phase-A scratch: per-block offsets into `lit` (used as the pool)
     int64_t isize_repaired = 0;                    // blocks whose table entry was replaced by their decoded length (isize_repair)
+    int64_t scratch_retries = 0, isize_repaired_retry = 0;   // ranges decoded again after DHTS_BLK_ERR_SCRATCH; blocks re-placed by those repeats (dhts_bgzf_repair_stats)
+    bool in_scratch_retry = false;                 // phase A is running as such a repeat
     bool pool_full_pending = false;                // the next phase-A range is the repeat of one that overflowed the packed scratch
     int64_t pool_per_block = 65536 + 4096;         // room per block in the packed scratch (a retry after DHTS_BLK_ERR_SCRATCH uses the full 152 KiB)
     DevBuf sg_cnt, sg_base, sg_cand, sg_hits;      // block discovery scratch
@@ -359,8 +361,11 @@ struct dhts_ctx {
     bool rg_empty_window = false;          // the index shows no chunk for the regions: the scan yields nothing
     // the chunk list of a region query (hts_itr_multi_bam / reg2intervals, hts.c:3597-3739, 3299-3354) as disjoint scan windows in file
     // order; the scan walks them one after the other.  scan_end_uoff: rows whose record starts at or behind it belong to a later window.
-    struct ScanWin { int64_t b0, b1; uint64_t first_uoff, end_uoff; };
+    // (positions that come from an index's virtual offsets are block + offset inside it: first_uoff lies in block b0, end_uoff in block
+    //  end_blk; isize_repair moves them with THAT block -- under a wrong ISIZE the old table cannot say which block an offset meant)
+    struct ScanWin { int64_t b0, b1; uint64_t first_uoff, end_uoff; int64_t first_blk, end_blk; };   // first_blk: b0, or -1 when first_uoff is the first record (a chunk that starts in the header)
     std::vector<ScanWin> wins; size_t win_cur = 0; uint64_t scan_end_uoff = ~0ull;
+    int64_t scan_first_blk = -1; uint64_t scan_first_anchor = ~0ull;   // scan_first_uoff == scan_first_anchor: it was placed in block scan_first_blk (a single index window)
     uint64_t scan_first_uoff = 0;          // inflated offset of the first record of a non-speculative scan (header end, or an index chunk start)
     // read_bcf
     bool bcf_open = false; bool bcf_tidy_req = false;

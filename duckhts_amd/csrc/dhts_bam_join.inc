@@ -104,7 +104,11 @@ extern "C" int64_t dhts_bam_set_overlap_bed_path(dhts_ctx *c, const char *path) 
             if (nb && huff_ensure(t, 0, nb, nb)) { err = dhts_error(t); break; }      // (the table may be corrected from the decoded lengths: sizes are read behind it)
             text.resize((size_t)t->h_uoff[(size_t)nb] + 64);
             std::vector<int32_t> st((size_t)nb + 1, 0);
-            const int64_t got = nb ? dhts_bgzf_inflate_to_host(t, 0, nb, text.data(), text.size(), st.data()) : 0;
+            int64_t got = nb ? dhts_bgzf_inflate_to_host(t, 0, nb, text.data(), text.size(), st.data()) : 0;
+            if (got < 0 && t->h_uoff[(size_t)nb] + 64 != text.size()) {      // a scratch retry inside moved the block table: once more with its sizes
+                text.resize((size_t)t->h_uoff[(size_t)nb] + 64);
+                got = dhts_bgzf_inflate_to_host(t, 0, nb, text.data(), text.size(), st.data());
+            }
             if (got < 0) { err = dhts_error(t); break; }
             text.resize((size_t)got); ok = true;
         } while (0);

@@ -132,7 +132,11 @@ int dhts_bam_open(dhts_ctx *c) {
         if (huff_ensure(c, 0, k, k)) return -1;              // (phase A first: the block table may be corrected from the decoded lengths)
         uint64_t total = c->h_uoff[k];
         h.resize(total + 16); bs.resize(k);
-        if (dhts_bgzf_inflate_to_host(c, 0, k, h.data(), total, bs.data()) < 0) return -1;
+        if (dhts_bgzf_inflate_to_host(c, 0, k, h.data(), total, bs.data()) < 0) {
+            if (c->h_uoff[k] != total) continue;             // a scratch retry inside moved the block table: size the buffer from it again
+            return -1;
+        }
+        total = c->h_uoff[k];                                // (an overstated ISIZE behind a scratch retry: the stream is shorter than the buffer)
         uint64_t good = total;
         for (int64_t b = 0; b < k; b++) if (bs[b] != 0) { good = c->h_uoff[b]; break; }
         // try to parse
@@ -379,6 +383,13 @@ int dhts_bam_set_shard(dhts_ctx *c, int rank, int world) {
 // a scan that starts at the top of the file begins with the block that holds the first record (headers may span many blocks)
 static void skip_header_blocks(dhts_ctx *c) {
     if (c->shard_rank != 0 || c->n_blocks <= 0) return;
+    {   // a scan that starts at an index chunk starts in the chunk's block: the table may misplace the offset while that block's ISIZE is
+        // unchecked (a block that understates its length would be passed over, and never decoded)
+        int64_t anchor = -1;
+        if (!c->wins.empty() && c->win_cur < c->wins.size() && c->wins[c->win_cur].first_uoff == c->scan_first_uoff) anchor = c->wins[c->win_cur].first_blk;
+        else if (c->wins.empty() && c->scan_first_blk >= 0 && c->scan_first_uoff == c->scan_first_anchor) anchor = c->scan_first_blk;
+        if (anchor >= c->shard_b0 && anchor < c->shard_b1) { c->next_block = anchor; return; }
+    }
     // the first block that ends behind scan_first_uoff; blocks that declare no bytes (ISIZE 0) at that position are not skipped: a damaged
     // ISIZE of 0 on the block that holds the first record has to be seen by the inflate stage (round-2 soak, seed 2001161)
     int64_t lo = 0, hi = c->n_blocks;

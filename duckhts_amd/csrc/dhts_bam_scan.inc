@@ -7,6 +7,26 @@ struct Batch {
     bool status_pending = false;      // the blocks' status words have not been looked at yet (batch_status_resolve)
 };
 static const uint32_t NONE32 = 0xffffffffu;
+// where the batch lies: the carry in front, then blocks [B.b0, B.b0 + B.nb) as the block table places them NOW.  Sets B.carry / ulen / out_base / u
+// and grows the stream buffer (the carry bytes at its front are kept).  Called again when the table moved under a batch (a scratch retry).
+static int batch_place(dhts_ctx *c, Batch &B) {
+    const uint64_t carry = c->carry_len;
+    const uint64_t inflated = c->h_uoff[B.b0 + B.nb] - c->h_uoff[B.b0];
+    const uint64_t ulen = carry + inflated;
+    if (ulen + PAD_BYTES >= (1ull << 32)) return fail(c, "batch too large");
+    DevBuf &ub = c->ubuf[c->ucur];
+    if (ub.cap < ulen + PAD_BYTES) {
+        discard_prefetch(c);
+        // grow while preserving the carry bytes at the front
+        DevBuf nbuf; if (nbuf.ensure(ulen + PAD_BYTES)) return fail(c, "hipMalloc failed");
+        if (carry) HIPCHK(c, hipMemcpyAsync(nbuf.p, ub.p, carry, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        ub.swap(nbuf);                                          // nbuf's destructor frees the old buffer
+    }
+    B.carry = carry; B.ulen = ulen; B.u = (uint8_t *)ub.p;
+    B.out_base = c->h_uoff[B.b0] - carry;                     // absolute stream offset of u[0]
+    return 0;
+}
 // `defer`: do not wait for the inflate here.  The first damaged block is found on the device (bgzf_first_bad_block -> c->d_bstat) and the
 // caller reads those four words together with its own first results, then calls batch_status_resolve: the record stage is queued behind
 // the inflate without a host round trip, and is queued again on the shortened stream in the rare case that a block was bad.
@@ -32,21 +52,9 @@ static int batch_begin(dhts_ctx *c, int64_t max_blocks, Batch &B, bool defer = f
         const int64_t ahead0 = c->shard_b1 + 8 < c->n_blocks ? c->shard_b1 + 8 : c->n_blocks;
         if (!(c->pf.valid && c->pf.b0 == b0 && c->pf.nb == nb) && huff_ensure(c, b0, nb, ahead0)) return -1;
     }
-    const uint64_t carry = c->carry_len;
-    const uint64_t inflated = c->h_uoff[b0 + nb] - c->h_uoff[b0];
-    uint64_t ulen = carry + inflated;
-    if (ulen + PAD_BYTES >= (1ull << 32)) return fail(c, "batch too large");
-    DevBuf &ub = c->ubuf[c->ucur];
-    if (ub.cap < ulen + PAD_BYTES) {
-        discard_prefetch(c);
-        // grow while preserving the carry bytes at the front
-        DevBuf nbuf; if (nbuf.ensure(ulen + PAD_BYTES)) return fail(c, "hipMalloc failed");
-        if (carry) HIPCHK(c, hipMemcpyAsync(nbuf.p, ub.p, carry, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        ub.swap(nbuf);                                          // nbuf's destructor frees the old buffer
-    }
-    uint8_t *u = (uint8_t *)ub.p;
-    const uint64_t out_base = c->h_uoff[b0] - carry;          // absolute stream offset of u[0]
+    if (batch_place(c, B)) return -1;
+    const uint64_t carry = B.carry;
+    uint64_t ulen = B.ulen; uint8_t *u = B.u; uint64_t out_base = B.out_base;
     if (c->pf.valid && c->pf.b0 == b0 && c->pf.nb == nb && c->pf.carry == carry && c->pf.ucur == c->ucur) {
         // this batch's phase B was started during the previous batch's record stage: just order the streams
         c->pf.valid = false;
@@ -74,9 +82,11 @@ static int batch_begin(dhts_ctx *c, int64_t max_blocks, Batch &B, bool defer = f
             // the packed phase-A scratch was too small for some block (data that expands into far more tokens than a BAM or BCF does):
             // decode this range again with the full 152 KiB per block
             if (attempt > 0) return fail(c, "internal: phase-A scratch exhausted twice");
-            discard_prefetch(c);
-            c->pool_per_block = (int64_t)DHTS_LIT_STRIDE + (int64_t)DHTS_TOK_STRIDE * 4; c->pool_full_pending = true; c->huff_b0 = c->huff_nb = 0;
             const int64_t ahead = c->shard_b1 + 8 < c->n_blocks ? c->shard_b1 + 8 : c->n_blocks;
+            // phase A first: it may move the block table (the blocks that failed are decoded now, isize_repair sees them); the batch is
+            // placed again from the table as it stands, then phase B writes into a buffer of that size
+            if (scratch_retry_phase_a(c, b0, nb, ahead) || batch_place(c, B)) return -1;
+            ulen = B.ulen; u = B.u; out_base = B.out_base;
             if (inflate_blocks(c, b0, nb, u, out_base, ahead)) return -1;
             HIPCHK(c, hipMemsetAsync(u + ulen, 0, PAD_BYTES, c->stream));
         }
@@ -96,9 +106,9 @@ static int batch_status_resolve(dhts_ctx *c, Batch &B, const uint32_t bst[4], in
     B.status_pending = false;
     if (bst[2] != NONE32) {
         if (attempt > 0) return fail(c, "internal: phase-A scratch exhausted twice");
-        discard_prefetch(c);
-        c->pool_per_block = (int64_t)DHTS_LIT_STRIDE + (int64_t)DHTS_TOK_STRIDE * 4; c->pool_full_pending = true; c->huff_b0 = c->huff_nb = 0;
         const int64_t ahead = c->shard_b1 + 8 < c->n_blocks ? c->shard_b1 + 8 : c->n_blocks;
+        // (as in batch_begin: phase A, then the batch placed again from the table, then phase B; the caller takes B.u / ulen / out_base anew)
+        if (scratch_retry_phase_a(c, B.b0, B.nb, ahead) || batch_place(c, B)) return -1;
         if (inflate_blocks(c, B.b0, B.nb, B.u, B.out_base, ahead)) return -1;
         HIPCHK(c, hipMemsetAsync(B.u + B.ulen, 0, PAD_BYTES, c->stream));
         hipLaunchKernelGGL(bgzf_first_bad_block, dim3(1), dim3(1024), 0, c->stream, (const int32_t *)c->blk_status.p, B.b0, (int32_t)B.nb, (uint32_t *)c->d_bstat.p);
@@ -470,7 +480,7 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
     if (batch_begin(c, max_blocks, B, !c->sam_text)) return -1;
     const bool sharded_tail = B.sharded_tail;
     bool final_batch = B.final_batch;
-    uint8_t *u = B.u; uint64_t ulen = B.ulen; const uint64_t out_base = B.out_base;
+    uint8_t *u = B.u; uint64_t ulen = B.ulen; uint64_t out_base = B.out_base;
     // SAM text (dhts_sam_scan.inc): the batch's complete lines become BAM records; the record stage below runs over them, every one complete
     const uint8_t *sam_enc = nullptr; int64_t sam_nrec = 0; uint64_t sam_carry = 0, sam_t0 = 0; bool sam_rej = false;
     if (c->sam_text) {
@@ -553,8 +563,15 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
             if (rs < 0) return -1;
             if (rs > 0) {           // the stream is shorter than assumed (or was inflated again): the tile pass starts over
                 ulen = B.ulen; final_batch = B.final_batch;
+                // (a scratch retry may have moved the block table: the batch can be longer than first assumed and lie elsewhere)
+                u = B.u; out_base = B.out_base; st.u = u;
+                if (c->first_batch && c->shard_rank == 0) start0 = c->scan_first_uoff - out_base;
                 st.ulen = ulen; st.final_batch = final_batch ? 1 : 0; c->last_stream = st;
                 ntiles = (int64_t)((ulen + TILE_BYTES - 1) / TILE_BYTES); if (ntiles < 1) ntiles = 1;
+                ENSURE(c, c->t_first, ntiles * 8); ENSURE(c, c->t_end, ntiles * 8); ENSURE(c, c->t_count, ntiles * 4); ENSURE(c, c->t_err, ntiles * 4);
+                ENSURE(c, c->t_rowbase, ntiles * 4 + 16);
+                ENSURE(c, c->t_recs, (size_t)ntiles * TL_RECS * 2 + 64); ENSURE(c, c->t_recs_first, ntiles * 8 + 64);
+                ENSURE(c, c->t2_first, ntiles * 8); ENSURE(c, c->t2_end, ntiles * 8); ENSURE(c, c->t2_count, ntiles * 4); ENSURE(c, c->t2_err, ntiles * 4);
                 spec_from = 0; spec_tries = 0; restoring = false; sk.lists = 0;
                 continue;
             }

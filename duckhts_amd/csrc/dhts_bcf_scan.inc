@@ -76,7 +76,11 @@ int dhts_bcf_open(dhts_ctx *c, int tidy_format) {
         if (huff_ensure(c, 0, k, k)) return -1;              // (phase A first: the block table may be corrected from the decoded lengths)
         uint64_t total = c->h_uoff[k];
         h.assign(total + 16, 0); bs.resize(k);
-        if (dhts_bgzf_inflate_to_host(c, 0, k, h.data(), total, bs.data()) < 0) return -1;
+        if (dhts_bgzf_inflate_to_host(c, 0, k, h.data(), total, bs.data()) < 0) {
+            if (c->h_uoff[k] != total) continue;             // a scratch retry inside moved the block table: size the buffer from it again
+            return -1;
+        }
+        total = c->h_uoff[k];                                // (an overstated ISIZE behind a scratch retry: the stream is shorter than the buffer)
         uint64_t good = total;
         for (int64_t b = 0; b < k; b++) if (bs[b] != 0) { good = c->h_uoff[b]; break; }
         const bool more = (good == total && k < c->n_blocks);

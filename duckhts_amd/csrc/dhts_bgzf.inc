@@ -493,10 +493,10 @@ static int isize_repair(dhts_ctx *c) {
     if (cnt == 0) return 0;
     std::vector<InflateMeta> m((size_t)n);
     HIPCHK(c, hipMemcpy(m.data(), c->meta.p, (size_t)n * sizeof(InflateMeta), hipMemcpyDeviceToHost));
-    int64_t first = -1;
+    int64_t first = -1, placed = 0;
     const std::vector<uint64_t> old_uoff = c->h_uoff;
     for (int64_t k = 0; k < n; k++) if (m[(size_t)k].status == 0 && m[(size_t)k].outlen != c->h_isize[(size_t)(b0 + k)] && m[(size_t)k].outlen <= 65536u) {
-        c->h_isize[(size_t)(b0 + k)] = m[(size_t)k].outlen; if (first < 0) first = b0 + k;
+        c->h_isize[(size_t)(b0 + k)] = m[(size_t)k].outlen; if (first < 0) first = b0 + k; placed++;
     }
     if (first < 0) return 0;
     const int64_t nbk = c->n_blocks;
@@ -512,10 +512,39 @@ static int isize_repair(dhts_ctx *c) {
         if (lo < nbk && w > room) w = room;
         return c->h_uoff[(size_t)lo] + w;
     };
-    c->first_rec_uoff = remap(c->first_rec_uoff); c->scan_first_uoff = remap(c->scan_first_uoff); c->scan_end_uoff = remap(c->scan_end_uoff);
-    for (auto &w : c->wins) { w.first_uoff = remap(w.first_uoff); w.end_uoff = remap(w.end_uoff); }
-    c->isize_repaired += (int64_t)cnt;
+    // a position that was computed as h_uoff[blk] + an offset inside block blk (an index's virtual offset) moves with block blk: when that
+    // block, or one in front of it inside the window, understated its length, the old table would place the offset in a later block
+    auto remap_at = [&](uint64_t u, int64_t blk) -> uint64_t {
+        if (u == ~0ull || blk < first || blk > nbk || u < old_uoff[(size_t)blk]) return remap(u);
+        return c->h_uoff[(size_t)blk] + (u - old_uoff[(size_t)blk]);
+    };
+    const bool in_win = !c->wins.empty() && c->win_cur < c->wins.size();
+    const bool first_is_win = in_win && c->scan_first_uoff == c->wins[c->win_cur].first_uoff, end_is_win = in_win && c->scan_end_uoff == c->wins[c->win_cur].end_uoff;
+    const bool first_anchored = !first_is_win && c->scan_first_blk >= 0 && c->scan_first_uoff == c->scan_first_anchor;
+    c->first_rec_uoff = remap(c->first_rec_uoff);
+    for (auto &w : c->wins) { w.first_uoff = remap_at(w.first_uoff, w.first_blk); w.end_uoff = remap_at(w.end_uoff, w.end_blk); }
+    c->scan_first_uoff = first_is_win ? c->wins[c->win_cur].first_uoff : first_anchored ? remap_at(c->scan_first_uoff, c->scan_first_blk) : remap(c->scan_first_uoff);
+    c->scan_end_uoff = end_is_win ? c->wins[c->win_cur].end_uoff : remap(c->scan_end_uoff);
+    if (first_anchored) c->scan_first_anchor = c->scan_first_uoff;
+    for (auto &w : c->wins) if (w.first_uoff < c->first_rec_uoff) w.first_uoff = c->first_rec_uoff;
+    c->isize_repaired += placed; if (c->in_scratch_retry) c->isize_repaired_retry += placed;
     if (g_debug) fprintf(stderr, "[dhts] %u blocks inflate to another length than their ISIZE field says: block table re-placed from block %lld on\n", cnt, (long long)first);
+    return 0;
+}
+// Some block of [b0, b0 + nb) found the packed scratch exhausted (DHTS_BLK_ERR_SCRATCH): phase A runs over the range again with the full
+// 152 KiB per block.  The first isize_repair passed over those blocks (their status was not 0); this one sees their decoded lengths, so the
+// block table MAY MOVE here: the caller reads its sizes and offsets from h_uoff again before it launches phase B.
+static int scratch_retry_phase_a(dhts_ctx *c, int64_t b0, int64_t nb, int64_t ahead_limit) {
+    discard_prefetch(c);
+    c->pool_per_block = (int64_t)DHTS_LIT_STRIDE + (int64_t)DHTS_TOK_STRIDE * 4; c->pool_full_pending = true; c->huff_b0 = c->huff_nb = 0;
+    c->scratch_retries++; c->in_scratch_retry = true;
+    const int rc = huff_ensure(c, b0, nb, ahead_limit);
+    c->in_scratch_retry = false;
+    return rc;
+}
+int dhts_bgzf_repair_stats(const dhts_ctx *c, int64_t out[3]) {
+    if (!c || !out) return -1;
+    out[0] = c->isize_repaired; out[1] = c->scratch_retries; out[2] = c->isize_repaired_retry;
     return 0;
 }
 
@@ -546,7 +575,12 @@ int64_t dhts_bgzf_inflate_to_host(dhts_ctx *c, int64_t blk0, int64_t nblk, uint8
         for (int64_t k = 0; k < nblk; k++) if (bs[(size_t)k] == DHTS_BLK_ERR_SCRATCH) { scratch = true; break; }
         if (!scratch) break;
         if (attempt > 0) return fail(c, "internal: phase-A scratch exhausted twice");
-        c->pool_per_block = (int64_t)DHTS_LIT_STRIDE + (int64_t)DHTS_TOK_STRIDE * 4; c->pool_full_pending = true; c->huff_b0 = c->huff_nb = 0;      // (see batch_begin)
+        // (see batch_begin) the repeat of phase A may move the table: the range is sized and placed again from what it says now
+        if (scratch_retry_phase_a(c, blk0, nblk, blk0 + nblk)) return -1;
+        base = c->h_uoff[blk0]; total = c->h_uoff[blk0 + nblk] - base;
+        if (total > cap) return fail(c, "output capacity too small (%llu needed)", (unsigned long long)total);
+        ENSURE(c, c->ubuf[0], total + PAD_BYTES);
+        HIPCHK(c, hipMemsetAsync(c->ubuf[0].p, 0, total + PAD_BYTES, c->stream));
     }
     HIPCHK(c, hipMemcpyAsync(out, c->ubuf[0].p, total, hipMemcpyDeviceToHost, c->stream));
     if (blk_status) memcpy(blk_status, bs.data(), (size_t)nblk * 4);

@@ -142,9 +142,14 @@ static int index_plain(dhts_ctx *c, const uint8_t *&d, uint64_t &n, std::vector<
         inflated.resize(tot + 16);
         std::vector<int32_t> bs(nb);
         int64_t got = dhts_bgzf_inflate_to_host(t, 0, nb, inflated.data(), tot, bs.data());
+        if (got < 0 && t->h_uoff[nb] != tot) {                // a scratch retry inside moved the block table: once more with its sizes
+            tot = t->h_uoff[nb]; inflated.resize(tot + 16);
+            got = dhts_bgzf_inflate_to_host(t, 0, nb, inflated.data(), tot, bs.data());
+        }
         dhts_destroy(t);
         HIPCHK(c, hipSetDevice(c->device));
         if (got < 0) return fail(c, "index inflate failed");
+        tot = (uint64_t)got;                                  // (the table may have shrunk behind a scratch retry)
         for (int64_t k = 0; k < nb; k++) if (bs[k] != 0) return fail(c, "index inflate failed (block %lld)", (long long)k);
         c->idx_cache.swap(inflated); c->idx_cache_len = tot; c->idx_cache_src = src0; c->idx_cache_n = n0; memcpy(c->idx_cache_key, key, 128);
         d = c->idx_cache.data(); n = tot;
@@ -306,8 +311,11 @@ static int apply_window(dhts_ctx *c, const IdxWindow &w, bool whole, bool nocoor
                     if (sw.b0 >= c->n_blocks || block_file_off(c, sw.b0) != (x.first >> 16)) return fail(c, "index does not match the file (chunk offset %llu)", (unsigned long long)(x.first >> 16));
                     int64_t be = block_of(x.second >> 16); if (be >= c->n_blocks) be = c->n_blocks - 1;
                     sw.b1 = be + 1;
-                    sw.first_uoff = c->h_uoff[sw.b0] + (x.first & 0xffff); if (sw.first_uoff < c->first_rec_uoff) sw.first_uoff = c->first_rec_uoff;
-                    sw.end_uoff = (block_file_off(c, be) == (x.second >> 16)) ? c->h_uoff[be] + (x.second & 0xffff) : c->h_uoff[be + 1];
+                    sw.first_uoff = c->h_uoff[sw.b0] + (x.first & 0xffff); sw.first_blk = sw.b0;
+                    if (sw.first_uoff < c->first_rec_uoff) { sw.first_uoff = c->first_rec_uoff; sw.first_blk = -1; }
+                    const bool in_be = block_file_off(c, be) == (x.second >> 16);
+                    sw.end_uoff = in_be ? c->h_uoff[be] + (x.second & 0xffff) : c->h_uoff[be + 1];
+                    sw.end_blk = in_be ? be : be + 1;
                     c->wins.push_back(sw);
                 }
                 b0 = c->wins[0].b0; b1 = c->wins[0].b1; first_uoff = c->wins[0].first_uoff; c->scan_end_uoff = c->wins[0].end_uoff;
@@ -322,6 +330,8 @@ static int apply_window(dhts_ctx *c, const IdxWindow &w, bool whole, bool nocoor
         if (first_uoff < c->first_rec_uoff) first_uoff = c->first_rec_uoff;
     }
     c->shard_b0 = b0; c->shard_b1 = b1; c->shard_rank = 0; c->shard_world = (b1 < c->n_blocks) ? 2 : 1; c->scan_first_uoff = first_uoff;
+    // (an index chunk start is an offset inside block b0 -- unless it lay in the header and the first record took its place)
+    c->scan_first_blk = (whole || first_uoff == c->first_rec_uoff || first_uoff < c->h_uoff[b0]) ? -1 : b0; c->scan_first_anchor = first_uoff;
     return 0;
 }
 

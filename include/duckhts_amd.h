@@ -202,6 +202,10 @@ int dhts_bam_load_index(dhts_ctx *, const void *index_bytes, uint64_t n);
 /* the scan range the regions + index produced: number of disjoint windows (the merged chunk list of hts_itr_multi_bam, hts.c:3597-3739;
  * chunks closer than DHTS_WINDOW_GAP_MB, default 32, are scanned as one window) and the BGZF blocks they cover */
 int dhts_scan_window_stats(const dhts_ctx *, int64_t *n_windows, int64_t *n_blocks);
+/* what the block table's corrections did on this context (htslib never reads a BGZF trailer's ISIZE; the scan places blocks by it and takes
+ * the decoded lengths where they differ): out[0] = blocks re-placed in total, out[1] = block ranges decoded again because the packed inflate
+ * scratch was too small, out[2] = blocks re-placed during such a repeat.                                                                  */
+int dhts_bgzf_repair_stats(const dhts_ctx *, int64_t out[3]);
 /* BCF: CSI bytes, narrows the window as above (optional).  bgzipped VCF TEXT: TBI, or CSI with a tabix header (tbx_index_load3, tbx.c:552-597)
  * -- REQUIRED for a region other than ".": the region names a sequence of the INDEX (tbx_itr_querys -> tbx_name2id), so it is resolved here;
  * the index's sequences missing from the header become ##contig lines as in vcf_hdr_read (vcf.c:2649-2668).  Rows are decided on the

@@ -117,6 +117,18 @@ class DepthStats(C.Structure):
                 ("n_positions", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PileupParams(C.Structure):
+    _fields_ = [("min_read_len", C.c_int64), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32), ("require_flags", C.c_int32), ("exclude_flags", C.c_int32),
+                ("include_flags", C.c_int32), ("include_deletions", C.c_int32), ("include_insertions", C.c_int32), ("distinguish_strands", C.c_int32),
+                ("min_nucleotide_depth", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PileupStats(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_flag_filtered", C.c_uint64), ("n_unplaced", C.c_uint64), ("n_short", C.c_uint64), ("n_low_mapq", C.c_uint64),
+                ("n_outside", C.c_uint64), ("n_counted", C.c_uint64), ("n_target_rows", C.c_uint64), ("table_bytes", C.c_uint64), ("n_result_rows", C.c_uint64),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TabixMap(C.Structure):
     _fields_ = [("pair_off", C.c_void_p), ("valid", C.c_void_p), ("n_pairs", C.c_uint64), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p), ("key_nbytes", C.c_uint64),
                 ("val_off", C.c_void_p), ("val_bytes", C.c_void_p), ("val_nbytes", C.c_uint64)]
@@ -179,6 +191,10 @@ COVERAGE_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4)              # FLAG
 DEPTH_COLUMNS = ["tid", "pos", "depth"]
 DEPTH_DTYPES = (np.int32, np.int64, np.int32)
 DEPTH_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4)                 # FLAG, RNAME, POS, MAPQ: the columns of the scan bam_depth accumulates (no string column)
+PILEUP_COLUMNS = ["tid", "pos", "strand", "nucleotide", "count"]
+PILEUP_DTYPES = (np.int32, np.int64, np.uint8, np.uint8, np.int32)           # strand and nucleotide: one ASCII byte per row
+PILEUP_SYMBOLS = b"ACGTN=-+"                                                # the order of the symbols inside a position and strand
+PILEUP_COLMASK = DEPTH_COLMASK                                              # the columns of the scan bam_pileup accumulates (SEQ and QUAL are read in their binary form)
 BEDCOV_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4)                # FLAG, RNAME, POS, MAPQ: no string column (the CIGARs are read in their binary form)
 BINS_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 7)        # FLAG, RNAME, POS, MAPQ, PNEXT: no string column
 
@@ -201,6 +217,7 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_bam_bedcov_open", "dhts_bam_bedcov_accumulate", "dhts_bam_bedcov_scan", "dhts_bam_bedcov_stats", "dhts_bam_bedcov_next", "dhts_bam_bedcov_batch_host_bytes", "dhts_bam_bedcov_batch_fetch",
            "dhts_bam_coverage_open", "dhts_bam_coverage_accumulate", "dhts_bam_coverage_scan", "dhts_bam_coverage_stats", "dhts_bam_coverage_next", "dhts_bam_coverage_batch_host_bytes", "dhts_bam_coverage_batch_fetch",
            "dhts_bam_depth_open", "dhts_bam_depth_accumulate", "dhts_bam_depth_scan", "dhts_bam_depth_stats", "dhts_bam_depth_next", "dhts_bam_depth_batch_host_bytes", "dhts_bam_depth_batch_fetch",
+           "dhts_bam_pileup_open", "dhts_bam_pileup_accumulate", "dhts_bam_pileup_scan", "dhts_bam_pileup_stats", "dhts_bam_pileup_next", "dhts_bam_pileup_batch_host_bytes", "dhts_bam_pileup_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
            "dhts_udf_upload", "dhts_udf_apply", "dhts_udf_result_host_bytes", "dhts_udf_fetch", "dhts_udf_seq_kmers", "dhts_udf_kmers_host_bytes", "dhts_udf_kmers_fetch"]
@@ -330,6 +347,15 @@ def lib():
         L.dhts_bam_depth_batch_host_bytes.restype = C.c_uint64
         L.dhts_bam_depth_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_bam_depth_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_bam_pileup_open.argtypes = [C.c_void_p, C.POINTER(PileupParams)]
+        L.dhts_bam_pileup_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
+        L.dhts_bam_pileup_scan.argtypes = [C.c_void_p, C.c_int64]
+        L.dhts_bam_pileup_stats.argtypes = [C.c_void_p, C.POINTER(PileupStats)]
+        L.dhts_bam_pileup_next.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(BedBatch)]
+        L.dhts_bam_pileup_batch_host_bytes.restype = C.c_uint64
+        L.dhts_bam_pileup_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
+        L.dhts_bam_pileup_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_debug_pileup_add_form.argtypes = [C.c_void_p, C.c_int]
         L.dhts_debug_coverage_max_table_bytes.restype = None
         L.dhts_debug_coverage_max_table_bytes.argtypes = [C.c_uint64]
         L.dhts_debug_bedcov_max_rows.restype = None
@@ -921,6 +947,62 @@ class Context:
         out = {"n_rows": n}
         for i in range(b.n_cols):
             name, dt = DEPTH_COLUMNS[host[i].col], DEPTH_DTYPES[host[i].col]
+            if not (mask >> host[i].col) & 1:
+                assert not b.cols[i].fixed and not host[i].fixed
+                out[name] = None
+            elif n == 0:
+                out[name] = np.zeros(0, dt)
+            else:
+                off = host[i].fixed - arena.ctypes.data
+                out[name] = arena[off:off + n * np.dtype(dt).itemsize].view(dt).copy()
+        return out, int(b.status)
+
+    # ---- bam_pileup (the batch has dhts_bed_batch's layout) ----
+    def bam_pileup_open(self, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0, include_deletions=0, include_insertions=0,
+                        distinguish_strands=0, min_nucleotide_depth=1):
+        """after bam_open and the optional set_regions / load_index: the target rows, the count table and the counters, zeroed.  The
+        parameters are taken as given (the C ABI's rule)."""
+        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
+        p = PileupParams(clip(min_read_len, 63), clip(min_mapq, 31), clip(min_baseq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31),
+                         clip(include_deletions, 31), clip(include_insertions, 31), clip(distinguish_strands, 31), clip(min_nucleotide_depth, 31), 0)
+        self._chk(self.L.dhts_bam_pileup_open(self.h, C.byref(p)))
+
+    def bam_pileup_add_form(self, form):
+        """tests and tools/bench_pileup.py: the add kernel's form (dhts_debug_pileup_add_form)"""
+        self._chk(self.L.dhts_debug_pileup_add_form(self.h, form))
+
+    def bam_pileup_accumulate(self, b):
+        """b: the batch next_batch returned last on this context"""
+        self._chk(self.L.dhts_bam_pileup_accumulate(self.h, C.byref(b)))
+
+    def bam_pileup_scan(self, max_blocks=0):
+        """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
+        rc = self.L.dhts_bam_pileup_scan(self.h, max_blocks)
+        if rc < 0:
+            msg = self.L.dhts_error(self.h).decode()
+            if self.bam_pileup_stats()["status"] == 0:                    # a call failed (a stream that ended on an error has set its status)
+                raise DhtsError(msg)
+        return rc
+
+    def bam_pileup_stats(self):
+        st = PileupStats()
+        self._chk(self.L.dhts_bam_pileup_stats(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in PileupStats._fields_ if k != "reserved"}
+
+    def bam_pileup_next(self, max_rows=0, columns=None):
+        """the next page of the result: ({"n_rows", "tid": int32, "pos": int64 (1-based), "strand", "nucleotide": uint8 (ASCII), "count": int32
+        arrays; None for a column that `columns` (names of PILEUP_COLUMNS; None: all) leaves out -- the batch has a null pointer there}, status)"""
+        mask = sum(1 << PILEUP_COLUMNS.index(k) for k in set(columns)) if columns is not None else 31
+        b = BedBatch()
+        self._chk(self.L.dhts_bam_pileup_next(self.h, max_rows, mask, C.byref(b)))
+        need = int(self.L.dhts_bam_pileup_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        self._chk(self.L.dhts_bam_pileup_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
+        n = int(b.n_rows)
+        out = {"n_rows": n}
+        for i in range(b.n_cols):
+            name, dt = PILEUP_COLUMNS[host[i].col], PILEUP_DTYPES[host[i].col]
             if not (mask >> host[i].col) & 1:
                 assert not b.cols[i].fixed and not host[i].fixed
                 out[name] = None
@@ -2148,6 +2230,48 @@ def bam_depth(src, region=None, index=None, bed=None, max_blocks=0, max_rows=0, 
     finally:
         if bctx is not None:
             bctx.close()
+        ctx.close()
+
+
+def bam_pileup(src, region=None, index=None, max_blocks=0, max_rows=0, columns=None, device=0, min_read_len=0, min_mapq=0, min_baseq=0,
+               include_flags=0, require_flags=0, exclude_flags=0x704, include_deletions=1, include_insertions=0, distinguish_strands=1, min_nucleotide_depth=1,
+               add_form=0):
+    """bam_pileup(path, region :=, index_path :=, min_read_len :=, min_mapq :=, min_baseq :=, include_flags :=, require_flags :=, exclude_flags :=,
+    include_deletions :=, include_insertions :=, distinguish_strands :=, min_nucleotide_depth :=): per position and strand the number of A C G T
+    N = - + on it, counted on the device (the contract: include/duckhts_amd.h), streamed page by page and concatenated here.  {"n_rows", "tid":
+    int32 (the contig's id), "pos": int64 (1-based), "strand", "nucleotide": uint8 (ASCII), "count": int32 arrays -- None for a column that
+    `columns` leaves out --, "contigs": the names by id, "stats": the step counters, the target rows, the table's bytes and the result's rows,
+    "status": how the stream ended}.  index: BAI / CSI bytes narrowing the scan of a region query; max_rows: rows per page; add_form: the
+    debug hook's value (tests and benchmarks)."""
+    ctx = Context(device)
+    try:
+        ctx.open(src)
+        ctx.bgzf_index()
+        hdr = ctx.bam_open()
+        if region is not None:
+            if not ctx.set_regions(region):
+                raise DhtsError(f"No reads found for region(s): {region}")
+            if index is not None:
+                ctx.load_index(index)
+        if add_form:
+            ctx.bam_pileup_add_form(add_form)
+        ctx.bam_pileup_open(min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, include_deletions, include_insertions, distinguish_strands,
+                            min_nucleotide_depth)
+        status = ctx.bam_pileup_scan(max_blocks)
+        parts = []
+        while True:
+            cols, st = ctx.bam_pileup_next(max_rows, columns)
+            parts.append(cols)
+            if st != 0:
+                break
+        out = {k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts]) for k in PILEUP_COLUMNS}
+        out["n_rows"] = sum(p["n_rows"] for p in parts)
+        out["pages"] = [p["n_rows"] for p in parts]
+        out["contigs"] = [n.encode() if isinstance(n, str) else bytes(n) for n in hdr["ref_names"]]
+        out["stats"] = {k: v for k, v in ctx.bam_pileup_stats().items() if k != "status"}
+        out["status"] = status
+        return out
+    finally:
         ctx.close()
 
 

@@ -20,6 +20,7 @@
 #include "bam_bedcov.hip"
 #include "bam_coverage.hip"
 #include "bam_depth.hip"
+#include "bam_pileup.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -242,6 +243,14 @@ struct DepthState : DepLayout {
     uint64_t n_bed_skipped = 0, n_positions = 0, o_next = 0, o_within = 0; std::vector<uint64_t> row_off; std::vector<dhts_col> out;
     DevBuf steps, touched, row_tid, step, rlen, k0, k1, tsum, toff, part, rowres, pagetiles, out_tid, out_pos, out_depth;
 };
+// bam_pileup (bam_pileup.hip, dhts_bam_pileup.inc): the parameters, the layout (diff: the count table, S words per slot), the step counters,
+// per-batch scratch, and of a result the result index in front of every tile of words (toff) and of every sorted row (row_off), where the next
+// page starts and the page's columns
+struct PileupState : DepLayout {
+    bool open = false, res_ready = false; dhts_pileup_params P; int32_t n_ref = 0, status = 0, form = 0;
+    uint64_t n_result_rows = 0, o_next = 0, o_within = 0; std::vector<uint64_t> row_off; std::vector<dhts_col> out;
+    DevBuf steps, row_tid, step, rlen, k0, k1, toff, part, rowres, pagetiles, out_tid, out_pos, out_strand, out_nuc, out_count;
+};
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
 struct UdfState {
@@ -289,6 +298,7 @@ struct dhts_ctx {
     BedcovState cov;
     CoverageState dep;
     DepthState dpt;
+    PileupState pil;
     UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
@@ -588,6 +598,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_bedcov.inc"
 #include "dhts_bam_coverage.inc"
 #include "dhts_bam_depth.inc"
+#include "dhts_bam_pileup.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

@@ -18,7 +18,8 @@ void dhts_debug_coverage_max_table_bytes(uint64_t n) { g_coverage_max_table_byte
 // are sorted by (contig, start) with the empty ones left out (o_k: a row's index among the sorted ones, -1 for an empty one), neighbours on one
 // contig must not overlap (tok(i): what row i was given as, for the error), every sorted row gets a span of (end - beg) + 1 slots of the
 // difference table rounded up to the tile, and the rows, tid_first, tile_row and the zeroed table go to the device (queued on the stream).
-static int dep_layout(dhts_ctx *c, DepLayout &S, const char *fn, const std::function<const char *(size_t)> &tok) {
+// bpp / noun: the table's bytes per slot and what the cap's error calls it (bam_pileup's count table has 32 or 64 bytes per position).
+static int dep_layout(dhts_ctx *c, DepLayout &S, const char *fn, const std::function<const char *(size_t)> &tok, uint64_t bpp = 4, const char *noun = "depth table") {
     const size_t n_ref = c->ref_len.size(), n_out = S.o_tid.size();
     std::vector<uint32_t> order;
     for (size_t i = 0; i < n_out; i++) if (S.o_end[i] > S.o_beg[i]) order.push_back((uint32_t)i);
@@ -43,18 +44,18 @@ static int dep_layout(dhts_ctx *c, DepLayout &S, const char *fn, const std::func
     }
     S.s_base[R] = slots;
     for (size_t t = 0; t < n_ref; t++) tid_first[t + 1] += tid_first[t];
-    if (slots * 4 > g_coverage_max_table_bytes)
-        return fail(c, "%s: the depth table needs %llu bytes (4 per position of every row); at most %llu are supported (fewer or shorter regions)",
-                    fn, (unsigned long long)(slots * 4), (unsigned long long)g_coverage_max_table_bytes);
+    if (slots * bpp > g_coverage_max_table_bytes)
+        return fail(c, "%s: the %s needs %llu bytes (%llu per position of every row); at most %llu are supported (fewer or shorter regions)",
+                    fn, noun, (unsigned long long)(slots * bpp), (unsigned long long)bpp, (unsigned long long)g_coverage_max_table_bytes);
     const uint64_t ntiles = slots / DEP_TILE;
     std::vector<uint32_t> tile_row((size_t)ntiles + 1, 0);
     for (size_t k = 0; k < R; k++) for (uint64_t t = S.s_base[k] / DEP_TILE; t < S.s_base[k + 1] / DEP_TILE; t++) tile_row[(size_t)t] = (uint32_t)k;
     HIPCHK(c, hipSetDevice(c->device));
     ENSURE(c, S.tid_first, (n_ref + 1) * 4 + 64); ENSURE(c, S.rbeg, (R + 1) * 8 + 64); ENSURE(c, S.rend, (R + 1) * 8 + 64); ENSURE(c, S.rbase, (R + 1) * 8 + 64);
-    ENSURE(c, S.tile_row, (size_t)(ntiles + 1) * 4 + 64); ENSURE(c, S.diff, (size_t)slots * 4 + 64);
+    ENSURE(c, S.tile_row, (size_t)(ntiles + 1) * 4 + 64); ENSURE(c, S.diff, (size_t)(slots * bpp) + 64);
     {
         KTimer tm(c, DHTS_K_BCF_CHECK);
-        HIPCHK(c, hipMemsetAsync(S.diff.p, 0, (size_t)slots * 4 + 64, c->stream));
+        HIPCHK(c, hipMemsetAsync(S.diff.p, 0, (size_t)(slots * bpp) + 64, c->stream));
     }
     HIPCHK(c, hipMemcpyAsync(S.tid_first.p, tid_first.data(), (n_ref + 1) * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(S.rbeg.p, S.s_beg.data(), (R + 1) * 8, hipMemcpyHostToDevice, c->stream));

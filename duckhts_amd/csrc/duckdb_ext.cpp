@@ -40,6 +40,7 @@ static double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); r
 #include "duckdb_bedcov.inc"
 #include "duckdb_coverage.inc"
 #include "duckdb_depth.inc"
+#include "duckdb_pileup.inc"
 #include "duckdb_tabix.inc"
 #include "duckdb_udf.inc"
 
@@ -76,6 +77,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     if (const char *e = getenv("DHTS_DEPTH_FUNCTIONS")) if (atoi(e) == 1) register_bam_coverage_function(conn);
     // bam_depth (PLAN.md 10.4 / 10.7.3) comes last, behind a variable of its own, DHTS_PERBASE_FUNCTIONS=1: no value of an existing variable changes its set
     if (const char *e = getenv("DHTS_PERBASE_FUNCTIONS")) if (atoi(e) == 1) register_bam_depth_function(conn);
+    // bam_pileup (PLAN.md 10.4 / 10.7.3) comes last, behind a variable of its own, DHTS_PILEUP_FUNCTIONS=1: no value of an existing variable changes its set
+    if (const char *e = getenv("DHTS_PILEUP_FUNCTIONS")) if (atoi(e) == 1) register_bam_pileup_function(conn);
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);
     return true;
 }

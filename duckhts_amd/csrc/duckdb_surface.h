@@ -191,7 +191,8 @@ enum ColKind { COL_NULL = 0,        // a slot outside the projection: NULL
                COL_INT32,           // INTEGER from a 64-bit value: NULL where valid is 0 or the value does not fit
                COL_MAP,             // MAP(VARCHAR, VARCHAR) from a dhts_tabix_map
                COL_WIDEN32,         // BIGINT from a 32-bit value, never NULL
-               COL_DICT32 };        // VARCHAR, never NULL: fixed holds 32-bit ids, off / bytes the text of every id (off[id] .. off[id + 1])
+               COL_DICT32,          // VARCHAR, never NULL: fixed holds 32-bit ids, off / bytes the text of every id (off[id] .. off[id + 1])
+               COL_CHAR8 };         // VARCHAR of one character, never NULL: fixed holds one byte per row
 static inline int kind_of_type(int32_t t) { return t == DHTS_T_VARCHAR ? COL_STRING : t == DHTS_T_INTEGER ? COL_INT32 : COL_FIXED8; }
 struct ColBatch {
     std::vector<dhts_col> host; int64_t n = 0, pos = 0; int32_t status = 0; bool done = false;   // HOST pointers; rows [pos, n) are still to be handed out
@@ -253,6 +254,11 @@ static inline void fill_col(duckdb_vector vec, int kind, const dhts_col &hc, con
     case COL_DICT32: {
         const int32_t *src = (const int32_t *)hc.fixed;
         for (idx_t r = 0; r < take; r++) { const int32_t id = src[s + r]; assign_len(vec, row_count + r, (const char *)hc.bytes + hc.off[id], hc.off[id + 1] - hc.off[id]); }
+        break;
+    }
+    case COL_CHAR8: {
+        const char *src = (const char *)hc.fixed;
+        for (idx_t r = 0; r < take; r++) assign_len(vec, row_count + r, src + s + r, 1);
         break;
     }
     default: for (idx_t r = 0; r < take; r++) set_null(vec, row_count + r); break;

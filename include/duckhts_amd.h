@@ -795,6 +795,90 @@ int dhts_bam_depth_next(dhts_ctx *bam, int64_t max_rows, uint32_t colmask, dhts_
 uint64_t dhts_bam_depth_batch_host_bytes(const dhts_depth_batch *b);
 int dhts_bam_depth_batch_fetch(dhts_ctx *bam, const dhts_depth_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- bam_pileup ------------------------------------------------------------------------------
+ * Per position and strand: how many A, C, G, T, N, '=', deletions and insertions lie on it (an Rsamtools-style base-level pileup), counted
+ * into a table in HBM from the columns, the binary CIGARs and the SEQ and QUAL bytes a read_bam batch leaves there, and streamed page by
+ * page as the compaction of that table.  The reference has only a plan for it (.github/PLAN.md, Phase 10, 10.4 / 10.7.3), so this is the
+ * specification.
+ *   Input, the six steps with their 64-bit counters, the read interval, the effective CIGAR (the CG tag's) and the rule that a read with
+ *     FLAG & 4 contributes nothing: exactly bam_coverage's.
+ *   Target rows: exactly bam_coverage's -- one per @SQ, or one per region in the order given, clipped to ref_len; regions that overlap are
+ *     refused with an error that names the two; empty rows emit nothing.  There is no BED and no all_positions here.
+ *   Symbols, eight, in this order: A C G T N = - +.
+ *     A base of an M, = or X operation at reference position x inside a row, with query index q, counts iff q >= l_seq or
+ *       qual[q] >= min_baseq (bam_coverage's rule).  Its symbol comes from the 4-bit code of SEQ: 1, 2, 4, 8 give A, C, G, T; 0 gives '=';
+ *       every other code (15 and the ambiguity codes) gives N; q >= l_seq (SEQ = *, or a CIGAR longer than l_seq) gives N.
+ *     '-' only with include_deletions: every reference position of a D operation inside a row counts, whatever min_baseq and the qualities
+ *       of the bases around it are; a leading or trailing D counts.
+ *     '+' only with include_insertions: every I operation of non-zero length adds 1 at its anchor, the reference position x - 1 where x is
+ *       the reference position the walk stands on at the I.  The last operation before the I that consumed reference must be M, =, X or D,
+ *       not N; S, I, P, H and zero-length operations in between are skipped; the anchor must lie inside a row; an I with no reference
+ *       consumed before it has no anchor and does not count; qualities play no part.  Two I operations with the same anchor count twice
+ *       (htslib's pileup sees one event there).
+ *     N and P operations never count.
+ *   Strand: with distinguish_strands '-' iff FLAG & 16, else '+'; without it '*'.
+ *   Result: one row per (position, strand, symbol) whose count is at least min_nucleotide_depth: chrom (here: the contig's id, int32), pos
+ *     (1-based, int64), strand (uint8, ASCII '+', '-' or '*'), nucleotide (uint8, ASCII of the eight symbols), count (int32).  Order: the
+ *     target rows in result order, then positions ascending, then '+' before '-', then the symbols in the order above.
+ *   Parameters: min_read_len >= 0; min_mapq, min_baseq 0..255; the three masks 0..65535; include_deletions, include_insertions,
+ *     distinguish_strands 0..1; min_nucleotide_depth >= 1.  This ABI takes them as given; the table function and the Python function default
+ *     exclude_flags to 0x704, include_deletions to 1, include_insertions to 0, distinguish_strands to 1 (Rsamtools' PileupParam),
+ *     min_nucleotide_depth to 1 and the rest to 0.
+ *   Limits: counts are 32-bit.  The count table takes 4 bytes x 8 symbols x (2 with strands, else 1) per position of every target row, each
+ *     row's span laid out as in bam_coverage ((end - beg) + 1 positions rounded up to 1,024 positions).  dhts_debug_coverage_max_table_bytes
+ *     and the 16 GiB cap apply; beyond the cap open fails with "bam_pileup: the count table needs N bytes (B per position of every row); at
+ *     most C are supported (fewer or shorter regions)".  A whole human genome therefore needs a region per contig: chr1 with strands is
+ *     15.9 GB and fits.  A shard or block range is refused; a stream that ends on an error has its rows counted and its status carried.
+ *   Not in this contract: mate-overlap handling, max_depth (for the reason given under bam_coverage), reference / CRAM, several files, a
+ *     BED, a wide one-row-per-position form, and sweeping a genome in several scans.
+ *   Method: one atomic add per counted base, SEQ read as aligned words by the eight lanes that read QUAL; the result is the table's words
+ *     compacted tile by tile behind a 64-bit carry (csrc/bam_pileup.hip).
+ * All errors are prefixed "bam_pileup:".  Every call on a context in the wrong state fails with a dhts_error that names what is missing. */
+enum { DHTS_PILEUP_CHROM = 0, DHTS_PILEUP_POS, DHTS_PILEUP_STRAND, DHTS_PILEUP_NUCLEOTIDE, DHTS_PILEUP_COUNT, DHTS_PILEUP_COL_COUNT };
+typedef struct {
+    int64_t min_read_len;    /* >= 0                                                                          */
+    int32_t min_mapq;        /* 0..255                                                                        */
+    int32_t min_baseq;       /* 0..255                                                                        */
+    int32_t require_flags, exclude_flags, include_flags;   /* 0..65535                                        */
+    int32_t include_deletions;                             /* 0 or 1                                          */
+    int32_t include_insertions;                            /* 0 or 1                                          */
+    int32_t distinguish_strands;                           /* 0 or 1                                          */
+    int32_t min_nucleotide_depth;                          /* >= 1                                            */
+    int32_t reserved;
+} dhts_pileup_params;
+typedef struct {
+    uint64_t n_rows, n_flag_filtered, n_unplaced, n_short, n_low_mapq, n_outside, n_counted;
+    uint64_t n_target_rows;  /* target rows (regions or @SQ lines)                                             */
+    uint64_t table_bytes;    /* bytes of the count table                                                       */
+    uint64_t n_result_rows;  /* rows of the whole result: valid once a result was taken (dhts_bam_pileup_next), 0 before */
+    int32_t status;          /* as in dhts_coverage_stats                                                      */
+    int32_t reserved;
+} dhts_pileup_stats;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows follow, 1 = the last page                                                                    */
+    int32_t n_cols;          /* DHTS_PILEUP_COL_COUNT, in that order                                                                       */
+    const dhts_col *cols;    /* host array of descriptors, DEVICE pointers inside: fixed = int32 (chrom, count), int64 (pos) or uint8 (strand,
+                                nucleotide) per row, a null pointer for a column colmask left out; no row is NULL and valid stays null       */
+} dhts_pileup_batch;
+/* after dhts_bam_open and the optional dhts_bam_set_regions / dhts_bam_load_index: the target rows, the count table and the counters,
+ * zeroed.  A second open starts a new count. */
+int dhts_bam_pileup_open(dhts_ctx *bam, const dhts_pileup_params *params);
+/* the batch dhts_bam_next_batch returned LAST on this context, as in dhts_bam_coverage_accumulate (SEQ is read where the scan left it, too).
+ * Starts a result over: the table and the counters stay intact, the next dhts_bam_pileup_next returns the first page of the new result. */
+int dhts_bam_pileup_accumulate(dhts_ctx *bam, const dhts_bam_batch *batch);
+/* dhts_bam_next_batch + accumulate to the end of the stream; returns as dhts_bam_coverage_scan does */
+int dhts_bam_pileup_scan(dhts_ctx *bam, int64_t max_blocks);
+int dhts_bam_pileup_stats(dhts_ctx *bam, dhts_pileup_stats *out);
+/* the next <= max_rows rows of the result (0 = 1,048,576 rows: 18 MiB with all five columns).  colmask: bit DHTS_PILEUP_* set = the column
+ * is written and fetched.  The first call after open or accumulate counts the rows of the result from the table, which stays as it is.  The
+ * page's columns stay valid until the next call on the context. */
+int dhts_bam_pileup_next(dhts_ctx *bam, int64_t max_rows, uint32_t colmask, dhts_pileup_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst (null where the batch has none); the columns follow each other,
+ * each rounded up to 8 bytes */
+uint64_t dhts_bam_pileup_batch_host_bytes(const dhts_pileup_batch *b);
+int dhts_bam_pileup_batch_fetch(dhts_ctx *bam, const dhts_pileup_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
 /* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
  * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and
  * uncompressed text are read.  Bind is dhts_tabix_set_conf + dhts_tabix_sniff + dhts_tabix_resolve_schema + dhts_tabix_set_schema;

@@ -28,9 +28,13 @@ int64_t dhts_debug_fastq_records(dhts_ctx *, uint8_t *dst, uint64_t cap, int64_t
 int64_t dhts_debug_bed_walk(dhts_ctx *, double *ms_line_table, double *ms_walk);
 /* tests: the most BED rows dhts_bam_bedcov_open takes, for the whole process (0: the contract's 2^27) */
 void dhts_debug_bedcov_max_rows(uint64_t n);
-/* tests: the most bytes the depth table of dhts_bam_coverage_open or dhts_bam_depth_open may take, for the whole process (0: the contract's
- * 16 GiB) */
+/* tests: the most bytes the depth table of dhts_bam_coverage_open or dhts_bam_depth_open, or the count table of dhts_bam_pileup_open, may take,
+ * for the whole process (0: the contract's 16 GiB) */
 void dhts_debug_coverage_max_table_bytes(uint64_t n);
+/* tests, tools/bench_pileup.py: the form of bam_pileup's add kernel on this context from the next accumulate on: 0 the default (the window form), 1 direct (one
+ * atomic add per counted base into the table), 2 window (the workgroup counts 512 positions of one row in LDS and adds the non-zero words to
+ * the table when the window moves).  Any other value fails with a dhts_error. */
+int dhts_debug_pileup_add_form(dhts_ctx *, int form);
 /* tools/dbg: phase A (kernel 0: lane per block, 1: wave per block) / phase B alone over blocks [b0, b0 + nb); ms per launch */
 double dhts_debug_time_huff(dhts_ctx *, int64_t b0, int64_t nb, int reps);
 double dhts_debug_time_lz(dhts_ctx *, int64_t b0, int64_t nb, int reps);

@@ -13,11 +13,14 @@
 //           Output is append-only: literal bytes and one 32-bit token per LZ77 match.  No
 //           loads depend on earlier stores, so lanes never stall on the LZ77 window.
 //  phase B  bgzf_lz_resolve  : ONE WAVE PER BGZF BLOCK.  Tokens are consumed 64 at a time
-//           (coalesced), wave prefix sums give every token's destination, literals are
-//           placed lane-parallel, matches are replayed in dependency rounds in a 4 KiB LDS
+//           (coalesced), wave prefix sums give every token's destination, literal runs of
+//           up to 32 bytes are placed lane-parallel through overlapping 8/4/2-byte windows
+//           (like ready matches), matches are replayed in dependency rounds in a 4 KiB LDS
 //           ring (older sources are read back from the block's own flushed output), every
-//           half ring is CRC-32'd from LDS (slice-by-4, per-lane pieces combined with
-//           x^(8n) mod P) and flushed to HBM with 16-byte coalesced stores.
+//           half ring is CRC-32'd from LDS (slice-by-4; one state per lane, carried from
+//           chunk to chunk and combined once per block, every multiplication by x^(8n)
+//           mod P being eight look-ups in the constant's nibble table) and flushed to HBM
+//           with 16-byte coalesced stores.
 #include "dhts_common.h"
 
 // ------------------------------------------------------------------------------------
@@ -595,11 +598,13 @@ __device__ __forceinline__ void lds_st_n(uint8_t *p, uint64_t v, uint32_t n) {  
 static_assert(BR_R >= BR_FLUSH + BR_SPAN + 265u, "far sources must always be flushed");
 #define B_WIN 0
 #define B_CRCT (BR_R)                    /* u32 [4][256] slice-by-4 tables */
-#define B_RING (B_CRCT + 4096)           /* u8 [2048] literal staging ring */
-#define B_LDS_BYTES (B_RING + 2048)
+#define BR_LMIRROR 32u                   /* bytes of the staging ring kept twice; the longest literal run copied through windows */
+#define B_RING (B_CRCT + 4096)           /* u8 [2048 + BR_LMIRROR] literal staging ring and the mirror of its first bytes */
+#define B_LDS_BYTES (B_RING + 2048 + BR_LMIRROR)
 #define B_NULLTOK 0xffffffffu
 // knock-out experiments (tools/dbg/time_lz.py; the output is wrong on purpose): -DB_EXP_NOCRC, -DB_EXP_NOLIT, -DB_EXP_NOFAR, -DB_EXP_NOROUNDS,
-// -DB_EXP_NOREPLAY, -DB_EXP_NOSTORE leave out one part of the kernel each, so that its cost can be read off the launch time
+// -DB_EXP_NOREPLAY, -DB_EXP_NOSTORE, -DB_EXP_NOEPI (the per-block CRC epilogue: the tail's table loop and the combine of the 64 states)
+// leave out one part of the kernel each, so that its cost can be read off the launch time
 // (NOROUNDS leaves out the windowed far copies too: round 1 makes them; NOFAR turns far matches into near ones and so removes their loads)
 #ifdef B_EXP_NOSTORE
 #define B_EXP_STORE(p_, v_) do { asm volatile("" :: "v"((v_).x), "v"((v_).y), "v"((v_).z), "v"((v_).w)); } while (0)
@@ -659,22 +664,27 @@ __device__ __forceinline__ uint32_t crc_xpow8(uint32_t nbytes) {
 }
 
 // Block-independent CRC constants, computed once per context by crc_const_init:
-//   [0,64)  K_lane = x^(8*BR_PIECE*(63-lane)),  [64] x^(8*BR_FLUSH),  [65,82) x^(8*2^k) for k < 17,  [96,1120) slice-by-4 tables,
-//   [1120,1248) products of every nibble position with x^(8*(BR_FLUSH-BR_PIECE))
-#define CRCC_K 0
-#define CRCC_XF 64
+//   [0,65) unused,  [65,82) x^(8*2^k) for k < 17 (the device compressor's input CRC),  [96,1120) slice-by-4 tables,
+//   [1120,1248) the nibble table of x^(8*(BR_FLUSH-BR_PIECE)),  [1248,2016) the nibble tables of x^(8*BR_PIECE*2^k), k < 6,
+//   [2016,6112) the nibble tables of x^(8*w), w < BR_PIECE
+// The nibble table of a constant K is u32 [8][16]: entry 16j + v = (v << 4j) * K, so a state times K is the XOR of eight look-ups.
 #define CRCC_XP2 65
 #define CRCC_TAB 96
 #define CRCC_MK (96 + 1024)              /* u32 [8][16]: (nibble << 4j) * x^(8*(BR_FLUSH-BR_PIECE)): a lane's CRC state carried over the other lanes' pieces */
-__device__ uint32_t g_crcc[96 + 1024 + 128];
+#define CRCC_EP (CRCC_MK + 128)           /* u32 [6][128]: nibble tables of x^(8*BR_PIECE*2^k): a lane's state carried over 2^k pieces */
+#define CRCC_XW (CRCC_EP + 6 * 128)       /* u32 [BR_PIECE][128]: nibble tables of x^(8*w): a state carried over the w bytes of a last, short piece */
+__device__ uint32_t g_crcc[CRCC_XW + 32 * 128];
+static_assert(BR_PIECE == 32u, "the CRCC_XW tables cover a piece of 32 bytes");
 extern "C" __global__ void __launch_bounds__(64) crc_const_init() {
     const uint32_t lane = threadIdx.x;
-    g_crcc[CRCC_K + lane] = crc_xpow8(BR_PIECE * (63u - lane));
-    if (lane == 0) g_crcc[CRCC_XF] = crc_xpow8(BR_FLUSH);
     if (lane < 17) g_crcc[CRCC_XP2 + lane] = crc_xpow8(1u << lane);
     {
         const uint32_t kadv = crc_xpow8(BR_FLUSH - BR_PIECE);
         for (uint32_t e = lane; e < 128u; e += 64u) g_crcc[CRCC_MK + e] = crc_mulmod((e & 15u) << (4u * (e >> 4)), kadv);
+    }
+    for (uint32_t t = 0; t < 6u + BR_PIECE; t++) {
+        const uint32_t kt = t < 6u ? crc_xpow8(BR_PIECE << t) : crc_xpow8(t - 6u);
+        for (uint32_t e = lane; e < 128u; e += 64u) g_crcc[CRCC_EP + 128u * t + e] = crc_mulmod((e & 15u) << (4u * (e >> 4)), kt);
     }
     for (uint32_t k = lane; k < 256; k += 64) {
         uint32_t t[4], c = k;
@@ -734,13 +744,16 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
     // (a multiplication by the constant x^(8*(BR_FLUSH-BR_PIECE)): linear, so eight nibble look-ups in the 128-entry table that the
     // wave holds in two registers, fetched with ds_bpermute).  The 64 states are combined once, behind the block's last full chunk.
     // BR_R is a multiple of BR_PIECE, so neither a lane's CRC piece nor a 16-byte store unit wraps in the ring.
-#define CRC_ADVANCE(r_) ({                                                                                                  \
+    // CRC_MULTAB: a state times the wave-uniform constant whose nibble table the wave holds in lo_ (entries [0,64)) and hi_ ([64,128)).
+    // Every lane of the wave must be active: ds_bpermute reads the table from the other lanes' registers.
+#define CRC_MULTAB(r_, lo_, hi_) ({                                                                                         \
         const uint32_t a_ = (r_); uint32_t m_ = 0;                                                                          \
         _Pragma("unroll") for (uint32_t j_ = 0; j_ < 4; j_++) {                                                            \
-            m_ ^= (uint32_t)__builtin_amdgcn_ds_bpermute((int)((((a_ >> (4u * j_)) & 15u) + 16u * j_) << 2), (int)mk_lo);      \
-            m_ ^= (uint32_t)__builtin_amdgcn_ds_bpermute((int)((((a_ >> (16u + 4u * j_)) & 15u) + 16u * j_) << 2), (int)mk_hi); \
+            m_ ^= (uint32_t)__builtin_amdgcn_ds_bpermute((int)((((a_ >> (4u * j_)) & 15u) + 16u * j_) << 2), (int)(lo_));      \
+            m_ ^= (uint32_t)__builtin_amdgcn_ds_bpermute((int)((((a_ >> (16u + 4u * j_)) & 15u) + 16u * j_) << 2), (int)(hi_)); \
         }                                                                                                                   \
         m_; })
+#define CRC_ADVANCE(r_) CRC_MULTAB(r_, mk_lo, mk_hi)
 #define FLUSH_CHUNK() do {                                                                                              \
         const uint32_t pi_ = ridx(flushed + (uint32_t)lane * BR_PIECE);                                                 \
         uint32_t c_ = CRC_ADVANCE(crc_acc);                                                                             \
@@ -762,7 +775,13 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
     // literal staging ring: literal bytes [.., stage_hi) are in LDS at (abs & 2047); filled 1 KiB at a time, one piece in flight
     uint32_t stage_hi = 0; bool pend = false; uint4 pv = make_uint4(0, 0, 0, 0);
 #define STAGE_ISSUE() do { if (!pend && stage_hi < m.nlit && (int32_t)(stage_hi - litpos) <= 1024) { __builtin_memcpy(&pv, lit + stage_hi + lane * 16, 16); pend = true; } } while (0)
-#define STAGE_COMMIT() do { if (pend) { *(uint4 *)(ring + ((stage_hi + lane * 16) & 2047u)) = pv; stage_hi += 1024u; pend = false; } } while (0)
+    // the ring's first BR_LMIRROR bytes are kept a second time behind its end, so that a literal run of up to BR_LMIRROR bytes that starts
+    // anywhere in the ring is read without a wrap test
+#define STAGE_COMMIT() do { if (pend) {                                                                                 \
+            const uint32_t so_ = (stage_hi + lane * 16) & 2047u;                                                       \
+            *(uint4 *)(ring + so_) = pv;                                                                                \
+            if (so_ < BR_LMIRROR) *(uint4 *)(ring + 2048u + so_) = pv;                                                  \
+            stage_hi += 1024u; pend = false; } } while (0)
     STAGE_ISSUE(); STAGE_COMMIT(); STAGE_ISSUE(); STAGE_COMMIT();
     uint32_t tnext = (lane < (int)m.ntok) ? tok[lane] : B_NULLTOK;
 
@@ -818,30 +837,46 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
             // ---- literals ----
             while (litpos + tot_lit > stage_hi && stage_hi < m.nlit) { STAGE_ISSUE(); STAGE_COMMIT(); }
             LZ_SYNC();
-            // the first 8 bytes of every run lane-parallel: one (usually unaligned) 64-bit ring read, then an exact-length store; the few
-            // runs that are longer (3 % on BAM data) are finished one at a time by the whole wave, a byte per lane -- a second and third
-            // lane-parallel step would cost the whole wave a full iteration each for one or two lanes' bytes
-#ifdef B_EXP_NOLIT
-            if (false) {
-#else
-            if (lrun) {
-#endif
-                const uint32_t ri = lsrc & 2047u;
-                uint64_t v;
-                if (ri <= 2040u) v = lds_ld64(ring + ri);
-                else { v = 0; for (uint32_t k = 0; k < 8; k++) v |= (uint64_t)ring[(ri + k) & 2047u] << (8 * k); }
-                win_st_n(win, dst, v, lrun);
+            // A run of 1..32 bytes whose destination does not wrap in the window ring is copied lane-parallel through the windows of the
+            // match copy below: 8..32 bytes as four 8-byte windows at min(8j, lrun - 8), 4..7 as two 4-byte windows at 0 and lrun - 4,
+            // 2..3 as two 2-byte windows at 0 and lrun - 2, one byte as one.  Every window lies inside the run, so no lane writes a byte
+            // of another token and bytes covered twice get the same value; the staging ring's mirror (STAGE_COMMIT) keeps the source
+            // windows from wrapping.  The few other runs (longer ones; a destination across the ring's end)
+            // take the exact-length store chain for their first 8 bytes and are finished one at a time by the whole wave, a byte per
+            // lane, behind one wave-uniform test.
+#ifndef B_EXP_NOLIT
+            {
+                const uint32_t rl = ridx(dst);
+                const uint8_t *lp = ring + (lsrc & 2047u); uint8_t *wp = win + rl;
+                const bool wlit = lrun - 1u < BR_LMIRROR && rl + lrun <= BR_R;
+                if (wlit) {
+                    if (lrun >= 8u) {
+                        const uint32_t k1 = lrun < 16u ? lrun - 8u : 8u, k2 = lrun < 24u ? lrun - 8u : 16u, k3 = lrun < 32u ? lrun - 8u : 24u;
+                        const uint64_t v0 = lds_ld64(lp), v1 = lds_ld64(lp + k1), v2 = lds_ld64(lp + k2), v3 = lds_ld64(lp + k3);
+                        __builtin_memcpy(wp, &v0, 8); __builtin_memcpy(wp + k1, &v1, 8);
+                        __builtin_memcpy(wp + k2, &v2, 8); __builtin_memcpy(wp + k3, &v3, 8);
+                    } else if (lrun >= 4u) {
+                        const uint32_t k = lrun - 4u;
+                        uint32_t a, b; __builtin_memcpy(&a, lp, 4); __builtin_memcpy(&b, lp + k, 4);
+                        __builtin_memcpy(wp, &a, 4); __builtin_memcpy(wp + k, &b, 4);
+                    } else if (lrun >= 2u) {
+                        const uint32_t k = lrun - 2u;
+                        uint16_t a, b; __builtin_memcpy(&a, lp, 2); __builtin_memcpy(&b, lp + k, 2);
+                        __builtin_memcpy(wp, &a, 2); __builtin_memcpy(wp + k, &b, 2);
+                    } else *wp = *lp;
+                }
+                uint64_t LL = __ballot(lrun != 0u && !wlit);
+                if (LL != 0ull) {
+                    if (lrun != 0u && !wlit) win_st_n(win, dst, lds_ld64(lp), lrun);      // (the 8 bytes read may end in the mirror)
+                    LL = __ballot(lrun > 8u && !wlit);
+                    while (LL) {
+                        const int i = __ffsll((unsigned long long)LL) - 1; LL &= LL - 1;
+                        const uint32_t d0 = RDLANE(dst, i) + 8u, s0 = RDLANE(lsrc, i) + 8u, n0 = RDLANE(lrun, i) - 8u;
+                        for (uint32_t k = lane; k < n0; k += 64) win[ridx(d0 + k)] = ring[(s0 + k) & 2047u];
+                    }
+                }
             }
-#ifdef B_EXP_NOLIT
-            uint64_t LL = 0;
-#else
-            uint64_t LL = __ballot(lrun > 8u);
 #endif
-            while (LL) {
-                const int i = __ffsll((unsigned long long)LL) - 1; LL &= LL - 1;
-                const uint32_t d0 = RDLANE(dst, i) + 8u, s0 = RDLANE(lsrc, i) + 8u, n0 = RDLANE(lrun, i) - 8u;
-                for (uint32_t k = lane; k < n0; k += 64) win[ridx(d0 + k)] = ring[(s0 + k) & 2047u];
-            }
             LZ_SYNC();
             DIAG_T(t_b);
             DIAG_TADD(1, t_a, t_b);
@@ -989,29 +1024,41 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
     if (outpos != m.outlen) { if (lane == 0) blk_status[bi] = DHTS_BLK_ERR_INFLATE; return; }
 
     DIAG_T(t_crc0);
-    // ---- tail [flushed, outlen): CRC per lane + combine, then fold into crc_run ----
+    // ---- tail [flushed, outlen): one more, short chunk of the same BR_PIECE-byte pieces, then ONE combine of the 64 carried states ----
+    // Lanes 0..np continue their state into the tail like FLUSH_CHUNK does (lanes below np over a whole piece, lane np over the last w
+    // bytes); the lanes behind keep the state they left behind their piece of the last full chunk.  In stream order the states then end
+    // BR_PIECE bytes apart: lane l's is followed by BR_PIECE * g + w bytes with g = (np - l - 1) mod 64, and lane np's by none.  So every
+    // lane but np multiplies its state by x^(8*BR_PIECE*2^k) for the set bits k of g (wave-uniform constants: CRC_MULTAB, a select per
+    // bit), the wave XORs the products, carries the sum over the w bytes with one more table and adds lane np's state.  No bit-serial
+    // polynomial product is left on the per-block path.
     const uint32_t n = m.outlen - flushed;                     // < BR_FLUSH
-    const uint32_t chunk = ((n + 63) / 64 + 3) & ~3u;          // multiple of 4; flushed is a multiple of 4, so dwords never wrap
-    uint32_t beg = lane * chunk; if (beg > n) beg = n;
-    uint32_t end = beg + chunk; if (end > n) end = n;
-    // the flushed chunks: a lane's state is followed by the BR_PIECE*(63-lane) bytes of the lanes behind it in the last chunk
-    uint32_t crc_run = 0;
-    if (flushed != 0) {
-        crc_run = crc_mulmod(crc_acc, g_crcc[CRCC_K + lane]);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) crc_run ^= __shfl_xor(crc_run, d, 64);
-    }
-    uint32_t c = lane == 0 ? (flushed == 0 ? 0xffffffffu : crc_run) : 0u;      // lane 0 continues the running CRC
-    uint32_t q = beg;
+#ifdef B_EXP_NOEPI
+    uint32_t c = crc_acc;                                      // (keeps the flushes' CRC alive)
+#else
+    const uint32_t np = (uint32_t)__builtin_amdgcn_readfirstlane((int)(n / BR_PIECE)), w = n % BR_PIECE;
+    const uint32_t beg = (uint32_t)lane * BR_PIECE, end = beg + BR_PIECE < n ? beg + BR_PIECE : n;
+    uint32_t c = CRC_ADVANCE(crc_acc);
+    if ((uint32_t)lane > np) c = crc_acc;
+    if (flushed == 0 && lane == 0) c = 0xffffffffu;            // the stream's first byte
+    uint32_t q = beg;                                          // (flushed and beg are multiples of BR_PIECE: a piece never wraps in the ring)
     for (; q + 4 <= end; q += 4) {
         uint32_t v = *(const uint32_t *)(win + ridx(flushed + q)) ^ c;
         c = crct[768 + (v & 0xff)] ^ crct[512 + ((v >> 8) & 0xff)] ^ crct[256 + ((v >> 16) & 0xff)] ^ crct[v >> 24];
     }
     for (; q < end; q++) c = crct[(c ^ win[ridx(flushed + q)]) & 0xff] ^ (c >> 8);
-    c = crc_mulmod(c, crc_xpow8_tab(n - end));
+    const uint32_t c_last = RDLANE(c, np);
+    if ((uint32_t)lane == np) c = 0;
+    const uint32_t g = (np - (uint32_t)lane - 1u) & 63u;
+#pragma unroll
+    for (uint32_t k = 0; k < 6; k++) {
+        const uint32_t p = CRC_MULTAB(c, g_crcc[CRCC_EP + 128u * k + lane], g_crcc[CRCC_EP + 128u * k + 64u + lane]);
+        c = ((g >> k) & 1u) ? p : c;
+    }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) c ^= __shfl_xor(c, d, 64);
+    c = CRC_MULTAB(c, g_crcc[CRCC_XW + 128u * w + lane], g_crcc[CRCC_XW + 128u * w + 64u + lane]) ^ c_last;
     c ^= 0xffffffffu;
+#endif
     uint32_t want; __builtin_memcpy(&want, comp + tab.coff[bi] + clen - 8, 4);
     if (c != want) st = DHTS_BLK_ERR_CRC;
     if (lane == 0) blk_status[bi] = st;
@@ -1030,13 +1077,13 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
 }
 
 // B_NW waves per workgroup, one BGZF block each: the waves share the 4 KiB of CRC tables, so a wave costs 6 KiB of LDS instead of 10
-// (4 KiB ring window + 2 KiB literal staging) and a CU holds 20 waves instead of 16.  Measured per 92 M-record step: one wave per workgroup
+// (4 KiB ring window + 2 KiB literal staging and its 32-byte mirror: 28,800 B per workgroup) and a CU holds 20 waves instead of 16.  Measured per 92 M-record step: one wave per workgroup
 // 175.4 ms, four 174.2 ms, eight (24 waves per CU) 182.3 ms -- the kernel is bound by the SIMDs' instruction issue (VALU and SALU together,
 // about 3 cycles per wave-instruction), not by latency, so more resident waves only take issue slots from the record stage beside it.
 #ifndef B_NW
 #define B_NW 4
 #endif
-#define B_WAVE_LDS (BR_R + 2048u)
+#define B_WAVE_LDS (BR_R + 2048u + BR_LMIRROR)
 #define B_LDS_BYTES_NW (4096u + B_NW * B_WAVE_LDS)
 extern "C" __global__ void __launch_bounds__(64 * B_NW)
 bgzf_lz_resolve(const uint8_t *__restrict__ comp, BgzfTable tab, int64_t blk0, int32_t nblk,

@@ -1,5 +1,6 @@
 """time_lz.py lib.so [lib.so ...] -- ms per bgzf_lz_resolve launch (24,576 blocks of the bench data) for library variants, e.g. the knock-out
-builds -DB_EXP_NOCRC / NOLIT / NOFAR / NOROUNDS / NOREPLAY / NOSTORE of bgzf_inflate.hip: what a part of the kernel costs is the time it saves."""
+builds -DB_EXP_NOCRC / NOEPI / NOLIT / NOFAR / NOROUNDS / NOREPLAY / NOSTORE of bgzf_inflate.hip (tools/dbg/build_variant.sh NAME -DB_EXP_...):
+what a part of the kernel costs is the time it saves."""
 import ctypes as C
 import os
 import subprocess

@@ -315,46 +315,21 @@ def lib():
         L.dhts_nuc_batch_host_bytes.restype = C.c_uint64
         L.dhts_nuc_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_nuc_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
-        L.dhts_bam_bins_open.argtypes = [C.c_void_p, C.POINTER(BinsParams)]
-        L.dhts_bam_bins_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
-        L.dhts_bam_bins_scan.argtypes = [C.c_void_p, C.c_int64]
-        L.dhts_bam_bins_stats.argtypes = [C.c_void_p, C.POINTER(BinsStats)]
-        L.dhts_bam_bins_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
-        L.dhts_bam_bins_batch_host_bytes.restype = C.c_uint64
-        L.dhts_bam_bins_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
-        L.dhts_bam_bins_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
-        L.dhts_bam_bedcov_open.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BedcovParams)]
-        L.dhts_bam_bedcov_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
-        L.dhts_bam_bedcov_scan.argtypes = [C.c_void_p, C.c_int64]
-        L.dhts_bam_bedcov_stats.argtypes = [C.c_void_p, C.POINTER(BedcovStats)]
-        L.dhts_bam_bedcov_next.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
-        L.dhts_bam_bedcov_batch_host_bytes.restype = C.c_uint64
-        L.dhts_bam_bedcov_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
-        L.dhts_bam_bedcov_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
-        L.dhts_bam_coverage_open.argtypes = [C.c_void_p, C.POINTER(CoverageParams)]
-        L.dhts_bam_coverage_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
-        L.dhts_bam_coverage_scan.argtypes = [C.c_void_p, C.c_int64]
-        L.dhts_bam_coverage_stats.argtypes = [C.c_void_p, C.POINTER(CoverageStats)]
-        L.dhts_bam_coverage_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(BedBatch)]
-        L.dhts_bam_coverage_batch_host_bytes.restype = C.c_uint64
-        L.dhts_bam_coverage_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
-        L.dhts_bam_coverage_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
-        L.dhts_bam_depth_open.argtypes = [C.c_void_p, C.POINTER(DepthParams), C.c_void_p]
-        L.dhts_bam_depth_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
-        L.dhts_bam_depth_scan.argtypes = [C.c_void_p, C.c_int64]
-        L.dhts_bam_depth_stats.argtypes = [C.c_void_p, C.POINTER(DepthStats)]
-        L.dhts_bam_depth_next.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(BedBatch)]
-        L.dhts_bam_depth_batch_host_bytes.restype = C.c_uint64
-        L.dhts_bam_depth_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
-        L.dhts_bam_depth_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
-        L.dhts_bam_pileup_open.argtypes = [C.c_void_p, C.POINTER(PileupParams)]
-        L.dhts_bam_pileup_accumulate.argtypes = [C.c_void_p, C.POINTER(BamBatch)]
-        L.dhts_bam_pileup_scan.argtypes = [C.c_void_p, C.c_int64]
-        L.dhts_bam_pileup_stats.argtypes = [C.c_void_p, C.POINTER(PileupStats)]
-        L.dhts_bam_pileup_next.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(BedBatch)]
-        L.dhts_bam_pileup_batch_host_bytes.restype = C.c_uint64
-        L.dhts_bam_pileup_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
-        L.dhts_bam_pileup_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        # the five bam_* count functions: the stats structure and the arguments of open and next around the common ones
+        for name, stats, open_args, next_args in (("bins", BinsStats, [C.POINTER(BinsParams)], [C.c_int64]),
+                                                  ("bedcov", BedcovStats, [C.c_void_p, C.POINTER(BedcovParams)], [C.c_void_p, C.c_int64]),
+                                                  ("coverage", CoverageStats, [C.POINTER(CoverageParams)], [C.c_int64]),
+                                                  ("depth", DepthStats, [C.POINTER(DepthParams), C.c_void_p], [C.c_int64, C.c_uint32]),
+                                                  ("pileup", PileupStats, [C.POINTER(PileupParams)], [C.c_int64, C.c_uint32])):
+            f = {what: getattr(L, "dhts_bam_%s_%s" % (name, what)) for what in ("open", "accumulate", "scan", "stats", "next", "batch_host_bytes", "batch_fetch")}
+            f["open"].argtypes = [C.c_void_p] + open_args
+            f["accumulate"].argtypes = [C.c_void_p, C.POINTER(BamBatch)]
+            f["scan"].argtypes = [C.c_void_p, C.c_int64]
+            f["stats"].argtypes = [C.c_void_p, C.POINTER(stats)]
+            f["next"].argtypes = [C.c_void_p] + next_args + [C.POINTER(BedBatch)]
+            f["batch_host_bytes"].restype = C.c_uint64
+            f["batch_host_bytes"].argtypes = [C.POINTER(BedBatch)]
+            f["batch_fetch"].argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
         L.dhts_debug_pileup_add_form.argtypes = [C.c_void_p, C.c_int]
         L.dhts_debug_coverage_max_table_bytes.restype = None
         L.dhts_debug_coverage_max_table_bytes.argtypes = [C.c_uint64]
@@ -390,6 +365,11 @@ def lib():
 
 class DhtsError(RuntimeError):
     pass
+
+
+def _clip(v, bits):
+    """what a signed C field of bits + 1 bits holds of v; the C side checks the ranges"""
+    return max(-1, min(int(v), 2 ** bits - 1))
 
 
 class Context:
@@ -824,13 +804,50 @@ class Context:
         self._chk(self.L.dhts_nuc_intervals(self.h, t.ctypes.data, s.ctypes.data, e.ctypes.data, len(t), C.byref(b)))
         return self.nuc_batch_columns(b)
 
-    # ---- bam_bin_counts (the batch has dhts_bed_batch's layout) ----
+    # ---- what the five bam_* count functions share (the batches have dhts_bed_batch's layout) ----
+    def _accum_scan(self, name, max_blocks):
+        rc = getattr(self.L, "dhts_bam_%s_scan" % name)(self.h, max_blocks)
+        if rc < 0:
+            msg = self.L.dhts_error(self.h).decode()
+            if getattr(self, "bam_%s_stats" % name)()["status"] == 0:        # a call failed (a stream that ended on an error has set its status)
+                raise DhtsError(msg)
+        return rc
+
+    def _accum_stats(self, name, cls):
+        st = cls()
+        self._chk(getattr(self.L, "dhts_bam_%s_stats" % name)(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in cls._fields_ if k != "reserved"}
+
+    def _fetch_cols(self, name, b):
+        """the columns of the result batch b on the host: (arena, host columns with pointers into it, rows)"""
+        need = int(getattr(self.L, "dhts_bam_%s_batch_host_bytes" % name)(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        self._chk(getattr(self.L, "dhts_bam_%s_batch_fetch" % name)(self.h, C.byref(b), arena.ctypes.data, need, host))
+        return arena, host, int(b.n_rows)
+
+    def _fixed_cols(self, name, b, mask, names, dtypes):
+        """a page of bare fixed columns (bam_depth, bam_pileup): None for a column the mask leaves out"""
+        arena, host, n = self._fetch_cols(name, b)
+        out = {"n_rows": n}
+        for i in range(b.n_cols):
+            col, dt = names[host[i].col], dtypes[host[i].col]
+            if not (mask >> host[i].col) & 1:
+                assert not b.cols[i].fixed and not host[i].fixed
+                out[col] = None
+            elif n == 0:
+                out[col] = np.zeros(0, dt)
+            else:
+                off = host[i].fixed - arena.ctypes.data
+                out[col] = arena[off:off + n * np.dtype(dt).itemsize].view(dt).copy()
+        return out, int(b.status)
+
+    # ---- bam_bin_counts ----
     def bam_bins_open(self, bin_width=5000, min_mapq=0, include_flags=0, require_flags=0, exclude_flags=0, dedup="none", emit_zero_bins=False):
         """after bam_open and the optional set_regions / load_index: the table of counters, zeroed"""
         if dedup not in BINS_DEDUP:
             raise DhtsError("bam_bin_counts: dedup must be one of: none, adjacent")
-        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
-        p = BinsParams(clip(bin_width, 63), clip(min_mapq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31), BINS_DEDUP[dedup], int(bool(emit_zero_bins)))
+        p = BinsParams(_clip(bin_width, 63), _clip(min_mapq, 31), _clip(require_flags, 31), _clip(exclude_flags, 31), _clip(include_flags, 31), BINS_DEDUP[dedup], int(bool(emit_zero_bins)))
         self._chk(self.L.dhts_bam_bins_open(self.h, C.byref(p)))
 
     def bam_bins_accumulate(self, b):
@@ -838,38 +855,26 @@ class Context:
 
     def bam_bins_scan(self, max_blocks=0):
         """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
-        rc = self.L.dhts_bam_bins_scan(self.h, max_blocks)
-        if rc < 0:
-            msg = self.L.dhts_error(self.h).decode()
-            if self.bam_bins_stats()["status"] == 0:                      # a call failed (a stream that ended on an error has set its status)
-                raise DhtsError(msg)
-        return rc
+        return self._accum_scan("bins", max_blocks)
 
     def bam_bins_stats(self):
-        st = BinsStats()
-        self._chk(self.L.dhts_bam_bins_stats(self.h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in BinsStats._fields_ if k != "reserved"}
+        return self._accum_stats("bins", BinsStats)
 
     def bam_bins_next(self, max_rows=0):
         """the next rows of the result: ({"n_rows", column: int64 array; chrom = the contig's id}, status)"""
         b = BedBatch()
         self._chk(self.L.dhts_bam_bins_next(self.h, max_rows, C.byref(b)))
-        need = int(self.L.dhts_bam_bins_batch_host_bytes(C.byref(b)))
-        arena = np.zeros(max(need, 8), np.uint8)
-        host = (BcfCol * max(b.n_cols, 1))()
-        self._chk(self.L.dhts_bam_bins_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
-        n = int(b.n_rows)
+        arena, host, n = self._fetch_cols("bins", b)
         out = {"n_rows": n}
         for i in range(b.n_cols):
             out[BINS_COLUMNS[host[i].col]] = np.ctypeslib.as_array(C.cast(host[i].fixed, C.POINTER(C.c_int64)), (n,)).copy() if n else np.zeros(0, np.int64)
         return out, int(b.status)
 
-    # ---- bam_coverage (the batch has dhts_bed_batch's layout) ----
+    # ---- bam_coverage ----
     def bam_coverage_open(self, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0, min_depth=1):
         """after bam_open and the optional set_regions / load_index: the target rows, the depth table and the counters, zeroed.  The
         parameters are taken as given (the C ABI's rule)."""
-        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
-        p = CoverageParams(clip(min_read_len, 63), clip(min_depth, 63), clip(min_mapq, 31), clip(min_baseq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31), 0)
+        p = CoverageParams(_clip(min_read_len, 63), _clip(min_depth, 63), _clip(min_mapq, 31), _clip(min_baseq, 31), _clip(require_flags, 31), _clip(exclude_flags, 31), _clip(include_flags, 31), 0)
         self._chk(self.L.dhts_bam_coverage_open(self.h, C.byref(p)))
 
     def bam_coverage_accumulate(self, b):
@@ -878,27 +883,16 @@ class Context:
 
     def bam_coverage_scan(self, max_blocks=0):
         """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
-        rc = self.L.dhts_bam_coverage_scan(self.h, max_blocks)
-        if rc < 0:
-            msg = self.L.dhts_error(self.h).decode()
-            if self.bam_coverage_stats()["status"] == 0:                  # a call failed (a stream that ended on an error has set its status)
-                raise DhtsError(msg)
-        return rc
+        return self._accum_scan("coverage", max_blocks)
 
     def bam_coverage_stats(self):
-        st = CoverageStats()
-        self._chk(self.L.dhts_bam_coverage_stats(self.h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in CoverageStats._fields_ if k != "reserved"}
+        return self._accum_stats("coverage", CoverageStats)
 
     def bam_coverage_next(self, max_rows=0):
         """the next rows of the result: ({"n_rows", column: int64 array (chrom = the contig's id), float64 for the four means}, status)"""
         b = BedBatch()
         self._chk(self.L.dhts_bam_coverage_next(self.h, max_rows, C.byref(b)))
-        need = int(self.L.dhts_bam_coverage_batch_host_bytes(C.byref(b)))
-        arena = np.zeros(max(need, 8), np.uint8)
-        host = (BcfCol * max(b.n_cols, 1))()
-        self._chk(self.L.dhts_bam_coverage_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
-        n = int(b.n_rows)
+        arena, host, n = self._fetch_cols("coverage", b)
         out = {"n_rows": n}
         for i in range(b.n_cols):
             dt = np.float64 if host[i].col in COVERAGE_DOUBLE_COLUMNS else np.int64
@@ -906,13 +900,12 @@ class Context:
             out[COVERAGE_COLUMNS[host[i].col]] = vals.view(dt)
         return out, int(b.status)
 
-    # ---- bam_depth (the batch has dhts_bed_batch's layout) ----
+    # ---- bam_depth ----
     def bam_depth_open(self, bed_ctx=None, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0, include_deletions=0, all_positions=0):
         """after bam_open and the optional set_regions / load_index; bed_ctx: None, or a second Context on this device after bed_open.  The
         target rows, the depth table and the counters, zeroed.  The parameters are taken as given (the C ABI's rule)."""
-        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
-        p = DepthParams(clip(min_read_len, 63), clip(min_mapq, 31), clip(min_baseq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31),
-                        clip(include_deletions, 31), clip(all_positions, 31), 0)
+        p = DepthParams(_clip(min_read_len, 63), _clip(min_mapq, 31), _clip(min_baseq, 31), _clip(require_flags, 31), _clip(exclude_flags, 31), _clip(include_flags, 31),
+                        _clip(include_deletions, 31), _clip(all_positions, 31), 0)
         self._chk(self.L.dhts_bam_depth_open(self.h, C.byref(p), bed_ctx.h if bed_ctx is not None else None))
 
     def bam_depth_accumulate(self, b):
@@ -921,17 +914,10 @@ class Context:
 
     def bam_depth_scan(self, max_blocks=0):
         """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
-        rc = self.L.dhts_bam_depth_scan(self.h, max_blocks)
-        if rc < 0:
-            msg = self.L.dhts_error(self.h).decode()
-            if self.bam_depth_stats()["status"] == 0:                     # a call failed (a stream that ended on an error has set its status)
-                raise DhtsError(msg)
-        return rc
+        return self._accum_scan("depth", max_blocks)
 
     def bam_depth_stats(self):
-        st = DepthStats()
-        self._chk(self.L.dhts_bam_depth_stats(self.h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in DepthStats._fields_ if k != "reserved"}
+        return self._accum_stats("depth", DepthStats)
 
     def bam_depth_next(self, max_rows=0, columns=None):
         """the next page of the result: ({"n_rows", "tid": int32, "pos": int64 (1-based), "depth": int32 arrays; None for a column that
@@ -939,32 +925,15 @@ class Context:
         mask = sum(1 << DEPTH_COLUMNS.index(k) for k in set(columns)) if columns is not None else 7
         b = BedBatch()
         self._chk(self.L.dhts_bam_depth_next(self.h, max_rows, mask, C.byref(b)))
-        need = int(self.L.dhts_bam_depth_batch_host_bytes(C.byref(b)))
-        arena = np.zeros(max(need, 8), np.uint8)
-        host = (BcfCol * max(b.n_cols, 1))()
-        self._chk(self.L.dhts_bam_depth_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
-        n = int(b.n_rows)
-        out = {"n_rows": n}
-        for i in range(b.n_cols):
-            name, dt = DEPTH_COLUMNS[host[i].col], DEPTH_DTYPES[host[i].col]
-            if not (mask >> host[i].col) & 1:
-                assert not b.cols[i].fixed and not host[i].fixed
-                out[name] = None
-            elif n == 0:
-                out[name] = np.zeros(0, dt)
-            else:
-                off = host[i].fixed - arena.ctypes.data
-                out[name] = arena[off:off + n * np.dtype(dt).itemsize].view(dt).copy()
-        return out, int(b.status)
+        return self._fixed_cols("depth", b, mask, DEPTH_COLUMNS, DEPTH_DTYPES)
 
-    # ---- bam_pileup (the batch has dhts_bed_batch's layout) ----
+    # ---- bam_pileup ----
     def bam_pileup_open(self, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0, include_deletions=0, include_insertions=0,
                         distinguish_strands=0, min_nucleotide_depth=1):
         """after bam_open and the optional set_regions / load_index: the target rows, the count table and the counters, zeroed.  The
         parameters are taken as given (the C ABI's rule)."""
-        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
-        p = PileupParams(clip(min_read_len, 63), clip(min_mapq, 31), clip(min_baseq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31),
-                         clip(include_deletions, 31), clip(include_insertions, 31), clip(distinguish_strands, 31), clip(min_nucleotide_depth, 31), 0)
+        p = PileupParams(_clip(min_read_len, 63), _clip(min_mapq, 31), _clip(min_baseq, 31), _clip(require_flags, 31), _clip(exclude_flags, 31), _clip(include_flags, 31),
+                         _clip(include_deletions, 31), _clip(include_insertions, 31), _clip(distinguish_strands, 31), _clip(min_nucleotide_depth, 31), 0)
         self._chk(self.L.dhts_bam_pileup_open(self.h, C.byref(p)))
 
     def bam_pileup_add_form(self, form):
@@ -977,17 +946,10 @@ class Context:
 
     def bam_pileup_scan(self, max_blocks=0):
         """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
-        rc = self.L.dhts_bam_pileup_scan(self.h, max_blocks)
-        if rc < 0:
-            msg = self.L.dhts_error(self.h).decode()
-            if self.bam_pileup_stats()["status"] == 0:                    # a call failed (a stream that ended on an error has set its status)
-                raise DhtsError(msg)
-        return rc
+        return self._accum_scan("pileup", max_blocks)
 
     def bam_pileup_stats(self):
-        st = PileupStats()
-        self._chk(self.L.dhts_bam_pileup_stats(self.h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in PileupStats._fields_ if k != "reserved"}
+        return self._accum_stats("pileup", PileupStats)
 
     def bam_pileup_next(self, max_rows=0, columns=None):
         """the next page of the result: ({"n_rows", "tid": int32, "pos": int64 (1-based), "strand", "nucleotide": uint8 (ASCII), "count": int32
@@ -995,30 +957,13 @@ class Context:
         mask = sum(1 << PILEUP_COLUMNS.index(k) for k in set(columns)) if columns is not None else 31
         b = BedBatch()
         self._chk(self.L.dhts_bam_pileup_next(self.h, max_rows, mask, C.byref(b)))
-        need = int(self.L.dhts_bam_pileup_batch_host_bytes(C.byref(b)))
-        arena = np.zeros(max(need, 8), np.uint8)
-        host = (BcfCol * max(b.n_cols, 1))()
-        self._chk(self.L.dhts_bam_pileup_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
-        n = int(b.n_rows)
-        out = {"n_rows": n}
-        for i in range(b.n_cols):
-            name, dt = PILEUP_COLUMNS[host[i].col], PILEUP_DTYPES[host[i].col]
-            if not (mask >> host[i].col) & 1:
-                assert not b.cols[i].fixed and not host[i].fixed
-                out[name] = None
-            elif n == 0:
-                out[name] = np.zeros(0, dt)
-            else:
-                off = host[i].fixed - arena.ctypes.data
-                out[name] = arena[off:off + n * np.dtype(dt).itemsize].view(dt).copy()
-        return out, int(b.status)
+        return self._fixed_cols("pileup", b, mask, PILEUP_COLUMNS, PILEUP_DTYPES)
 
-    # ---- bam_bedcov (the batch has dhts_bed_batch's layout) ----
+    # ---- bam_bedcov ----
     def bam_bedcov_open(self, bed_ctx, min_mapq=0, require_flags=0, exclude_flags=0, include_flags=0, count_deletions=True, count_ref_skips=True):
         """after bam_open and the optional set_regions / load_index; bed_ctx: a second Context on this device after bed_open.  One pass over
         the BED, the breakpoints to the device, the counters zeroed.  The masks are taken as given (the C ABI's rule)."""
-        clip = lambda v, bits: max(-1, min(int(v), 2 ** bits - 1))          # what the C structure holds; the C side checks the ranges
-        p = BedcovParams(clip(min_mapq, 31), clip(require_flags, 31), clip(exclude_flags, 31), clip(include_flags, 31), int(count_deletions), int(count_ref_skips))
+        p = BedcovParams(_clip(min_mapq, 31), _clip(require_flags, 31), _clip(exclude_flags, 31), _clip(include_flags, 31), int(count_deletions), int(count_ref_skips))
         self._chk(self.L.dhts_bam_bedcov_open(self.h, bed_ctx.h if bed_ctx is not None else None, C.byref(p)))
 
     def bam_bedcov_accumulate(self, b):
@@ -1027,28 +972,17 @@ class Context:
 
     def bam_bedcov_scan(self, max_blocks=0):
         """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
-        rc = self.L.dhts_bam_bedcov_scan(self.h, max_blocks)
-        if rc < 0:
-            msg = self.L.dhts_error(self.h).decode()
-            if self.bam_bedcov_stats()["status"] == 0:                    # a call failed (a stream that ended on an error has set its status)
-                raise DhtsError(msg)
-        return rc
+        return self._accum_scan("bedcov", max_blocks)
 
     def bam_bedcov_stats(self):
-        st = BedcovStats()
-        self._chk(self.L.dhts_bam_bedcov_stats(self.h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in BedcovStats._fields_ if k != "reserved"}
+        return self._accum_stats("bedcov", BedcovStats)
 
     def bam_bedcov_next(self, bed_ctx, max_blocks=0):
         """the result for the next batch of the BED: ({"n_rows", chrom / name / score / strand: lists of bytes or None, start / end: lists of
         int or None, bases_covered / read_count: int64 arrays}, status)"""
         b = BedBatch()
         self._chk(self.L.dhts_bam_bedcov_next(self.h, bed_ctx.h if bed_ctx is not None else None, max_blocks, C.byref(b)))
-        n = int(b.n_rows)
-        need = int(self.L.dhts_bam_bedcov_batch_host_bytes(C.byref(b)))
-        arena = np.zeros(max(need, 8), np.uint8)
-        host = (BcfCol * max(b.n_cols, 1))()
-        self._chk(self.L.dhts_bam_bedcov_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
+        arena, host, n = self._fetch_cols("bedcov", b)
         base = arena.ctypes.data
         out = {"n_rows": n}
         for i in range(b.n_cols):
@@ -2074,12 +2008,8 @@ def read_bam(src, device=0, max_blocks=0, shard=None, region=None, index=None, s
         ctx.close()
 
 
-def bam_bin_counts(src, bin_width=5000, min_mapq=0, include_flags=0, require_flags=0, exclude_flags=0, dedup="none", region=None, index=None, emit_zero_bins=False,
-                   device=0, max_blocks=0, max_rows=0):
-    """bam_bin_counts(path, bin_width :=, min_mapq :=, include_flags :=, require_flags :=, exclude_flags :=, dedup :=, region :=, index_path :=,
-    emit_zero_bins :=): read-start counts in fixed-width bins, accumulated on the device (the contract: include/duckhts_amd.h).
-    {"n_rows", "chrom": list of bytes, "start" .. "count_rev": int64 arrays, "stats": the seven counters, "status": how the stream ended}.
-    index: BAI / CSI bytes narrowing the scan of a region query."""
+def _bam_ctx(src, device, region, index):
+    """a Context on `device` with src open as a BAM, its regions set and the index loaded: (ctx, header).  The caller closes it."""
     ctx = Context(device)
     try:
         ctx.open(src)
@@ -2090,14 +2020,46 @@ def bam_bin_counts(src, bin_width=5000, min_mapq=0, include_flags=0, require_fla
                 raise DhtsError(f"No reads found for region(s): {region}")
             if index is not None:
                 ctx.load_index(index)
+    except BaseException:
+        ctx.close()
+        raise
+    return ctx, hdr
+
+
+def _bed_ctx(device, bed):
+    """a second Context on `device` with bed (a path or the file's bytes) open as read_bed opens it.  The caller closes it."""
+    bctx = Context(device)
+    try:
+        bctx.open(bed)
+        bctx.L.dhts_bgzf_index(bctx.h)
+        bctx._chk(bctx.L.dhts_bed_open(bctx.h))
+    except BaseException:
+        bctx.close()
+        raise
+    return bctx
+
+
+def _drain(next_fn):
+    """every batch of a result: next_fn() -> (columns, status) until the status is not 0"""
+    parts = []
+    while True:
+        cols, st = next_fn()
+        parts.append(cols)
+        if st != 0:
+            return parts
+
+
+def bam_bin_counts(src, bin_width=5000, min_mapq=0, include_flags=0, require_flags=0, exclude_flags=0, dedup="none", region=None, index=None, emit_zero_bins=False,
+                   device=0, max_blocks=0, max_rows=0):
+    """bam_bin_counts(path, bin_width :=, min_mapq :=, include_flags :=, require_flags :=, exclude_flags :=, dedup :=, region :=, index_path :=,
+    emit_zero_bins :=): read-start counts in fixed-width bins, accumulated on the device (the contract: include/duckhts_amd.h).
+    {"n_rows", "chrom": list of bytes, "start" .. "count_rev": int64 arrays, "stats": the seven counters, "status": how the stream ended}.
+    index: BAI / CSI bytes narrowing the scan of a region query."""
+    ctx, hdr = _bam_ctx(src, device, region, index)
+    try:
         ctx.bam_bins_open(bin_width, min_mapq, include_flags, require_flags, exclude_flags, dedup, emit_zero_bins)
         status = ctx.bam_bins_scan(max_blocks)
-        parts = []
-        while True:
-            cols, st = ctx.bam_bins_next(max_rows)
-            parts.append(cols)
-            if st != 0:
-                break
+        parts = _drain(lambda: ctx.bam_bins_next(max_rows))
         out = {k: np.concatenate([p[k] for p in parts]) for k in BINS_COLUMNS}
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in hdr["ref_names"]]
         out["chrom"] = [names[t] for t in out["chrom"]]
@@ -2117,28 +2079,12 @@ def bam_bedcov(src, bed, min_mapq=0, require_flags=0, exclude_flags=0x704, inclu
     None, "start", "end": lists of int or None, "bases_covered", "read_count": int64 arrays, "stats": the step counters, the BED's rows and
     the breakpoints, "status": how the BAM stream ended}.  index: BAI / CSI bytes narrowing the scan of a region query; max_blocks: BAM blocks
     per batch, bed_max_blocks: BED blocks per result batch."""
-    ctx, bctx = Context(device), None
+    (ctx, hdr), bctx = _bam_ctx(src, device, region, index), None
     try:
-        ctx.open(src)
-        ctx.bgzf_index()
-        ctx.bam_open()
-        if region is not None:
-            if not ctx.set_regions(region):
-                raise DhtsError(f"No reads found for region(s): {region}")
-            if index is not None:
-                ctx.load_index(index)
-        bctx = Context(device)
-        bctx.open(bed)
-        bctx.L.dhts_bgzf_index(bctx.h)
-        bctx._chk(bctx.L.dhts_bed_open(bctx.h))
+        bctx = _bed_ctx(device, bed)
         ctx.bam_bedcov_open(bctx, min_mapq, require_flags, exclude_flags, include_flags, count_deletions, count_ref_skips)
         status = ctx.bam_bedcov_scan(max_blocks)
-        parts = []
-        while True:
-            cols, st = ctx.bam_bedcov_next(bctx, bed_max_blocks)
-            parts.append(cols)
-            if st != 0:
-                break
+        parts = _drain(lambda: ctx.bam_bedcov_next(bctx, bed_max_blocks))
         out = {}
         for k in BEDCOV_COLUMNS:
             vals = [p[k] for p in parts if k in p]
@@ -2160,24 +2106,11 @@ def bam_coverage(src, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, 
     include/duckhts_amd.h).  {"n_rows", "chrom": list of bytes, "start", "end", "numreads", "covbases": int64 arrays, "coverage", "meandepth",
     "meanbaseq", "meanmapq": float64 arrays, "sum_depth", "sum_baseq", "sum_mapq": int64 arrays, "stats": the step counters, "status": how the
     stream ended}.  index: BAI / CSI bytes narrowing the scan of a region query."""
-    ctx = Context(device)
+    ctx, hdr = _bam_ctx(src, device, region, index)
     try:
-        ctx.open(src)
-        ctx.bgzf_index()
-        hdr = ctx.bam_open()
-        if region is not None:
-            if not ctx.set_regions(region):
-                raise DhtsError(f"No reads found for region(s): {region}")
-            if index is not None:
-                ctx.load_index(index)
         ctx.bam_coverage_open(min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, min_depth)
         status = ctx.bam_coverage_scan(max_blocks)
-        parts = []
-        while True:
-            cols, st = ctx.bam_coverage_next(max_rows)
-            parts.append(cols)
-            if st != 0:
-                break
+        parts = _drain(lambda: ctx.bam_coverage_next(max_rows))
         out = {k: np.concatenate([p[k] for p in parts]) for k in COVERAGE_COLUMNS}
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in hdr["ref_names"]]
         out["chrom"] = [names[t] for t in out["chrom"]]
@@ -2197,29 +2130,13 @@ def bam_depth(src, region=None, index=None, bed=None, max_blocks=0, max_rows=0, 
     contig's id), "pos": int64 (1-based), "depth": int32 arrays -- None for a column that `columns` leaves out --, "contigs": the names by
     id, "stats": the step counters, the target rows, the skipped BED rows, the table's bytes and the result's rows, "status": how the stream
     ended}.  bed: a path or the file's bytes; index: BAI / CSI bytes narrowing the scan of a region query; max_rows: rows per page."""
-    ctx, bctx = Context(device), None
+    (ctx, hdr), bctx = _bam_ctx(src, device, region, index), None
     try:
-        ctx.open(src)
-        ctx.bgzf_index()
-        hdr = ctx.bam_open()
-        if region is not None:
-            if not ctx.set_regions(region):
-                raise DhtsError(f"No reads found for region(s): {region}")
-            if index is not None:
-                ctx.load_index(index)
         if bed is not None:
-            bctx = Context(device)
-            bctx.open(bed)
-            bctx.L.dhts_bgzf_index(bctx.h)
-            bctx._chk(bctx.L.dhts_bed_open(bctx.h))
+            bctx = _bed_ctx(device, bed)
         ctx.bam_depth_open(bctx, min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, include_deletions, all_positions)
         status = ctx.bam_depth_scan(max_blocks)
-        parts = []
-        while True:
-            cols, st = ctx.bam_depth_next(max_rows, columns)
-            parts.append(cols)
-            if st != 0:
-                break
+        parts = _drain(lambda: ctx.bam_depth_next(max_rows, columns))
         out = {k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts]) for k in DEPTH_COLUMNS}
         out["n_rows"] = sum(p["n_rows"] for p in parts)
         out["pages"] = [p["n_rows"] for p in parts]
@@ -2243,27 +2160,14 @@ def bam_pileup(src, region=None, index=None, max_blocks=0, max_rows=0, columns=N
     `columns` leaves out --, "contigs": the names by id, "stats": the step counters, the target rows, the table's bytes and the result's rows,
     "status": how the stream ended}.  index: BAI / CSI bytes narrowing the scan of a region query; max_rows: rows per page; add_form: the
     debug hook's value (tests and benchmarks)."""
-    ctx = Context(device)
+    ctx, hdr = _bam_ctx(src, device, region, index)
     try:
-        ctx.open(src)
-        ctx.bgzf_index()
-        hdr = ctx.bam_open()
-        if region is not None:
-            if not ctx.set_regions(region):
-                raise DhtsError(f"No reads found for region(s): {region}")
-            if index is not None:
-                ctx.load_index(index)
         if add_form:
             ctx.bam_pileup_add_form(add_form)
         ctx.bam_pileup_open(min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, include_deletions, include_insertions, distinguish_strands,
                             min_nucleotide_depth)
         status = ctx.bam_pileup_scan(max_blocks)
-        parts = []
-        while True:
-            cols, st = ctx.bam_pileup_next(max_rows, columns)
-            parts.append(cols)
-            if st != 0:
-                break
+        parts = _drain(lambda: ctx.bam_pileup_next(max_rows, columns))
         out = {k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts]) for k in PILEUP_COLUMNS}
         out["n_rows"] = sum(p["n_rows"] for p in parts)
         out["pages"] = [p["n_rows"] for p in parts]

@@ -26,6 +26,7 @@
 #include "bgzf_deflate.hip"
 #include "hts_index.hip"
 #include "bcf_header.h"
+#include "bam_filter_check.h"
 
 #include <errno.h>
 #include <time.h>
@@ -203,53 +204,59 @@ struct NucState {
     DevBuf ents, names, table, cum, in_tid, in_start, in_end, tmp, keep, rank, src, rows, err, npieces, piece_off, counts;
     DevBuf name_len, name_off, name_bytes, name_valid, seq_len, seq_off32, seq_off64, seq_valid, ones, fixed[NUC_N_COLS];
 };
+// What the states of the five bam_* count functions start with (dhts_bam_accum.inc works on it): whether the function is open, the contigs of
+// the header, the status the scan's stream ended on, the step counters on the device and the columns of the last result batch
+struct AccumBase { bool open = false; int32_t n_ref = 0, status = 0; std::vector<dhts_col> out; DevBuf steps; };
 // bam_bin_counts (bam_bins.hip, dhts_bam_bins.inc): the parameters, the table of counters (two 64-bit words per bin) with the bins in front of
 // every contig, the step counters, the duplicate rule's last visible row (two slots used in turn), per-batch scratch, and the window of the
 // table the result is being paged out of
-struct BinsState {
-    bool open = false, table_ready = false; dhts_bins_params P; uint64_t total_bins = 0; int32_t n_ref = 0, status = 0; int carry_cur = 0;
-    uint64_t win_b0 = 0, win_rows = 0, win_done = 0; uint32_t win_n = 0; std::vector<dhts_col> out;
-    DevBuf counts, steps, carry, bin_base, ref_len, zero_ok, step, word, vis, rank, src, keep, krank, ones, cols[DHTS_BINS_COL_COUNT];
+struct BinsState : AccumBase {
+    bool table_ready = false; dhts_bins_params P; uint64_t total_bins = 0; int carry_cur = 0;
+    uint64_t win_b0 = 0, win_rows = 0, win_done = 0; uint32_t win_n = 0;
+    DevBuf counts, carry, bin_base, ref_len, zero_ok, step, word, vis, rank, src, keep, krank, ones, cols[DHTS_BINS_COL_COUNT];
 };
 // bam_bedcov (bam_bedcov.hip, dhts_bam_bedcov.inc): the parameters, the breakpoints (X, with base[t] in front of every contig) and the indices
 // ks / ke of every BED row's start and end among them, the counters (four 64-bit words per breakpoint index) and their prefix sums, the step
 // counters, per-batch scratch, and the position of the second pass over the BED context
-struct BedcovState {
-    bool open = false, sums_ready = false, started = false; dhts_bedcov_params P; int32_t n_ref = 0, status = 0;
-    uint64_t n_points = 0, n_bed = 0, row_next = 0; std::vector<dhts_col> out;
-    DevBuf cnt, sums, partial, steps, base, X, ks, ke, step, rlen, nseg, bases, reads, ones;
+struct BedcovState : AccumBase {
+    bool sums_ready = false, started = false; dhts_bedcov_params P;
+    uint64_t n_points = 0, n_bed = 0, row_next = 0;
+    DevBuf cnt, sums, partial, base, X, ks, ke, step, rlen, nseg, bases, reads, ones;
 };
 // bam_coverage (bam_coverage.hip, dhts_bam_coverage.inc): the parameters, the target rows in the order they are answered in (o_k: a row's
 // index among the sorted non-empty rows, -1 for an empty one), the sorted rows on the device with their spans of the difference table, the
 // per-row words and the step counters, per-batch scratch, the per-tile values of a result, and the result's columns on the host
-// (DepLayout: what bam_coverage and bam_depth share -- the target rows and their spans of the difference table, made by dep_layout)
+// (DepLayout: what bam_coverage, bam_depth and bam_pileup share -- the target rows and their spans of the table, made by dep_layout;
+// DepPager: what bam_depth and bam_pileup page a result out with -- the result index in front of every tile (toff) and of every sorted row
+// (row_off), where the next page starts (the row in answer order and the result rows of it already taken) and the tiles of a page's windows)
 struct DepLayout {
     uint64_t n_sorted = 0, slots = 0;
     std::vector<int32_t> o_tid; std::vector<int64_t> o_beg, o_end, o_k;
     std::vector<int64_t> s_beg, s_end; std::vector<uint64_t> s_base; std::vector<int32_t> s_tid;   // the sorted rows on the host
     DevBuf diff, tid_first, rbeg, rend, rbase, tile_row;
 };
-struct CoverageState : DepLayout {
-    bool open = false, res_ready = false; dhts_coverage_params P; int32_t n_ref = 0, status = 0;
-    uint64_t row_next = 0; std::vector<dhts_col> out;
+struct DepPager { uint64_t o_next = 0, o_within = 0; std::vector<uint64_t> row_off; DevBuf toff, pagetiles; };
+struct CoverageState : AccumBase, DepLayout {
+    bool res_ready = false; dhts_coverage_params P;
+    uint64_t row_next = 0;
     std::vector<int64_t> h_cols[DHTS_COVERAGE_COL_COUNT];
-    DevBuf words, steps, step, rlen, k0, k1, tsum, tcov, tdepth, res, ones, cols[DHTS_COVERAGE_COL_COUNT];
+    DevBuf words, step, rlen, k0, k1, tsum, tcov, tdepth, res, ones, cols[DHTS_COVERAGE_COL_COUNT];
 };
 // bam_depth (bam_depth.hip, dhts_bam_depth.inc): the parameters, the layout, the touched contigs and the step counters, per-batch scratch, and
 // of a result the depth (tsum) and the result index (toff) in front of every tile, the result index in front of every sorted row (row_off),
 // where the next page starts (the row in answer order and the positions of it already taken) and the page's columns
-struct DepthState : DepLayout {
-    bool open = false, res_ready = false; dhts_depth_params P; int32_t n_ref = 0, status = 0;
-    uint64_t n_bed_skipped = 0, n_positions = 0, o_next = 0, o_within = 0; std::vector<uint64_t> row_off; std::vector<dhts_col> out;
-    DevBuf steps, touched, row_tid, step, rlen, k0, k1, tsum, toff, part, rowres, pagetiles, out_tid, out_pos, out_depth;
+struct DepthState : AccumBase, DepLayout, DepPager {
+    bool res_ready = false; dhts_depth_params P;
+    uint64_t n_bed_skipped = 0, n_positions = 0;
+    DevBuf touched, row_tid, step, rlen, k0, k1, tsum, part, rowres, out_tid, out_pos, out_depth;
 };
 // bam_pileup (bam_pileup.hip, dhts_bam_pileup.inc): the parameters, the layout (diff: the count table, S words per slot), the step counters,
 // per-batch scratch, and of a result the result index in front of every tile of words (toff) and of every sorted row (row_off), where the next
 // page starts and the page's columns
-struct PileupState : DepLayout {
-    bool open = false, res_ready = false; dhts_pileup_params P; int32_t n_ref = 0, status = 0, form = 0;
-    uint64_t n_result_rows = 0, o_next = 0, o_within = 0; std::vector<uint64_t> row_off; std::vector<dhts_col> out;
-    DevBuf steps, row_tid, step, rlen, k0, k1, toff, part, rowres, pagetiles, out_tid, out_pos, out_strand, out_nuc, out_count;
+struct PileupState : AccumBase, DepLayout, DepPager {
+    bool res_ready = false; dhts_pileup_params P; int32_t form = 0;
+    uint64_t n_result_rows = 0;
+    DevBuf row_tid, step, rlen, k0, k1, part, rowres, out_tid, out_pos, out_strand, out_nuc, out_count;
 };
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
@@ -420,6 +427,14 @@ static int fail(dhts_ctx *c, const char *fmt, ...) {
 // shards and index building have no meaning on a context that dhts_bed_open prepared
 #define BED_REFUSE(c, what) do { if ((c) && (c)->bed.open) return fail(c, "%s is not supported on a BED context (read_bed scans BED text in file order)", what); \
                                  if ((c) && (c)->tbx.open) return fail(c, "%s is not supported on a tabix text context (read_tabix / read_gtf / read_gff scan text in file order)", what); } while (0)
+
+// the read-back of dhts_col columns every dhts_*_batch_fetch of such a batch goes through (dhts_bam_accum.inc; read_bed and fasta_nuc, which
+// are included in front of it, use it too).  kind(col): COL_INT64 (valid, then 8 n), COL_STRING (valid, off, bytes), or the width in bytes
+// of a bare fixed column without validity (a null `fixed` is a column left out: it is skipped)
+enum { COL_STRING = -1, COL_INT64 = 0 };
+typedef int (*ColKind)(int col);
+static uint64_t cols_host_bytes(int64_t n_rows, int n_cols, const dhts_col *cols, ColKind kind);
+static int cols_fetch(dhts_ctx *c, const char *fn, int64_t n_rows, int n_cols, const dhts_col *cols, ColKind kind, void *dst, uint64_t cap, dhts_col *out_cols);
 
 // ---- kernel timing with HIP events on the context's stream --------------------------------
 static hipEvent_t ev_get(dhts_ctx *c) {
@@ -594,6 +609,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bed_scan.inc"
 #include "dhts_tabix_scan.inc"
 #include "dhts_fasta_nuc.inc"
+#include "dhts_bam_accum.inc"
 #include "dhts_bam_bins.inc"
 #include "dhts_bam_bedcov.inc"
 #include "dhts_bam_coverage.inc"

@@ -1,25 +1,25 @@
 // dhts_bam_bins.inc -- part of dhts_api.hip (included there, inside its extern "C" block; not a translation unit of its own):
 // bam_bin_counts.  The table of 64-bit counters (two per bin) and the step counters live in HBM from dhts_bam_bins_open on; every batch of
 // the context's read_bam scan is classified and added by the kernels of bam_bins.hip without a visit to the host; the result rows are
-// cut out of the table window by window (mark, scan, emit) and paged out.
+// cut out of the table window by window (mark, scan, emit) and paged out.  The checks in front of a batch, the scan loop, the step counters
+// and the read-back are dhts_bam_accum.inc's.
 #define BINS_MAX_TOTAL (1ull << 28)
 #define BINS_WINDOW (1u << 22)                 /* bins marked and scanned at once when the result is paged out */
 static const uint32_t BINS_COLMASK = (1u << DHTS_BAM_FLAG) | (1u << DHTS_BAM_RNAME) | (1u << DHTS_BAM_POS) | (1u << DHTS_BAM_MAPQ) | (1u << DHTS_BAM_PNEXT);   // no string column
 
-// a shard or a block range of the file (the windows of a region query are the whole answer of that query, not a shard)
-static bool bins_sharded(const dhts_ctx *c) { return c->range_cut; }
+// (a shard or a block range of the file is refused; the windows of a region query are the whole answer of that query, not a shard)
+static const AccumWho BINS_WHO = {"bam_bin_counts", "bam_bin_counts: dhts_bam_bins_open not called",
+                                  "bam_bin_counts: a shard or block range of the file is not supported (the duplicate rule and the counts need the whole file on one device)"};
 
 int dhts_bam_bins_open(dhts_ctx *c, const dhts_bins_params *p) {
     if (!c || !p) return c ? fail(c, "bam_bin_counts: no parameters") : -1;
     BinsState &S = c->bins;
     S.open = false;
     if (!c->bam_open) return fail(c, "bam_bin_counts: dhts_bam_open not called");
-    if (bins_sharded(c)) return fail(c, "bam_bin_counts: a shard or block range of the file is not supported (the duplicate rule and the counts need the whole file on one device)");
+    if (c->range_cut) return fail(c, "%s", BINS_WHO.sharded);
     if (p->bin_width <= 0) return fail(c, "bam_bin_counts: bin_width must be > 0");
-    if (p->min_mapq < 0 || p->min_mapq > 255) return fail(c, "bam_bin_counts: min_mapq must be between 0 and 255");
-    if (p->include_flags < 0 || p->include_flags > 65535) return fail(c, "bam_bin_counts: include_flags must be between 0 and 65535");
-    if (p->require_flags < 0 || p->require_flags > 65535) return fail(c, "bam_bin_counts: require_flags must be between 0 and 65535");
-    if (p->exclude_flags < 0 || p->exclude_flags > 65535) return fail(c, "bam_bin_counts: exclude_flags must be between 0 and 65535");
+    BamFilterMsg m;
+    if (const char *bad = bam_filter_check(m, "bam_bin_counts", 0, p->min_mapq, 0, p->include_flags, p->require_flags, p->exclude_flags, false, false)) return fail(c, "%s", bad);
     if (p->dedup != DHTS_BINS_DEDUP_NONE && p->dedup != DHTS_BINS_DEDUP_ADJACENT) return fail(c, "bam_bin_counts: dedup must be one of: none, adjacent");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n_ref = c->ref_len.size();
@@ -55,13 +55,9 @@ static int bins_table(dhts_ctx *c) {
 int dhts_bam_bins_accumulate(dhts_ctx *c, const dhts_bam_batch *b) {
     if (!c || !b) return c ? fail(c, "bam_bin_counts: no batch") : -1;
     BinsState &S = c->bins;
-    if (!S.open) return fail(c, "bam_bin_counts: dhts_bam_bins_open not called");
-    if (bins_sharded(c)) return fail(c, "bam_bin_counts: a shard or block range of the file is not supported (the duplicate rule and the counts need the whole file on one device)");
-    if (b->status != 0) S.status = b->status;
+    const int go = accum_batch_ok(c, BINS_WHO, S, b, true, nullptr);
+    if (go <= 0) return go;
     const int64_t n = b->n_rows;
-    if (n <= 0) return 0;
-    if (n > 0x7fffff00ll || !b->flag || !b->tid || !b->pos || !b->mapq || !b->pnext) return fail(c, "bam_bin_counts: the batch lacks FLAG, tid, POS, MAPQ or PNEXT");
-    HIPCHK(c, hipSetDevice(c->device));
     if (bins_table(c)) return -1;
     const bool dedup = S.P.dedup == DHTS_BINS_DEDUP_ADJACENT;
     ENSURE(c, S.step, (size_t)n + 64); ENSURE(c, S.word, (size_t)n * 4 + 64);
@@ -90,29 +86,16 @@ int dhts_bam_bins_accumulate(dhts_ctx *c, const dhts_bam_batch *b) {
     return 0;
 }
 
-// the context's scan to the end of the stream; returns the status it ended on (1, or the negative status of a stream that ended on an error:
-// its rows are counted), < 0 with dhts_error set when a call failed (dhts_bam_bins_stats.status stays 0 then)
 int dhts_bam_bins_scan(dhts_ctx *c, int64_t max_blocks) {
-    if (!c) return -1;
-    if (!c->bins.open) return fail(c, "bam_bin_counts: dhts_bam_bins_open not called");
-    if (bins_sharded(c)) return fail(c, "bam_bin_counts: a shard or block range of the file is not supported (the duplicate rule and the counts need the whole file on one device)");
-    for (;;) {
-        dhts_bam_batch b;
-        if (dhts_bam_next_batch(c, max_blocks, BINS_COLMASK, &b) != 0) return -1;
-        if (dhts_bam_bins_accumulate(c, &b) != 0) return -1;
-        if (b.status != 0) return b.status;
-    }
+    return c ? accum_scan(c, BINS_WHO, c->bins.open, max_blocks, BINS_COLMASK, dhts_bam_bins_accumulate) : -1;
 }
 
 int dhts_bam_bins_stats(dhts_ctx *c, dhts_bins_stats *out) {
     if (!c || !out) return c ? fail(c, "bam_bin_counts: no stats") : -1;
     memset(out, 0, sizeof(*out));
     BinsState &S = c->bins;
-    if (!S.open) return fail(c, "bam_bin_counts: dhts_bam_bins_open not called");
-    HIPCHK(c, hipSetDevice(c->device));
     uint64_t s[BIN_N_STEPS];
-    HIPCHK(c, hipMemcpyAsync(s, S.steps.p, sizeof(s), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (accum_steps(c, BINS_WHO, S, s, BIN_N_STEPS)) return -1;
     out->n_flag_filtered = s[BIN_STEP_FLAG]; out->n_unplaced = s[BIN_STEP_UNPLACED]; out->n_out_of_range = s[BIN_STEP_RANGE]; out->n_duplicate = s[BIN_STEP_DUP];
     out->n_low_mapq = s[BIN_STEP_MAPQ]; out->n_counted = s[BIN_STEP_COUNTED];
     for (int k = 0; k < BIN_N_STEPS; k++) out->n_rows += s[k];
@@ -125,7 +108,7 @@ int dhts_bam_bins_next(dhts_ctx *c, int64_t max_rows, dhts_bins_batch *out) {
     if (!c || !out) return -1;
     memset(out, 0, sizeof(*out));
     BinsState &S = c->bins;
-    if (!S.open) return fail(c, "bam_bin_counts: dhts_bam_bins_open not called");
+    if (!S.open) return fail(c, "%s", BINS_WHO.not_open);
     HIPCHK(c, hipSetDevice(c->device));
     if (max_rows <= 0) max_rows = 1 << 20;
     if (max_rows > BINS_WINDOW) max_rows = BINS_WINDOW;
@@ -144,8 +127,7 @@ int dhts_bam_bins_next(dhts_ctx *c, int64_t max_rows, dhts_bins_batch *out) {
     }
     const uint64_t avail = S.win_rows - S.win_done;
     const int64_t nrows = avail < (uint64_t)max_rows ? (int64_t)avail : max_rows;
-    S.out.assign(DHTS_BINS_COL_COUNT, dhts_col());
-    for (int i = 0; i < DHTS_BINS_COL_COUNT; i++) { memset(&S.out[(size_t)i], 0, sizeof(dhts_col)); S.out[(size_t)i].col = i; }
+    cols_reset(S.out, DHTS_BINS_COL_COUNT);
     out->n_rows = nrows; out->n_cols = DHTS_BINS_COL_COUNT; out->cols = S.out.data();
     if (nrows > 0) {
         BinCols o; long long **op[DHTS_BINS_COL_COUNT] = {&o.chrom, &o.start, &o.end, &o.bin_id, &o.total, &o.fwd, &o.rev};
@@ -164,23 +146,7 @@ int dhts_bam_bins_next(dhts_ctx *c, int64_t max_rows, dhts_bins_batch *out) {
 }
 
 // ---- read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst (every column eight bytes wide) ----------------------------
-uint64_t dhts_bam_bins_batch_host_bytes(const dhts_bins_batch *b) {
-    if (!b) return 0;
-    const uint64_t n = (uint64_t)b->n_rows;
-    return (uint64_t)b->n_cols * (((n + 7) & ~7ull) + n * 8);
-}
+uint64_t dhts_bam_bins_batch_host_bytes(const dhts_bins_batch *b) { return b ? cols_host_bytes(b->n_rows, b->n_cols, b->cols, col_kind_int64) : 0; }
 int dhts_bam_bins_batch_fetch(dhts_ctx *c, const dhts_bins_batch *b, void *dst, uint64_t cap, dhts_col *out_cols) {
-    if (!c || !b || !out_cols || (!dst && cap)) return -1;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (cap < dhts_bam_bins_batch_host_bytes(b)) return fail(c, "bam_bin_counts: fetch buffer too small");
-    uint8_t *p = (uint8_t *)dst; const uint64_t n = (uint64_t)b->n_rows;
-    for (int i = 0; i < b->n_cols; i++) {
-        const dhts_col &s = b->cols[i]; dhts_col &o = out_cols[i];
-        memset(&o, 0, sizeof(o)); o.col = s.col;
-        if (n == 0) continue;
-        HIPCHK(c, hipMemcpyAsync(p, s.valid, n, hipMemcpyDeviceToHost, c->stream)); o.valid = p; p += (n + 7) & ~7ull;
-        HIPCHK(c, hipMemcpyAsync(p, s.fixed, n * 8, hipMemcpyDeviceToHost, c->stream)); o.fixed = p; p += n * 8;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return b ? cols_fetch(c, "bam_bin_counts", b->n_rows, b->n_cols, b->cols, col_kind_int64, dst, cap, out_cols) : -1;
 }

@@ -3,10 +3,11 @@
 // per position (32, or 64 with strands).  A batch is classified (bam_depth_classify_del) and counted where it lies by bam_pileup_add.  The
 // result is counted once (per tile of words the words that emit, their 64-bit carry, one result index per row to the host) and then emitted
 // page by page as in bam_depth: the host turns the next max_rows result rows into windows of result indices and launches pil_emit on the
-// tiles that hold each window.
+// tiles that hold each window.  dep_target_rows, dep_layout, dep_args, depth_carry, the page's windows and tiles (dep_page_windows,
+// dep_page_tiles_of), the checks in front of a batch, the scan loop, the step counters and the read-back are dhts_bam_accum.inc's.
 static const uint32_t PILEUP_COLMASK = (1u << DHTS_BAM_FLAG) | (1u << DHTS_BAM_RNAME) | (1u << DHTS_BAM_POS) | (1u << DHTS_BAM_MAPQ);   // no string column
-#define PILEUP_SHARDED "bam_pileup: a shard or block range of the file is not supported (the counts need the whole file on one device)"
-#define PILEUP_NOT_OPEN "bam_pileup: dhts_bam_pileup_open not called"
+static const AccumWho PILEUP_WHO = {"bam_pileup", "bam_pileup: dhts_bam_pileup_open not called",
+                                     "bam_pileup: a shard or block range of the file is not supported (the counts need the whole file on one device)"};
 #define PILEUP_DEFAULT_ROWS (1ll << 20)
 
 // the form dhts_debug_pileup_add_form's 0 stands for (DESIGN.md 4m has the rule and the measurements)
@@ -24,30 +25,18 @@ int dhts_bam_pileup_open(dhts_ctx *c, const dhts_pileup_params *p) {
     PileupState &S = c->pil;
     S.open = false;
     if (!c->bam_open) return fail(c, "bam_pileup: dhts_bam_open not called");
-    if (c->range_cut) return fail(c, PILEUP_SHARDED);
-    if (p->min_read_len < 0) return fail(c, "bam_pileup: min_read_len must be >= 0");
-    if (p->min_mapq < 0 || p->min_mapq > 255) return fail(c, "bam_pileup: min_mapq must be between 0 and 255");
-    if (p->min_baseq < 0 || p->min_baseq > 255) return fail(c, "bam_pileup: min_baseq must be between 0 and 255");
-    if (p->include_flags < 0 || p->include_flags > 65535) return fail(c, "bam_pileup: include_flags must be between 0 and 65535");
-    if (p->require_flags < 0 || p->require_flags > 65535) return fail(c, "bam_pileup: require_flags must be between 0 and 65535");
-    if (p->exclude_flags < 0 || p->exclude_flags > 65535) return fail(c, "bam_pileup: exclude_flags must be between 0 and 65535");
+    if (c->range_cut) return fail(c, "%s", PILEUP_WHO.sharded);
+    BamFilterMsg m;
+    if (const char *bad = bam_filter_check(m, "bam_pileup", p->min_read_len, p->min_mapq, p->min_baseq, p->include_flags, p->require_flags, p->exclude_flags, true, true)) return fail(c, "%s", bad);
     if (p->include_deletions < 0 || p->include_deletions > 1) return fail(c, "bam_pileup: include_deletions must be 0 or 1");
     if (p->include_insertions < 0 || p->include_insertions > 1) return fail(c, "bam_pileup: include_insertions must be 0 or 1");
     if (p->distinguish_strands < 0 || p->distinguish_strands > 1) return fail(c, "bam_pileup: distinguish_strands must be 0 or 1");
     if (p->min_nucleotide_depth < 1) return fail(c, "bam_pileup: min_nucleotide_depth must be >= 1");
-    // ---- the target rows, in the order they are answered in: bam_coverage's ----
     const size_t n_ref = c->ref_len.size();
-    S.o_tid.clear(); S.o_beg.clear(); S.o_end.clear(); S.o_k.clear();
     std::vector<size_t> o_given;
-    if (c->rg_active && !c->rg_given.empty()) {
-        for (size_t g = 0; g < c->rg_given.size(); g++) {
-            const auto &r = c->rg_given[g];
-            const int64_t L = (int64_t)c->ref_len[(size_t)r.tid];
-            S.o_tid.push_back(r.tid); S.o_beg.push_back(r.beg < L ? r.beg : L); S.o_end.push_back(r.end < L ? r.end : L); o_given.push_back(g);
-        }
-    } else for (size_t t = 0; t < n_ref; t++) { S.o_tid.push_back((int32_t)t); S.o_beg.push_back(0); S.o_end.push_back((int64_t)c->ref_len[t]); }
+    dep_target_rows(c, S, o_given);                        // (bam_coverage's)
     const uint64_t words = p->distinguish_strands ? 2u * PIL_SYMBOLS : PIL_SYMBOLS;
-    if (dep_layout(c, S, "bam_pileup", [&](size_t i) { return c->rg_given[o_given[i]].tok.c_str(); }, 4 * words, "count table")) return -1;
+    if (dep_layout(c, S, "bam_pileup", o_given, 4 * words, "count table")) return -1;
     const size_t R = (size_t)S.n_sorted;
     ENSURE(c, S.steps, 64); ENSURE(c, S.row_tid, (R + 1) * 4 + 64);
     HIPCHK(c, hipMemsetAsync(S.steps.p, 0, 64, c->stream));
@@ -76,23 +65,11 @@ template <bool BQ> static void pileup_launch_add_bq(dhts_ctx *c, PileupState &S,
 int dhts_bam_pileup_accumulate(dhts_ctx *c, const dhts_bam_batch *b) {
     if (!c || !b) return c ? fail(c, "bam_pileup: no batch") : -1;
     PileupState &S = c->pil;
-    if (!S.open) return fail(c, PILEUP_NOT_OPEN);
-    if (c->range_cut) return fail(c, PILEUP_SHARDED);
-    if (b->status != 0) S.status = b->status;
+    const int go = accum_batch_ok(c, PILEUP_WHO, S, b, false, "CIGAR, SEQ and QUAL are read where the scan left them");
+    if (go <= 0) return go;
     const int64_t n = b->n_rows;
-    if (n <= 0) return 0;
-    if (n > 0x7fffff00ll || !b->flag || !b->tid || !b->pos || !b->mapq) return fail(c, "bam_pileup: the batch lacks FLAG, tid, POS or MAPQ");
-    if (n != c->last_batch_rows || b->first_rec_uoff != c->last_batch_first || !c->last_stream.u || !c->rec_off.p || !c->cig_rel.p || !c->ncig_eff.p)
-        return fail(c, "bam_pileup: the batch is not the one dhts_bam_next_batch returned last on this context (CIGAR, SEQ and QUAL are read where the scan left them)");
-    HIPCHK(c, hipSetDevice(c->device));
-    ENSURE(c, S.step, (size_t)n + 64); ENSURE(c, S.rlen, (size_t)n * 8 + 64); ENSURE(c, S.k0, (size_t)n * 4 + 64); ENSURE(c, S.k1, (size_t)n * 4 + 64);
-    DepArgs a; memset(&a, 0, sizeof(a));
-    a.u = c->last_stream.u; a.rec_off = (const uint32_t *)c->rec_off.p; a.cig_rel = (const uint32_t *)c->cig_rel.p; a.ncig_eff = (const uint32_t *)c->ncig_eff.p;
-    a.flag = b->flag; a.tid = b->tid; a.pos = (const int64_t *)b->pos; a.mapq = b->mapq; a.n = (uint32_t)n; a.n_ref = S.n_ref;
-    a.require = (uint32_t)S.P.require_flags; a.exclude = (uint32_t)S.P.exclude_flags; a.include = (uint32_t)S.P.include_flags; a.min_mapq = (uint32_t)S.P.min_mapq;
-    a.min_baseq = (uint32_t)S.P.min_baseq; a.min_read_len = (long long)S.P.min_read_len;
-    a.tid_first = (const uint32_t *)S.tid_first.p; a.rbeg = (const long long *)S.rbeg.p; a.rend = (const long long *)S.rend.p; a.rbase = (const unsigned long long *)S.rbase.p;
-    a.step = (uint8_t *)S.step.p; a.rlen = (long long *)S.rlen.p; a.k0 = (uint32_t *)S.k0.p; a.k1 = (uint32_t *)S.k1.p;
+    DepArgs a;
+    if (dep_args(c, S, b, a)) return -1;
     const unsigned grid = (unsigned)((n + 255) / 256), agrid0 = (unsigned)((n + 31) / 32), agrid = agrid0 < DEP_ADD_MAX_BLOCKS ? agrid0 : DEP_ADD_MAX_BLOCKS;
     KTimer tm(c, DHTS_K_BCF_CHECK);
     hipLaunchKernelGGL(bam_depth_classify_del, dim3(grid), dim3(256), 0, c->stream, a);            // (a superset of what must be walked: M = X and D)
@@ -103,15 +80,7 @@ int dhts_bam_pileup_accumulate(dhts_ctx *c, const dhts_bam_batch *b) {
 }
 
 int dhts_bam_pileup_scan(dhts_ctx *c, int64_t max_blocks) {
-    if (!c) return -1;
-    if (!c->pil.open) return fail(c, PILEUP_NOT_OPEN);
-    if (c->range_cut) return fail(c, PILEUP_SHARDED);
-    for (;;) {
-        dhts_bam_batch b;
-        if (dhts_bam_next_batch(c, max_blocks, PILEUP_COLMASK, &b) != 0) return -1;
-        if (dhts_bam_pileup_accumulate(c, &b) != 0) return -1;
-        if (b.status != 0) return b.status;
-    }
+    return c ? accum_scan(c, PILEUP_WHO, c->pil.open, max_blocks, PILEUP_COLMASK, dhts_bam_pileup_accumulate) : -1;
 }
 
 static uint32_t pileup_sshift(const PileupState &S) { return S.P.distinguish_strands ? 4u : 3u; }
@@ -120,14 +89,9 @@ int dhts_bam_pileup_stats(dhts_ctx *c, dhts_pileup_stats *out) {
     if (!c || !out) return c ? fail(c, "bam_pileup: no stats") : -1;
     memset(out, 0, sizeof(*out));
     PileupState &S = c->pil;
-    if (!S.open) return fail(c, PILEUP_NOT_OPEN);
-    HIPCHK(c, hipSetDevice(c->device));
     uint64_t s[DEP_N_STEPS];
-    HIPCHK(c, hipMemcpyAsync(s, S.steps.p, sizeof(s), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    out->n_flag_filtered = s[DEP_STEP_FLAG]; out->n_unplaced = s[DEP_STEP_UNPLACED]; out->n_short = s[DEP_STEP_SHORT]; out->n_low_mapq = s[DEP_STEP_MAPQ];
-    out->n_outside = s[DEP_STEP_OUTSIDE]; out->n_counted = s[DEP_STEP_COUNTED];
-    for (int k = 0; k < DEP_N_STEPS; k++) out->n_rows += s[k];
+    if (accum_steps(c, PILEUP_WHO, S, s, DEP_N_STEPS)) return -1;
+    dep_stats_common(out, s);
     out->n_target_rows = S.o_tid.size(); out->table_bytes = (S.slots << pileup_sshift(S)) * 4;
     out->n_result_rows = S.res_ready ? S.n_result_rows : 0; out->status = S.status;
     return 0;
@@ -161,52 +125,30 @@ int dhts_bam_pileup_next(dhts_ctx *c, int64_t max_rows, uint32_t colmask, dhts_p
     if (!c || !out) return -1;
     memset(out, 0, sizeof(*out));
     PileupState &S = c->pil;
-    if (!S.open) return fail(c, PILEUP_NOT_OPEN);
+    if (!S.open) return fail(c, "%s", PILEUP_WHO.not_open);
     HIPCHK(c, hipSetDevice(c->device));
     if (max_rows <= 0) max_rows = PILEUP_DEFAULT_ROWS;
     if (pileup_result(c)) return -1;
-    // ---- the windows of this page: runs of rows that follow each other in the answer and in the table ----
-    struct Win { uint64_t o_a, o_b, dst0; };
-    std::vector<Win> wins;
-    const size_t n_out = S.o_tid.size();
-    uint64_t taken = 0; size_t o = (size_t)S.o_next; uint64_t within = S.o_within;
-    while (o < n_out && taken < (uint64_t)max_rows) {
-        const int64_t k = S.o_k[o];
-        const uint64_t cnt = k < 0 ? 0 : S.row_off[(size_t)k + 1] - S.row_off[(size_t)k];
-        if (within >= cnt) { o++; within = 0; continue; }
-        const uint64_t a = S.row_off[(size_t)k] + within, room = (uint64_t)max_rows - taken, m = cnt - within < room ? cnt - within : room;
-        if (!wins.empty() && wins.back().o_b == a) wins.back().o_b = a + m;            // (the row before it in the answer is the row before it in the table)
-        else wins.push_back({a, a + m, taken});
-        taken += m; within += m;
-    }
-    while (o < n_out && (S.o_k[o] < 0 || within >= S.row_off[(size_t)S.o_k[o] + 1] - S.row_off[(size_t)S.o_k[o]])) { o++; within = 0; }      // (rows that have nothing left)
-    const int64_t nrows = (int64_t)taken;
+    DepPage pg;
+    dep_page_windows(S, S, max_rows, pg);
+    const int64_t nrows = (int64_t)pg.rows;
     DevBuf *bufs[DHTS_PILEUP_COL_COUNT] = {&S.out_tid, &S.out_pos, &S.out_strand, &S.out_nuc, &S.out_count};
     static const size_t width[DHTS_PILEUP_COL_COUNT] = {4, 8, 1, 1, 4};
-    S.out.assign(DHTS_PILEUP_COL_COUNT, dhts_col());
-    for (int i = 0; i < DHTS_PILEUP_COL_COUNT; i++) { memset(&S.out[(size_t)i], 0, sizeof(dhts_col)); S.out[(size_t)i].col = i; }
+    cols_reset(S.out, DHTS_PILEUP_COL_COUNT);
     out->n_rows = nrows; out->n_cols = DHTS_PILEUP_COL_COUNT; out->cols = S.out.data();
     colmask &= (1u << DHTS_PILEUP_COL_COUNT) - 1u;
     if (nrows > 0 && colmask) {
         for (int i = 0; i < DHTS_PILEUP_COL_COUNT; i++) if ((colmask >> i) & 1u) ENSURE(c, *bufs[i], (size_t)nrows * width[i] + 64);
         const uint32_t sh = pileup_sshift(S); const uint64_t ntiles = (S.slots << sh) / PIL_TILE;
-        ENSURE(c, S.pagetiles, wins.size() * 16 + 64);
-        std::vector<uint64_t> tiles(wins.size() * 2, 0);
-        for (size_t w = 0; w < wins.size(); w++)
-            hipLaunchKernelGGL(dep_page_tiles, dim3(1), dim3(64), 0, c->stream, (const unsigned long long *)S.toff.p, ntiles, (unsigned long long)wins[w].o_a, (unsigned long long)wins[w].o_b,
-                               (unsigned long long *)S.pagetiles.p + 2 * w);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(tiles.data(), S.pagetiles.p, wins.size() * 16, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (dep_page_tiles_of(c, "bam_pileup", S, ntiles, pg)) return -1;
         KTimer tm(c, DHTS_K_SCAN);
-        for (size_t w = 0; w < wins.size(); w++) {
-            const uint64_t t0 = tiles[2 * w], t1 = tiles[2 * w + 1];
-            if (t1 < t0 || t1 >= ntiles) return fail(c, "bam_pileup: internal error: the tiles of a page are out of range");
+        for (size_t w = 0; w < pg.wins.size(); w++) {
+            const uint64_t t0 = pg.tiles[2 * w], t1 = pg.tiles[2 * w + 1];
             PilEmitArgs e; memset(&e, 0, sizeof(e));
             e.table = (const uint32_t *)S.diff.p; e.toff = (const unsigned long long *)S.toff.p; e.tile_row = (const uint32_t *)S.tile_row.p;
             e.rbase = (const unsigned long long *)S.rbase.p; e.rbeg = (const long long *)S.rbeg.p; e.rend = (const long long *)S.rend.p;
             e.row_tid = (const int32_t *)S.row_tid.p; e.sshift = sh; e.min_count = (uint32_t)S.P.min_nucleotide_depth;
-            e.t0 = t0; e.o_a = wins[w].o_a; e.o_b = wins[w].o_b; e.dst0 = wins[w].dst0;
+            e.t0 = t0; e.o_a = pg.wins[w].o_a; e.o_b = pg.wins[w].o_b; e.dst0 = pg.wins[w].dst0;
             e.out_tid = (colmask >> DHTS_PILEUP_CHROM) & 1u ? (int32_t *)S.out_tid.p : nullptr; e.out_pos = (colmask >> DHTS_PILEUP_POS) & 1u ? (long long *)S.out_pos.p : nullptr;
             e.out_strand = (colmask >> DHTS_PILEUP_STRAND) & 1u ? (uint8_t *)S.out_strand.p : nullptr; e.out_nuc = (colmask >> DHTS_PILEUP_NUCLEOTIDE) & 1u ? (uint8_t *)S.out_nuc.p : nullptr;
             e.out_count = (colmask >> DHTS_PILEUP_COUNT) & 1u ? (int32_t *)S.out_count.p : nullptr;
@@ -216,31 +158,14 @@ int dhts_bam_pileup_next(dhts_ctx *c, int64_t max_rows, uint32_t colmask, dhts_p
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (int i = 0; i < DHTS_PILEUP_COL_COUNT; i++) if ((colmask >> i) & 1u) S.out[(size_t)i].fixed = bufs[i]->p;
     }
-    S.o_next = o; S.o_within = within;
-    out->status = o >= n_out ? 1 : 0;
+    S.o_next = pg.o; S.o_within = pg.within;
+    out->status = pg.o >= S.o_tid.size() ? 1 : 0;
     return 0;
 }
 
 // ---- read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst --------------------------------------------------------------
-static uint64_t pileup_col_width(int col) { return col == DHTS_PILEUP_POS ? 8 : col == DHTS_PILEUP_STRAND || col == DHTS_PILEUP_NUCLEOTIDE ? 1 : 4; }
-static uint64_t pileup_col_bytes(int col, uint64_t n) { return (n * pileup_col_width(col) + 7) & ~7ull; }
-uint64_t dhts_bam_pileup_batch_host_bytes(const dhts_pileup_batch *b) {
-    if (!b) return 0;
-    uint64_t need = 0;
-    for (int i = 0; i < b->n_cols; i++) if (b->cols[i].fixed) need += pileup_col_bytes(b->cols[i].col, (uint64_t)b->n_rows);
-    return need;
-}
+static int pileup_col_kind(int col) { return col == DHTS_PILEUP_POS ? 8 : col == DHTS_PILEUP_STRAND || col == DHTS_PILEUP_NUCLEOTIDE ? 1 : 4; }
+uint64_t dhts_bam_pileup_batch_host_bytes(const dhts_pileup_batch *b) { return b ? cols_host_bytes(b->n_rows, b->n_cols, b->cols, pileup_col_kind) : 0; }
 int dhts_bam_pileup_batch_fetch(dhts_ctx *c, const dhts_pileup_batch *b, void *dst, uint64_t cap, dhts_col *out_cols) {
-    if (!c || !b || !out_cols || (!dst && cap)) return -1;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (cap < dhts_bam_pileup_batch_host_bytes(b)) return fail(c, "bam_pileup: fetch buffer too small");
-    uint8_t *p = (uint8_t *)dst; const uint64_t n = (uint64_t)b->n_rows;
-    for (int i = 0; i < b->n_cols; i++) {
-        const dhts_col &s = b->cols[i]; dhts_col &o = out_cols[i];
-        memset(&o, 0, sizeof(o)); o.col = s.col;
-        if (n == 0 || !s.fixed) continue;
-        HIPCHK(c, hipMemcpyAsync(p, s.fixed, n * pileup_col_width(s.col), hipMemcpyDeviceToHost, c->stream)); o.fixed = p; p += pileup_col_bytes(s.col, n);
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return b ? cols_fetch(c, "bam_pileup", b->n_rows, b->n_cols, b->cols, pileup_col_kind, dst, cap, out_cols) : -1;
 }

@@ -312,35 +312,12 @@ int dhts_bed_next_batch(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *out) {
     }
 }
 
-// read-back in the style of dhts_bcf_batch_fetch: out_cols[b->n_cols] = b->cols with HOST pointers into dst (every copy queued, one wait)
-uint64_t dhts_bed_batch_host_bytes(const dhts_bed_batch *b) {
-    if (!b) return 0;
-    uint64_t need = 0; const uint64_t n = (uint64_t)b->n_rows;
-    for (int i = 0; i < b->n_cols; i++) {
-        need += (n + 7) & ~7ull;
-        if (bed_col_is_int(b->cols[i].col)) need += n * 8; else need += (((n + 1) * 4 + 7) & ~7ull) + ((b->cols[i].nbytes + 7) & ~7ull);
-    }
-    return need;
-}
+// read-back in the style of dhts_bcf_batch_fetch: out_cols[b->n_cols] = b->cols with HOST pointers into dst (every copy queued, one wait;
+// cols_fetch, dhts_bam_accum.inc)
+static int bed_col_kind(int col) { return bed_col_is_int(col) ? COL_INT64 : COL_STRING; }
+uint64_t dhts_bed_batch_host_bytes(const dhts_bed_batch *b) { return b ? cols_host_bytes(b->n_rows, b->n_cols, b->cols, bed_col_kind) : 0; }
 int dhts_bed_batch_fetch(dhts_ctx *c, const dhts_bed_batch *b, void *dst, uint64_t cap, dhts_col *out_cols) {
-    if (!c || !b || !out_cols || (!dst && cap)) return -1;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (cap < dhts_bed_batch_host_bytes(b)) return fail(c, "read_bed: fetch buffer too small");
-    uint8_t *p = (uint8_t *)dst; const uint64_t n = (uint64_t)b->n_rows;
-    for (int i = 0; i < b->n_cols; i++) {
-        const dhts_col &s = b->cols[i]; dhts_col &o = out_cols[i];
-        memset(&o, 0, sizeof(o)); o.col = s.col;
-        if (n == 0) continue;
-        HIPCHK(c, hipMemcpyAsync(p, s.valid, n, hipMemcpyDeviceToHost, c->stream)); o.valid = p; p += (n + 7) & ~7ull;
-        if (bed_col_is_int(s.col)) { HIPCHK(c, hipMemcpyAsync(p, s.fixed, n * 8, hipMemcpyDeviceToHost, c->stream)); o.fixed = p; p += n * 8; }
-        else {
-            HIPCHK(c, hipMemcpyAsync(p, s.off, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream)); o.off = (const uint32_t *)p; p += ((n + 1) * 4 + 7) & ~7ull;
-            if (s.nbytes) HIPCHK(c, hipMemcpyAsync(p, s.bytes, s.nbytes, hipMemcpyDeviceToHost, c->stream));
-            o.bytes = p; o.nbytes = s.nbytes; p += (s.nbytes + 7) & ~7ull;
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return b ? cols_fetch(c, "read_bed", b->n_rows, b->n_cols, b->cols, bed_col_kind, dst, cap, out_cols) : -1;
 }
 
 // measurement hook (include/duckhts_amd_debug.h, tools/bench_bed.py): the lane-per-line walk the delimiter table is compared with, over the

@@ -327,33 +327,9 @@ int dhts_nuc_next_bed(dhts_ctx *c, dhts_ctx *b, int64_t max_blocks, dhts_nuc_bat
     }
 }
 
-// ---- read-back in the style of dhts_bed_batch_fetch ------------------------------------------------------------------------------
-uint64_t dhts_nuc_batch_host_bytes(const dhts_nuc_batch *b) {
-    if (!b) return 0;
-    uint64_t need = 0; const uint64_t n = (uint64_t)b->n_rows;
-    for (int i = 0; i < b->n_cols; i++) {
-        need += (n + 7) & ~7ull;
-        if (!nuc_col_is_str(b->cols[i].col)) need += n * 8; else need += (((n + 1) * 4 + 7) & ~7ull) + ((b->cols[i].nbytes + 7) & ~7ull);
-    }
-    return need;
-}
+// ---- read-back in the style of dhts_bed_batch_fetch (cols_fetch, dhts_bam_accum.inc) -------------------------------------------------
+static int nuc_col_kind(int col) { return nuc_col_is_str(col) ? COL_STRING : COL_INT64; }
+uint64_t dhts_nuc_batch_host_bytes(const dhts_nuc_batch *b) { return b ? cols_host_bytes(b->n_rows, b->n_cols, b->cols, nuc_col_kind) : 0; }
 int dhts_nuc_batch_fetch(dhts_ctx *c, const dhts_nuc_batch *b, void *dst, uint64_t cap, dhts_col *out_cols) {
-    if (!c || !b || !out_cols || (!dst && cap)) return -1;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (cap < dhts_nuc_batch_host_bytes(b)) return fail(c, "fasta_nuc: fetch buffer too small");
-    uint8_t *p = (uint8_t *)dst; const uint64_t n = (uint64_t)b->n_rows;
-    for (int i = 0; i < b->n_cols; i++) {
-        const dhts_col &s = b->cols[i]; dhts_col &o = out_cols[i];
-        memset(&o, 0, sizeof(o)); o.col = s.col;
-        if (n == 0) continue;
-        HIPCHK(c, hipMemcpyAsync(p, s.valid, n, hipMemcpyDeviceToHost, c->stream)); o.valid = p; p += (n + 7) & ~7ull;
-        if (!nuc_col_is_str(s.col)) { HIPCHK(c, hipMemcpyAsync(p, s.fixed, n * 8, hipMemcpyDeviceToHost, c->stream)); o.fixed = p; p += n * 8; }
-        else {
-            HIPCHK(c, hipMemcpyAsync(p, s.off, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream)); o.off = (const uint32_t *)p; p += ((n + 1) * 4 + 7) & ~7ull;
-            if (s.nbytes) HIPCHK(c, hipMemcpyAsync(p, s.bytes, s.nbytes, hipMemcpyDeviceToHost, c->stream));
-            o.bytes = p; o.nbytes = s.nbytes; p += (s.nbytes + 7) & ~7ull;
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return b ? cols_fetch(c, "fasta_nuc", b->n_rows, b->n_cols, b->cols, nuc_col_kind, dst, cap, out_cols) : -1;
 }

@@ -29,11 +29,8 @@ static void bam_bedcov_bind(duckdb_bind_info info) {
     (void)named_int(info, "include_flags", &include_flags); (void)named_int(info, "require_flags", &require_flags); (void)named_int(info, "exclude_flags", &exclude_flags);
     (void)named_bool(info, "count_deletions", &count_deletions); (void)named_bool(info, "count_ref_skips", &count_ref_skips);
     (void)named_string(info, "region", region); (void)named_string(info, "index_path", idx);
-    const char *bad = nullptr;
-    if (min_mapq < 0 || min_mapq > 255) bad = "bam_bedcov: min_mapq must be between 0 and 255";
-    else if (include_flags < 0 || include_flags > 65535) bad = "bam_bedcov: include_flags must be between 0 and 65535";
-    else if (require_flags < 0 || require_flags > 65535) bad = "bam_bedcov: require_flags must be between 0 and 65535";
-    else if (exclude_flags < 0 || exclude_flags > 65535) bad = "bam_bedcov: exclude_flags must be between 0 and 65535";
+    BamFilterMsg m;
+    const char *bad = bam_filter_check(m, "bam_bedcov", 0, min_mapq, 0, include_flags, require_flags, exclude_flags, false, false);
     if (bad) { set_error(info, bad); delete b; return; }
     b->P.min_mapq = (int32_t)min_mapq; b->P.include_flags = (int32_t)include_flags; b->P.require_flags = (int32_t)require_flags; b->P.exclude_flags = (int32_t)exclude_flags;
     b->P.count_deletions = count_deletions ? 1 : 0; b->P.count_ref_skips = count_ref_skips ? 1 : 0;

@@ -27,13 +27,10 @@ static void bam_bin_counts_bind(duckdb_bind_info info) {
     (void)named_int(info, "include_flags", &include_flags); (void)named_int(info, "require_flags", &require_flags); (void)named_int(info, "exclude_flags", &exclude_flags);
     (void)named_string(info, "dedup", dedup); (void)named_string(info, "region", region); (void)named_string(info, "index_path", idx);
     const bool emit_zero = named_flag(info, "emit_zero_bins");
-    const char *bad = nullptr;
+    BamFilterMsg m; const char *bad = nullptr;
     if (bin_width <= 0) bad = "bam_bin_counts: bin_width must be > 0";
-    else if (min_mapq < 0 || min_mapq > 255) bad = "bam_bin_counts: min_mapq must be between 0 and 255";
-    else if (include_flags < 0 || include_flags > 65535) bad = "bam_bin_counts: include_flags must be between 0 and 65535";
-    else if (require_flags < 0 || require_flags > 65535) bad = "bam_bin_counts: require_flags must be between 0 and 65535";
-    else if (exclude_flags < 0 || exclude_flags > 65535) bad = "bam_bin_counts: exclude_flags must be between 0 and 65535";
-    else if (dedup != "none" && dedup != "adjacent") bad = "bam_bin_counts: dedup must be one of: none, adjacent";
+    else bad = bam_filter_check(m, "bam_bin_counts", 0, min_mapq, 0, include_flags, require_flags, exclude_flags, false, false);
+    if (!bad && dedup != "none" && dedup != "adjacent") bad = "bam_bin_counts: dedup must be one of: none, adjacent";
     if (bad) { set_error(info, bad); delete b; return; }
     b->P.bin_width = bin_width; b->P.min_mapq = (int32_t)min_mapq; b->P.include_flags = (int32_t)include_flags; b->P.require_flags = (int32_t)require_flags; b->P.exclude_flags = (int32_t)exclude_flags;
     b->P.dedup = dedup == "adjacent" ? DHTS_BINS_DEDUP_ADJACENT : DHTS_BINS_DEDUP_NONE; b->P.emit_zero_bins = emit_zero ? 1 : 0;

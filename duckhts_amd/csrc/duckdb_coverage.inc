@@ -28,14 +28,9 @@ static void bam_coverage_bind(duckdb_bind_info info) {
     (void)named_int(info, "include_flags", &include_flags); (void)named_int(info, "require_flags", &require_flags); (void)named_int(info, "exclude_flags", &exclude_flags);
     (void)named_int(info, "min_depth", &min_depth);
     (void)named_string(info, "region", region); (void)named_string(info, "index_path", idx);
-    const char *bad = nullptr;
-    if (min_read_len < 0) bad = "bam_coverage: min_read_len must be >= 0";
-    else if (min_mapq < 0 || min_mapq > 255) bad = "bam_coverage: min_mapq must be between 0 and 255";
-    else if (min_baseq < 0 || min_baseq > 255) bad = "bam_coverage: min_baseq must be between 0 and 255";
-    else if (include_flags < 0 || include_flags > 65535) bad = "bam_coverage: include_flags must be between 0 and 65535";
-    else if (require_flags < 0 || require_flags > 65535) bad = "bam_coverage: require_flags must be between 0 and 65535";
-    else if (exclude_flags < 0 || exclude_flags > 65535) bad = "bam_coverage: exclude_flags must be between 0 and 65535";
-    else if (min_depth < 1) bad = "bam_coverage: min_depth must be >= 1";
+    BamFilterMsg m;
+    const char *bad = bam_filter_check(m, "bam_coverage", min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, true, true);
+    if (!bad && min_depth < 1) bad = "bam_coverage: min_depth must be >= 1";
     if (bad) { set_error(info, bad); delete b; return; }
     memset(&b->P, 0, sizeof(b->P));
     b->P.min_read_len = min_read_len; b->P.min_depth = min_depth; b->P.min_mapq = (int32_t)min_mapq; b->P.min_baseq = (int32_t)min_baseq;

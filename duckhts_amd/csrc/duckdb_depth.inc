@@ -32,15 +32,10 @@ static void bam_depth_bind(duckdb_bind_info info) {
     (void)named_bool(info, "all_positions", &all_positions); (void)named_bool(info, "all_reference_positions", &all_reference_positions);
     (void)named_bool(info, "include_deletions", &include_deletions); (void)named_bool(info, "suppress_overlaps", &suppress_overlaps);
     (void)named_string(info, "region", region); (void)named_string(info, "index_path", idx); (void)named_string(info, "bed_path", b->bed);
-    const char *bad = nullptr;
-    if (min_read_len < 0) bad = "bam_depth: min_read_len must be >= 0";
-    else if (min_mapq < 0 || min_mapq > 255) bad = "bam_depth: min_mapq must be between 0 and 255";
-    else if (min_baseq < 0 || min_baseq > 255) bad = "bam_depth: min_baseq must be between 0 and 255";
-    else if (include_flags < 0 || include_flags > 65535) bad = "bam_depth: include_flags must be between 0 and 65535";
-    else if (require_flags < 0 || require_flags > 65535) bad = "bam_depth: require_flags must be between 0 and 65535";
-    else if (exclude_flags < 0 || exclude_flags > 65535) bad = "bam_depth: exclude_flags must be between 0 and 65535";
-    else if (suppress_overlaps) bad = DEPTH_NO_OVERLAPS;
-    else if (!b->bed.empty() && !region.empty()) bad = "bam_depth: a BED and regions cannot be combined (give the target rows one way)";
+    BamFilterMsg m;
+    const char *bad = bam_filter_check(m, "bam_depth", min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, true, true);
+    if (!bad && suppress_overlaps) bad = DEPTH_NO_OVERLAPS;
+    if (!bad && !b->bed.empty() && !region.empty()) bad = "bam_depth: a BED and regions cannot be combined (give the target rows one way)";
     if (bad) { set_error(info, bad); delete b; return; }
     memset(&b->P, 0, sizeof(b->P));
     b->P.min_read_len = min_read_len; b->P.min_mapq = (int32_t)min_mapq; b->P.min_baseq = (int32_t)min_baseq;

@@ -12,6 +12,7 @@
 // unchanged.  This file also carries a weak definition of that global and a weak duckhts_init_c_api, which
 // are what a stand-alone libduckhts_amd.so uses; strong definitions from src/duckhts.c win at link time.
 #include "duckdb_surface.h"
+#include "bam_filter_check.h"
 
 #include <time.h>
 #include <condition_variable>

@@ -32,14 +32,9 @@ static void bam_pileup_bind(duckdb_bind_info info) {
     (void)named_bool(info, "include_deletions", &include_deletions); (void)named_bool(info, "include_insertions", &include_insertions);
     (void)named_bool(info, "distinguish_strands", &distinguish_strands);
     (void)named_string(info, "region", region); (void)named_string(info, "index_path", idx);
-    const char *bad = nullptr;
-    if (min_read_len < 0) bad = "bam_pileup: min_read_len must be >= 0";
-    else if (min_mapq < 0 || min_mapq > 255) bad = "bam_pileup: min_mapq must be between 0 and 255";
-    else if (min_baseq < 0 || min_baseq > 255) bad = "bam_pileup: min_baseq must be between 0 and 255";
-    else if (include_flags < 0 || include_flags > 65535) bad = "bam_pileup: include_flags must be between 0 and 65535";
-    else if (require_flags < 0 || require_flags > 65535) bad = "bam_pileup: require_flags must be between 0 and 65535";
-    else if (exclude_flags < 0 || exclude_flags > 65535) bad = "bam_pileup: exclude_flags must be between 0 and 65535";
-    else if (min_nucleotide_depth < 1 || min_nucleotide_depth > INT32_MAX) bad = "bam_pileup: min_nucleotide_depth must be >= 1";
+    BamFilterMsg m;
+    const char *bad = bam_filter_check(m, "bam_pileup", min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, true, true);
+    if (!bad && (min_nucleotide_depth < 1 || min_nucleotide_depth > INT32_MAX)) bad = "bam_pileup: min_nucleotide_depth must be >= 1";
     if (bad) { set_error(info, bad); delete b; return; }
     memset(&b->P, 0, sizeof(b->P));
     b->P.min_read_len = min_read_len; b->P.min_mapq = (int32_t)min_mapq; b->P.min_baseq = (int32_t)min_baseq;

@@ -81,18 +81,24 @@ def test_the_python_mirror_binds_the_entries():
 
 
 def test_the_inc_states_the_errors_the_header_promises():
-    inc, ddb = source("dhts_bam_depth.inc"), source("duckdb_depth.inc")
+    inc, ddb, acc, chk = source("dhts_bam_depth.inc"), source("duckdb_depth.inc"), source("dhts_bam_accum.inc"), source("bam_filter_check.h")
     msgs = re.findall(r'"(bam_depth[^"]+ [^"]*)"', inc)                                     # (every literal but the bare name dep_layout is given)
     assert msgs and all(m.startswith("bam_depth: ") for m in msgs)
-    for which in ("min_mapq", "min_baseq", "include_flags", "require_flags", "exclude_flags"):
-        line = f"bam_depth: {which} must be between 0 and {255 if which.startswith('min_') else 65535}"
-        assert line in inc and line in ddb
-    for line in ("bam_depth: min_read_len must be >= 0", "bam_depth: a BED and regions cannot be combined (give the target rows one way)"):
-        assert line in inc and line in ddb
+    # the six range checks are written once, in the header both translation units include: one format each, which give the promised lines;
+    # the open and the bind call it with this function's name
+    assert chk.count('"%s: min_read_len must be >= 0"') == 1 and chk.count('"%s: %s must be between 0 and %d"') == 1 and chk.count("must be") == 2
+    for which, top in (("min_mapq", 255), ("min_baseq", 255), ("include_flags", 65535), ("require_flags", 65535), ("exclude_flags", 65535)):
+        assert '{"%s", %s, %d, ' % (which, which, top) in chk
+        assert "%s: %s must be between 0 and %d" % ("bam_depth", which, top) == f"bam_depth: {which} must be between 0 and {255 if which.startswith('min_') else 65535}"
+    assert "%s: min_read_len must be >= 0" % "bam_depth" == "bam_depth: min_read_len must be >= 0"
+    assert inc.count('bam_filter_check(m, "bam_depth", p->min_read_len, ') == 1 and ddb.count('bam_filter_check(m, "bam_depth", min_read_len, ') == 1
+    line = "bam_depth: a BED and regions cannot be combined (give the target rows one way)"
+    assert line in inc and line in ddb
     assert "bam_depth: suppress_overlaps is not supported (mates are not paired on the device)" in ddb
     # the layout is shared, not copied: bam_coverage's open and bam_depth's both call dep_layout, and the overlap error is written once
     cov = source("dhts_bam_coverage.inc")
-    assert cov.count("dep_layout(") == 2 and inc.count("dep_layout(c, S,") == 1 and (cov + inc).count("overlap (one row is answered per region") == 1
+    assert acc.count("static int dep_layout(") == 1 and cov.count("dep_layout(c, S,") == 1 and inc.count("dep_layout(c, S,") == 1
+    assert (acc + cov + inc).count("overlap (one row is answered per region") == 1 and "overlap (one row is answered per region" in acc
     assert "rbase" not in inc.split("int dhts_bam_depth_accumulate")[0]
 
 
@@ -101,9 +107,14 @@ def test_the_sources_are_part_of_the_build():
     deps = {os.path.basename(p) for p in ge.HIP_DEPS}
     assert {"bam_depth.hip", "dhts_bam_depth.inc", "duckdb_depth.inc"} <= deps
     assert "register_bam_depth_function" in ge.declared_exports() and set(ENTRIES) <= set(ge.declared_exports())
-    api = source("dhts_api.hip")
+    api, ext = source("dhts_api.hip"), source("duckdb_ext.cpp")
     assert '#include "bam_depth.hip"' in api and '#include "dhts_bam_depth.inc"' in api
-    ext = source("duckdb_ext.cpp")
+    # the scaffold of the five count functions and the shared range checks: built, and included in front of the first of them
+    assert {"dhts_bam_accum.inc", "bam_filter_check.h"} <= deps
+    assert api.index('#include "dhts_fasta_nuc.inc"') < api.index('#include "dhts_bam_accum.inc"') < api.index('#include "dhts_bam_bins.inc"')
+    assert '#include "bam_filter_check.h"' in api and '#include "bam_filter_check.h"' in ext
+    for name, fn in (("bins", "bam_bin_counts"), ("bedcov", "bam_bedcov"), ("coverage", "bam_coverage"), ("depth", "bam_depth"), ("pileup", "bam_pileup")):
+        assert source(f"dhts_bam_{name}.inc").count(f'bam_filter_check(m, "{fn}", ') == 1 and source(f"duckdb_{name}.inc").count(f'bam_filter_check(m, "{fn}", ') == 1
     assert ext.index('#include "duckdb_depth.inc"') > ext.index('#include "duckdb_coverage.inc"')
     assert '#include "bam_coverage.hip"' in source("bam_depth.hip")
     # bam_coverage launches what it launched: the two instantiations of bam_depth_add, and dep_tile_carry in its result

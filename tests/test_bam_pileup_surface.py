@@ -88,29 +88,38 @@ def test_the_python_mirror_binds_the_entries():
 
 
 def test_the_inc_states_the_errors_the_header_promises():
-    inc, ddb = source("dhts_bam_pileup.inc"), source("duckdb_pileup.inc")
+    inc, ddb, acc, chk = source("dhts_bam_pileup.inc"), source("duckdb_pileup.inc"), source("dhts_bam_accum.inc"), source("bam_filter_check.h")
     msgs = re.findall(r'"(bam_pileup[^"]+ [^"]*)"', inc)                                    # (every literal but the bare name dep_layout is given)
     assert msgs and all(m.startswith("bam_pileup: ") for m in msgs)
-    for which in ("min_mapq", "min_baseq", "include_flags", "require_flags", "exclude_flags"):
-        assert M.err_range(which) in inc and M.err_range(which) in ddb
-    for line in (M.ERR_READ_LEN, M.ERR_MIN_DEPTH):
-        assert line in inc and line in ddb
+    # the six range checks are written once, in the header both translation units include: one format each, which give the promised lines;
+    # the open and the bind call it with this function's name
+    assert chk.count('"%s: min_read_len must be >= 0"') == 1 and chk.count('"%s: %s must be between 0 and %d"') == 1 and chk.count("must be") == 2
+    for which, top in (("min_mapq", 255), ("min_baseq", 255), ("include_flags", 65535), ("require_flags", 65535), ("exclude_flags", 65535)):
+        assert '{"%s", %s, %d, ' % (which, which, top) in chk
+        assert "%s: %s must be between 0 and %d" % ("bam_pileup", which, top) == M.err_range(which)
+    assert "%s: min_read_len must be >= 0" % "bam_pileup" == M.ERR_READ_LEN
+    assert inc.count('bam_filter_check(m, "bam_pileup", p->min_read_len, ') == 1 and ddb.count('bam_filter_check(m, "bam_pileup", min_read_len, ') == 1
+    assert M.ERR_MIN_DEPTH in inc and M.ERR_MIN_DEPTH in ddb
     for which in ("include_deletions", "include_insertions", "distinguish_strands"):
         assert M.err_switch(which) in inc
-    assert M.ERR_NOT_OPEN in inc and M.ERR_BAM_NOT_OPEN in inc and M.ERR_SHARD in inc and M.ERR_STALE in inc and M.ERR_PATH in ddb
+    assert M.ERR_NOT_OPEN in inc and M.ERR_BAM_NOT_OPEN in inc and M.ERR_SHARD in inc and M.ERR_PATH in ddb
+    # the stale-batch error: the scaffold's format, written once, with this function's name and what it reads where the scan left it
+    stale = '"%s: the batch is not the one dhts_bam_next_batch returned last on this context (%s)"'
+    assert acc.count(stale) == 1 and (stale[1:-1] % ("bam_pileup", "")).startswith(M.ERR_STALE)
+    assert 'accum_batch_ok(c, PILEUP_WHO, S, b, false, "CIGAR, SEQ and QUAL are read where the scan left them")' in inc and 'PILEUP_WHO = {"bam_pileup", ' in inc
     # the layout is shared, not copied: the opens call dep_layout, and the overlap and the cap errors are written once, with the table's noun
     cov = source("dhts_bam_coverage.inc")
-    assert inc.count("dep_layout(c, S,") == 1 and '"count table"' in inc and (cov + inc).count("overlap (one row is answered per region") == 1
-    assert (cov + inc).count("per position of every row") == 1 and '"depth table"' in cov
+    assert inc.count("dep_layout(c, S,") == 1 and '"count table"' in inc and (acc + cov + inc).count("overlap (one row is answered per region") == 1
+    assert (acc + cov + inc).count("per position of every row") == 1 and "per position of every row" in acc and 'noun = "depth table"' in acc
 
 
 def test_the_sources_are_part_of_the_build():
     import __graft_entry__ as ge
     deps = {os.path.basename(p) for p in ge.HIP_DEPS}
-    assert {"bam_pileup.hip", "dhts_bam_pileup.inc", "duckdb_pileup.inc"} <= deps
+    assert {"bam_pileup.hip", "dhts_bam_pileup.inc", "duckdb_pileup.inc", "dhts_bam_accum.inc", "bam_filter_check.h"} <= deps
     assert set(ENTRIES + OTHERS) <= set(ge.declared_exports())
     api = source("dhts_api.hip")
-    assert '#include "bam_pileup.hip"' in api and api.index('#include "dhts_bam_pileup.inc"') > api.index('#include "dhts_bam_depth.inc"')
+    assert '#include "bam_pileup.hip"' in api and api.index('#include "dhts_bam_pileup.inc"') > api.index('#include "dhts_bam_depth.inc"') > api.index('#include "dhts_bam_accum.inc"')
     ext = source("duckdb_ext.cpp")
     assert ext.index('#include "duckdb_pileup.inc"') > ext.index('#include "duckdb_depth.inc"')
     assert ext.index("register_bam_pileup_function(conn)") > ext.index("register_bam_depth_function(conn)")              # registered last

@@ -122,7 +122,9 @@ def test_bind_errors_without_a_device(tmp_path):
         assert "unknown named parameter" not in out
     # the parameters are checked in front of the file
     for named, msg in (([("min_mapq", "256")], M.ERR_MAPQ), ([("min_mapq", "-1")], M.ERR_MAPQ), ([("include_flags", "65536")], M.err_flags("include")),
-                       ([("require_flags", "-1")], M.err_flags("require")), ([("exclude_flags", "65536")], M.err_flags("exclude"))):
+                       ([("require_flags", "-1")], M.err_flags("require")), ([("exclude_flags", "65536")], M.err_flags("exclude")),
+                       # wrong in two ways: the first in the order of the checks is reported
+                       ([("min_mapq", "256"), ("include_flags", "65536")], M.ERR_MAPQ), ([("require_flags", "-1"), ("exclude_flags", "70000")], M.err_flags("require"))):
         rc, out, _ = bedcov("/no/such/file.bam", "x.bed", named=named)
         assert rc == 3 and out == "ERROR bind: " + msg, out
 

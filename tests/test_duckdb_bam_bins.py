@@ -109,7 +109,10 @@ def test_path_error_without_a_device(tmp_path):
     # the parameters are checked in front of the file
     for named, msg in (([("bin_width", "0")], M.ERR_BIN_WIDTH), ([("bin_width", "-5")], M.ERR_BIN_WIDTH), ([("min_mapq", "256")], M.ERR_MAPQ), ([("min_mapq", "-1")], M.ERR_MAPQ),
                        ([("include_flags", "65536")], M.err_flags("include")), ([("require_flags", "-1")], M.err_flags("require")), ([("exclude_flags", "65536")], M.err_flags("exclude")),
-                       ([("dedup", "optical")], M.ERR_DEDUP)):
+                       ([("dedup", "optical")], M.ERR_DEDUP),
+                       # wrong in two ways: the first in the order of the checks is reported
+                       ([("bin_width", "0"), ("min_mapq", "256")], M.ERR_BIN_WIDTH), ([("min_mapq", "256"), ("include_flags", "65536")], M.ERR_MAPQ),
+                       ([("require_flags", "-1"), ("exclude_flags", "70000")], M.err_flags("require")), ([("dedup", "optical"), ("exclude_flags", "70000")], M.err_flags("exclude"))):
         rc, out, _ = bins("/no/such/file.bam", named=named)
         assert rc == 3 and out == "ERROR bind: " + msg, out
 

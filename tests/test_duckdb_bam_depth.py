@@ -149,7 +149,12 @@ def test_bind_errors_without_a_device():
     for named, msg in (([("min_mapq", "256")], M.err_range("min_mapq")), ([("min_mapq", "-1")], M.err_range("min_mapq")), ([("min_baseq", "256")], M.err_range("min_baseq")),
                        ([("min_baseq", "-1")], M.err_range("min_baseq")), ([("include_flags", "65536")], M.err_range("include_flags")), ([("require_flags", "-1")], M.err_range("require_flags")),
                        ([("exclude_flags", "65536")], M.err_range("exclude_flags")), ([("min_read_len", "-1")], M.ERR_READ_LEN), ([("suppress_overlaps", "true")], M.ERR_SUPPRESS),
-                       ([("bed_path", "/no/such.bed"), ("region", "c1:1-5")], M.ERR_BED_AND_REGION)):
+                       ([("bed_path", "/no/such.bed"), ("region", "c1:1-5")], M.ERR_BED_AND_REGION),
+                       # wrong in two ways: the first in the order of the checks is reported
+                       ([("min_read_len", "-1"), ("min_mapq", "256")], M.ERR_READ_LEN), ([("min_baseq", "-1"), ("include_flags", "65536")], M.err_range("min_baseq")),
+                       ([("require_flags", "-1"), ("exclude_flags", "70000")], M.err_range("require_flags")),
+                       ([("suppress_overlaps", "true"), ("exclude_flags", "70000")], M.err_range("exclude_flags")),
+                       ([("suppress_overlaps", "true"), ("bed_path", "/no/such.bed"), ("region", "c1:1-5")], M.ERR_SUPPRESS)):
         rc, out, _ = depth("/no/such/file.bam", named=named)
         assert rc == 3 and out == "ERROR bind: " + msg, out
 

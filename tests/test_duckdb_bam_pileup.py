@@ -133,7 +133,11 @@ def test_bind_errors_without_a_device():
     # the parameters are checked in front of the file
     for named, msg in (([("min_mapq", "256")], M.err_range("min_mapq")), ([("min_mapq", "-1")], M.err_range("min_mapq")), ([("min_baseq", "256")], M.err_range("min_baseq")),
                        ([("min_baseq", "-1")], M.err_range("min_baseq")), ([("include_flags", "65536")], M.err_range("include_flags")), ([("require_flags", "-1")], M.err_range("require_flags")),
-                       ([("exclude_flags", "65536")], M.err_range("exclude_flags")), ([("min_read_len", "-1")], M.ERR_READ_LEN), ([("min_nucleotide_depth", "0")], M.ERR_MIN_DEPTH)):
+                       ([("exclude_flags", "65536")], M.err_range("exclude_flags")), ([("min_read_len", "-1")], M.ERR_READ_LEN), ([("min_nucleotide_depth", "0")], M.ERR_MIN_DEPTH),
+                       # wrong in two ways: the first in the order of the checks is reported
+                       ([("min_read_len", "-1"), ("min_mapq", "256")], M.ERR_READ_LEN), ([("min_baseq", "-1"), ("include_flags", "65536")], M.err_range("min_baseq")),
+                       ([("require_flags", "-1"), ("exclude_flags", "70000")], M.err_range("require_flags")),
+                       ([("min_nucleotide_depth", "0"), ("exclude_flags", "70000")], M.err_range("exclude_flags"))):
         rc, out, _ = pileup("/no/such/file.bam", named=named)
         assert rc == 3 and out == "ERROR bind: " + msg, out
 

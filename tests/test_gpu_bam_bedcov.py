@@ -357,7 +357,10 @@ def test_calls_in_the_wrong_state(rng):
             with pytest.raises(duckhts_amd.DhtsError, match="dhts_bam_bedcov_open not called"):
                 call()
         for kw, msg in ((dict(min_mapq=256), M.ERR_MAPQ), (dict(min_mapq=-1), M.ERR_MAPQ), (dict(include_flags=65536), M.err_flags("include")),
-                        (dict(require_flags=-1), M.err_flags("require")), (dict(exclude_flags=70000), M.err_flags("exclude"))):
+                        (dict(require_flags=-1), M.err_flags("require")), (dict(exclude_flags=70000), M.err_flags("exclude")),
+                        # wrong in two ways: the first in the order of the checks is reported
+                        (dict(min_mapq=256, include_flags=65536), M.ERR_MAPQ), (dict(require_flags=-1, exclude_flags=70000), M.err_flags("require")),
+                        (dict(count_deletions=2, exclude_flags=70000), M.err_flags("exclude"))):
             with pytest.raises(duckhts_amd.DhtsError) as e:
                 ctx.bam_bedcov_open(bctx, **kw)
             assert str(e.value) == msg

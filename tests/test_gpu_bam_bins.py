@@ -241,7 +241,10 @@ def test_calls_in_the_wrong_state(rng):
             with pytest.raises(duckhts_amd.DhtsError, match="dhts_bam_bins_open not called"):
                 call()
         for kw, msg in ((dict(bin_width=0), M.ERR_BIN_WIDTH), (dict(min_mapq=256), M.ERR_MAPQ), (dict(include_flags=65536), M.err_flags("include")),
-                        (dict(require_flags=-1), M.err_flags("require")), (dict(exclude_flags=70000), M.err_flags("exclude")), (dict(dedup="optical"), M.ERR_DEDUP)):
+                        (dict(require_flags=-1), M.err_flags("require")), (dict(exclude_flags=70000), M.err_flags("exclude")), (dict(dedup="optical"), M.ERR_DEDUP),
+                        # wrong in two ways: the first in the order of the checks is reported
+                        (dict(bin_width=0, min_mapq=256), M.ERR_BIN_WIDTH), (dict(min_mapq=256, include_flags=65536), M.ERR_MAPQ),
+                        (dict(require_flags=-1, exclude_flags=70000), M.err_flags("require"))):
             with pytest.raises(duckhts_amd.DhtsError) as e:
                 ctx.bam_bins_open(**kw)
             assert str(e.value) == msg

@@ -389,7 +389,10 @@ def test_calls_in_the_wrong_state_and_refusals(rng):
                 call()
         for kw, msg in ((dict(min_mapq=256), M.err_range("min_mapq")), (dict(min_mapq=-1), M.err_range("min_mapq")), (dict(min_baseq=256), M.err_range("min_baseq")),
                         (dict(min_baseq=-1), M.err_range("min_baseq")), (dict(include_flags=65536), M.err_range("include_flags")), (dict(require_flags=-1), M.err_range("require_flags")),
-                        (dict(exclude_flags=70000), M.err_range("exclude_flags")), (dict(min_read_len=-1), M.ERR_READ_LEN), (dict(min_depth=0), M.ERR_DEPTH)):
+                        (dict(exclude_flags=70000), M.err_range("exclude_flags")), (dict(min_read_len=-1), M.ERR_READ_LEN), (dict(min_depth=0), M.ERR_DEPTH),
+                        # wrong in two ways: the first in the order of the checks is reported
+                        (dict(min_read_len=-1, min_mapq=256), M.ERR_READ_LEN), (dict(min_baseq=-1, include_flags=65536), M.err_range("min_baseq")),
+                        (dict(require_flags=-1, exclude_flags=70000), M.err_range("require_flags")), (dict(min_depth=0, exclude_flags=70000), M.err_range("exclude_flags"))):
             with pytest.raises(duckhts_amd.DhtsError) as e:
                 ctx.bam_coverage_open(**kw)
             assert str(e.value) == msg

@@ -466,7 +466,11 @@ def test_calls_in_the_wrong_state_and_refusals(rng):
         for kw, msg in ((dict(min_mapq=256), M.err_range("min_mapq")), (dict(min_mapq=-1), M.err_range("min_mapq")), (dict(min_baseq=256), M.err_range("min_baseq")),
                         (dict(min_baseq=-1), M.err_range("min_baseq")), (dict(include_flags=65536), M.err_range("include_flags")), (dict(require_flags=-1), M.err_range("require_flags")),
                         (dict(exclude_flags=70000), M.err_range("exclude_flags")), (dict(min_read_len=-1), M.ERR_READ_LEN), (dict(include_deletions=2), M.ERR_DELETIONS),
-                        (dict(include_deletions=-1), M.ERR_DELETIONS), (dict(all_positions=3), M.ERR_ALL), (dict(all_positions=-1), M.ERR_ALL)):
+                        (dict(include_deletions=-1), M.ERR_DELETIONS), (dict(all_positions=3), M.ERR_ALL), (dict(all_positions=-1), M.ERR_ALL),
+                        # wrong in two ways: the first in the order of the checks is reported
+                        (dict(min_read_len=-1, min_mapq=256), M.ERR_READ_LEN), (dict(min_baseq=-1, include_flags=65536), M.err_range("min_baseq")),
+                        (dict(require_flags=-1, exclude_flags=70000), M.err_range("require_flags")), (dict(include_deletions=2, exclude_flags=70000), M.err_range("exclude_flags")),
+                        (dict(include_deletions=2, all_positions=3), M.ERR_DELETIONS)):
             with pytest.raises(duckhts_amd.DhtsError) as e:
                 ctx.bam_depth_open(**kw)
             assert str(e.value) == msg

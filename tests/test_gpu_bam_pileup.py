@@ -383,7 +383,11 @@ def test_calls_in_the_wrong_state_and_refusals():
                         (dict(min_baseq=-1), M.err_range("min_baseq")), (dict(include_flags=65536), M.err_range("include_flags")), (dict(require_flags=-1), M.err_range("require_flags")),
                         (dict(exclude_flags=70000), M.err_range("exclude_flags")), (dict(min_read_len=-1), M.ERR_READ_LEN), (dict(include_deletions=2), M.err_switch("include_deletions")),
                         (dict(include_insertions=-1), M.err_switch("include_insertions")), (dict(distinguish_strands=2), M.err_switch("distinguish_strands")),
-                        (dict(min_nucleotide_depth=0), M.ERR_MIN_DEPTH)):
+                        (dict(min_nucleotide_depth=0), M.ERR_MIN_DEPTH),
+                        # wrong in two ways: the first in the order of the checks is reported
+                        (dict(min_read_len=-1, min_mapq=256), M.ERR_READ_LEN), (dict(min_baseq=-1, include_flags=65536), M.err_range("min_baseq")),
+                        (dict(require_flags=-1, exclude_flags=70000), M.err_range("require_flags")), (dict(include_deletions=2, exclude_flags=70000), M.err_range("exclude_flags")),
+                        (dict(distinguish_strands=2, min_nucleotide_depth=0), M.err_switch("distinguish_strands"))):
             with pytest.raises(duckhts_amd.DhtsError) as e:
                 ctx.bam_pileup_open(**kw)
             assert str(e.value) == msg

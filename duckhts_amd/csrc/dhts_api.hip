@@ -21,6 +21,7 @@
 #include "bam_coverage.hip"
 #include "bam_depth.hip"
 #include "bam_pileup.hip"
+#include "bam_bedgraph.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -204,7 +205,7 @@ struct NucState {
     DevBuf ents, names, table, cum, in_tid, in_start, in_end, tmp, keep, rank, src, rows, err, npieces, piece_off, counts;
     DevBuf name_len, name_off, name_bytes, name_valid, seq_len, seq_off32, seq_off64, seq_valid, ones, fixed[NUC_N_COLS];
 };
-// What the states of the five bam_* count functions start with (dhts_bam_accum.inc works on it): whether the function is open, the contigs of
+// What the states of the six bam_* count functions start with (dhts_bam_accum.inc works on it): whether the function is open, the contigs of
 // the header, the status the scan's stream ended on, the step counters on the device and the columns of the last result batch
 struct AccumBase { bool open = false; int32_t n_ref = 0, status = 0; std::vector<dhts_col> out; DevBuf steps; };
 // bam_bin_counts (bam_bins.hip, dhts_bam_bins.inc): the parameters, the table of counters (two 64-bit words per bin) with the bins in front of
@@ -258,6 +259,13 @@ struct PileupState : AccumBase, DepLayout, DepPager {
     uint64_t n_result_rows = 0;
     DevBuf row_tid, step, rlen, k0, k1, part, rowres, out_tid, out_pos, out_strand, out_nuc, out_count;
 };
+// bam_bedgraph (bam_bedgraph.hip, dhts_bam_bedgraph.inc): bam_depth's state with the classes in the parameters, and of a result the next
+// boundary of any class behind every tile (tnext) beside the depth (tsum) and the result index (toff) in front of it
+struct BedgraphState : AccumBase, DepLayout, DepPager {
+    bool res_ready = false; dhts_bedgraph_params P;
+    uint64_t n_bed_skipped = 0, n_runs = 0;
+    DevBuf touched, row_tid, step, rlen, k0, k1, tsum, part, rowres, tnext, out_tid, out_start, out_end, out_depth;
+};
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
 struct UdfState {
@@ -306,6 +314,7 @@ struct dhts_ctx {
     CoverageState dep;
     DepthState dpt;
     PileupState pil;
+    BedgraphState bdg;
     UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
@@ -615,6 +624,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_coverage.inc"
 #include "dhts_bam_depth.inc"
 #include "dhts_bam_pileup.inc"
+#include "dhts_bam_bedgraph.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

@@ -1,5 +1,5 @@
 // dhts_bam_accum.inc -- part of dhts_api.hip (included there in front of dhts_bam_bins.inc, inside its extern "C" block; not a translation unit
-// of its own): the host scaffold of the five bam_* count functions (bam_bin_counts, bam_bedcov, bam_coverage, bam_depth, bam_pileup).  It owns
+// of its own): the host scaffold of the six bam_* count functions (bam_bin_counts, bam_bedcov, bam_coverage, bam_depth, bam_pileup, bam_bedgraph).  It owns
 // what carries none of the work and was the same in all of them: the checks in front of an accumulate, the scan loop, the read-out of the step
 // counters, the target rows and their layout in the table (dep_layout), the arguments of the depth kernels, the windows and tiles of a result
 // page, the reset of a result batch's columns, and the read-back of dhts_col columns.  A function keeps its own extern "C" entry points, its
@@ -95,7 +95,7 @@ static int bed_rows_read(dhts_ctx *c, dhts_ctx *b, uint64_t max_rows, std::vecto
     return 0;
 }
 
-// ---- the layout bam_coverage, bam_depth and bam_pileup share ------------------------------------------------------------------------------
+// ---- the layout bam_coverage, bam_depth, bam_pileup and bam_bedgraph share ------------------------------------------------------------------------------
 #define COVERAGE_MAX_TABLE_BYTES (16ull << 30)
 static uint64_t g_coverage_max_table_bytes = COVERAGE_MAX_TABLE_BYTES;
 // tests: the most bytes the table may take (0: the contract's 16 GiB)
@@ -112,6 +112,29 @@ static void dep_target_rows(const dhts_ctx *c, DepLayout &L, std::vector<size_t>
             L.o_tid.push_back(r.tid); L.o_beg.push_back(r.beg < len ? r.beg : len); L.o_end.push_back(r.end < len ? r.end : len); o_given.push_back(g);
         }
     } else for (size_t t = 0; t < c->ref_len.size(); t++) { L.o_tid.push_back((int32_t)t); L.o_beg.push_back(0); L.o_end.push_back((int64_t)c->ref_len[t]); }
+}
+
+// the target rows of a BED context b (bam_depth, bam_bedgraph): the union of its rows -- per contig in header order, sorted by start, rows that
+// overlap or touch merged, clipped to the contig, empty ones dropped.  n_skipped: the rows that name a contig the header lacks
+static int dep_bed_target_rows(dhts_ctx *c, dhts_ctx *b, DepLayout &L, uint64_t &n_skipped) {
+    L.o_tid.clear(); L.o_beg.clear(); L.o_end.clear(); L.o_k.clear();
+    n_skipped = 0;
+    std::vector<int32_t> tid; std::vector<int64_t> beg, end; uint64_t n_bed = 0;
+    if (bed_rows_read(c, b, ~0ull, tid, beg, end, n_bed)) return -1;
+    std::vector<uint32_t> order;
+    for (size_t i = 0; i < tid.size(); i++) {
+        if (tid[i] < 0) { n_skipped++; continue; }
+        const int64_t len = (int64_t)c->ref_len[(size_t)tid[i]];
+        if (beg[i] < 0) beg[i] = 0;
+        if (end[i] > len) end[i] = len;
+        if (end[i] > beg[i]) order.push_back((uint32_t)i);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return tid[x] != tid[y] ? tid[x] < tid[y] : beg[x] < beg[y]; });
+    for (const uint32_t i : order) {
+        if (!L.o_tid.empty() && L.o_tid.back() == tid[i] && beg[i] <= L.o_end.back()) { if (end[i] > L.o_end.back()) L.o_end.back() = end[i]; }
+        else { L.o_tid.push_back(tid[i]); L.o_beg.push_back(beg[i]); L.o_end.push_back(end[i]); }
+    }
+    return 0;
 }
 
 // S.o_tid / o_beg / o_end hold the target rows in the order they are answered in, clipped.  They are sorted by (contig, start) with the empty
@@ -170,7 +193,8 @@ static int dep_layout(dhts_ctx *c, DepLayout &S, const char *fn, const std::vect
 
 extern "C++" {
 // the per-batch scratch and the arguments of the depth kernels (bam_depth_classify* and the add kernels of bam_coverage, bam_depth and
-// bam_pileup) from the batch, the scan's stream, the layout and the function's filter; S: CoverageState, DepthState or PileupState
+// bam_pileup; bam_bedgraph launches bam_depth's) from the batch, the scan's stream, the layout and the function's filter; S: CoverageState, DepthState,
+// PileupState or BedgraphState
 template <typename State> static int dep_args(dhts_ctx *c, State &S, const dhts_bam_batch *b, DepArgs &a) {
     const int64_t n = b->n_rows;
     ENSURE(c, S.step, (size_t)n + 64); ENSURE(c, S.rlen, (size_t)n * 8 + 64); ENSURE(c, S.k0, (size_t)n * 4 + 64); ENSURE(c, S.k1, (size_t)n * 4 + 64);
@@ -184,7 +208,7 @@ template <typename State> static int dep_args(dhts_ctx *c, State &S, const dhts_
     return 0;
 }
 
-// the seven counters dhts_coverage_stats, dhts_depth_stats and dhts_pileup_stats share, from the DEP_N_STEPS step counters
+// the seven counters dhts_coverage_stats, dhts_depth_stats, dhts_pileup_stats and dhts_bedgraph_stats share, from the DEP_N_STEPS step counters
 template <typename Stats> static void dep_stats_common(Stats *out, const uint64_t *s) {
     out->n_flag_filtered = s[DEP_STEP_FLAG]; out->n_unplaced = s[DEP_STEP_UNPLACED]; out->n_short = s[DEP_STEP_SHORT]; out->n_low_mapq = s[DEP_STEP_MAPQ];
     out->n_outside = s[DEP_STEP_OUTSIDE]; out->n_counted = s[DEP_STEP_COUNTED];
@@ -202,7 +226,7 @@ template <typename T> static int depth_carry(dhts_ctx *c, DevBuf &part, T *v, ui
 }
 }
 
-// ---- a page of a result that is emitted out of the table (bam_depth, bam_pileup) ----------------------------------------------------------
+// ---- a page of a result that is emitted out of the table (bam_depth, bam_pileup, bam_bedgraph) ----------------------------------------------------------
 // The host walks the rows in the order they are answered in and turns the next max_rows result rows into windows of result indices -- one per
 // run of rows that follow each other in both orders.  rows: the page's rows; o / within: where the page behind it starts (the caller stores
 // them in the pager once the page is made); tiles[2 w], tiles[2 w + 1]: the first and the last tile that holds window w.

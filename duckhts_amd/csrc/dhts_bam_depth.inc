@@ -3,7 +3,7 @@
 // dep_layout, the layout both functions share.  A batch is classified and added where it lies, as in bam_coverage, by the add kernel's form
 // without per-row words.  The result is counted once (tile sums, their carry, the positions every tile emits, their carry, one result index per
 // row to the host) and then emitted page by page: the next max_rows positions become windows of result indices (dep_page_windows), and dep_emit
-// is launched on the tiles that hold each window (dep_page_tiles_of).  Those two, bed_rows_read, dep_target_rows, dep_layout, dep_args,
+// is launched on the tiles that hold each window (dep_page_tiles_of).  Those two, dep_bed_target_rows, dep_target_rows, dep_layout, dep_args,
 // depth_carry, the checks in front of a batch, the scan loop, the step counters and the read-back are dhts_bam_accum.inc's.
 static const uint32_t DEPTH_COLMASK = (1u << DHTS_BAM_FLAG) | (1u << DHTS_BAM_RNAME) | (1u << DHTS_BAM_POS) | (1u << DHTS_BAM_MAPQ);   // no string column
 static const AccumWho DEPTH_WHO = {"bam_depth", "bam_depth: dhts_bam_depth_open not called",
@@ -29,25 +29,7 @@ int dhts_bam_depth_open(dhts_ctx *c, const dhts_depth_params *p, dhts_ctx *b) {
     S.n_bed_skipped = 0;
     std::vector<size_t> o_given;
     if (!b) dep_target_rows(c, S, o_given);
-    else {
-        S.o_tid.clear(); S.o_beg.clear(); S.o_end.clear(); S.o_k.clear();
-        // the union of the BED's rows: per contig sorted by start, rows that overlap or touch merged, clipped to the contig, empty ones dropped
-        std::vector<int32_t> tid; std::vector<int64_t> beg, end; uint64_t n_bed = 0;
-        if (bed_rows_read(c, b, ~0ull, tid, beg, end, n_bed)) return -1;
-        std::vector<uint32_t> order;
-        for (size_t i = 0; i < tid.size(); i++) {
-            if (tid[i] < 0) { S.n_bed_skipped++; continue; }
-            const int64_t L = (int64_t)c->ref_len[(size_t)tid[i]];
-            if (beg[i] < 0) beg[i] = 0;
-            if (end[i] > L) end[i] = L;
-            if (end[i] > beg[i]) order.push_back((uint32_t)i);
-        }
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return tid[x] != tid[y] ? tid[x] < tid[y] : beg[x] < beg[y]; });
-        for (const uint32_t i : order) {
-            if (!S.o_tid.empty() && S.o_tid.back() == tid[i] && beg[i] <= S.o_end.back()) { if (end[i] > S.o_end.back()) S.o_end.back() = end[i]; }
-            else { S.o_tid.push_back(tid[i]); S.o_beg.push_back(beg[i]); S.o_end.push_back(end[i]); }
-        }
-    }
+    else if (dep_bed_target_rows(c, b, S, S.n_bed_skipped)) return -1;
     if (dep_layout(c, S, "bam_depth", o_given)) return -1;
     const size_t R = (size_t)S.n_sorted;
     ENSURE(c, S.steps, 64); ENSURE(c, S.touched, (n_ref + 1) * 4 + 64); ENSURE(c, S.row_tid, (R + 1) * 4 + 64);

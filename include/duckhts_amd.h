@@ -745,8 +745,8 @@ int dhts_bam_coverage_batch_fetch(dhts_ctx *, const dhts_coverage_batch *b, void
  *     takes them as given; the table function and the Python function default exclude_flags to 0x704 and the rest to 0.
  *   Limits: bam_coverage's -- 32-bit depth, the table cap and its error (dhts_debug_coverage_max_table_bytes applies to both functions), a
  *     shard or block range refused, a stream that ends on an error has its rows counted and its status carried.
- *   Not in this contract: suppress_overlaps (mates are not paired on the device), several input files, reference / CRAM, max_depth, and a
- *     run-length (bedGraph) form of the result.
+ *   Not in this contract: suppress_overlaps (mates are not paired on the device), several input files, reference / CRAM and max_depth.  The
+ *     run-length (bedGraph) form of the result is bam_bedgraph's (below).
  *   Method: the add pass without the per-row words, a D joined to the runs around it; a carry in two levels for the depth and the result index
  *     in front of every tile; a page is a window of result indices, emitted by the tiles that hold it (csrc/bam_depth.hip).
  * All errors are prefixed "bam_depth:".  Every call on a context in the wrong state fails with a dhts_error that names what is missing. */
@@ -878,6 +878,84 @@ int dhts_bam_pileup_next(dhts_ctx *bam, int64_t max_rows, uint32_t colmask, dhts
  * each rounded up to 8 bytes */
 uint64_t dhts_bam_pileup_batch_host_bytes(const dhts_pileup_batch *b);
 int dhts_bam_pileup_batch_fetch(dhts_ctx *bam, const dhts_pileup_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
+/* ---- bam_bedgraph ----------------------------------------------------------------------------
+ * Per run of equal depth class: chrom, start, end, depth -- bedGraph rows, what `bedtools genomecov -bg / -bga` and `mosdepth --quantize`
+ * print -- cut and paged on the device out of the depth table bam_depth's add pass fills in HBM.  The rows join read_bed, fasta_nuc and
+ * bam_bin_counts on the same 0-based half-open key.  The reference has only a plan for it (.github/PLAN.md, Phase 10), so this is the
+ * specification.
+ *   Input, the six steps with their 64-bit counters, the read interval, the effective CIGAR, the counted bases (include_deletions: every
+ *     reference position of a D operation inside a row counts, a leading or trailing D too; N and P never count) and the target rows -- one
+ *     per @SQ, one per region in the order given, or the merged intervals of a BED (n_bed_skipped; at least 4 KiB of table each, a row's span
+ *     is padded to 1,024 slots): exactly bam_depth's.  A BED together with regions is refused by name; regions that overlap are refused.
+ *   Classes: breaks is up to 16 strictly increasing integers in 1 .. 2147483647.  class(d) = the number of breaks <= d.  The reported depth of
+ *     class 0 is 0, of class j > 0 it is breaks[j - 1] (the class's lower edge; its upper edge is the next break).  Without breaks
+ *     class(d) = d and the reported depth is d.
+ *   Runs: inside one target row a run is a maximal stretch of positions of equal class.  A run never spans two target rows, not even
+ *     adjacent regions of one contig.  A run is emitted iff its class is > 0 or zero_runs is 1; with zero_runs a contig of length L that no
+ *     read touches gives the one row (chrom, 0, L, 0).
+ *   Result: one row per emitted run: chrom (here: the contig's id, int32), start (0-based, int64), end (exclusive, int64), depth (int32, the
+ *     reported depth of the run's class).  No column is ever NULL.  Order: the target rows in the order they are answered in (the order given
+ *     for regions, sorted order otherwise), then by start.
+ *   The identity that defines correctness: without breaks, every row (chrom, start, end, d) of zero_runs = 1 expanded into the positions
+ *     start + 1 .. end is exactly bam_depth with all_positions = 2 on the same input and parameters; zero_runs = 0 gives all_positions = 0.
+ *     There is no counterpart of all_positions = 1 (touched contigs).
+ *   Parameters: min_read_len >= 0; min_mapq, min_baseq 0..255; the three masks 0..65535; include_deletions, zero_runs 0..1; n_breaks 0..16.
+ *     This ABI takes them as given; the table function and the Python function default exclude_flags to 0x704 and the rest to 0.
+ *   Limits: bam_depth's -- 32-bit depth, the table cap and its error (dhts_debug_coverage_max_table_bytes applies here as well), a shard or
+ *     block range refused, a stream that ends on an error has its rows counted and its status carried.
+ *   Not in this contract: a mean depth per class run, the depth histogram, suppress_overlaps, several input files, reference / CRAM, max_depth.
+ *   Method: bam_depth's add pass; per tile the emitted boundaries and its first boundary of any class, a suffix minimum in two levels for the
+ *     next boundary behind every tile and a carry in two levels for the result index in front of it; a page is a window of result indices,
+ *     emitted by the tiles that hold it, and a run that leaves its tile ends where the suffix minimum says, clipped to its row
+ *     (csrc/bam_bedgraph.hip).
+ * All errors are prefixed "bam_bedgraph:".  Every call on a context in the wrong state fails with a dhts_error that names what is missing. */
+enum { DHTS_BEDGRAPH_CHROM = 0, DHTS_BEDGRAPH_START, DHTS_BEDGRAPH_END, DHTS_BEDGRAPH_DEPTH, DHTS_BEDGRAPH_COL_COUNT };
+typedef struct {
+    int64_t min_read_len;    /* >= 0                                                                          */
+    int32_t min_mapq;        /* 0..255                                                                        */
+    int32_t min_baseq;       /* 0..255                                                                        */
+    int32_t require_flags, exclude_flags, include_flags;   /* 0..65535                                        */
+    int32_t include_deletions;                             /* 0 or 1                                          */
+    int32_t zero_runs;                                     /* 0 or 1: runs of class 0 are emitted             */
+    int32_t n_breaks;                                      /* 0..16                                           */
+    int32_t breaks[16];                                    /* the first n_breaks: strictly increasing, >= 1   */
+    int32_t reserved[2];
+} dhts_bedgraph_params;
+typedef struct {
+    uint64_t n_rows, n_flag_filtered, n_unplaced, n_short, n_low_mapq, n_outside, n_counted;
+    uint64_t n_target_rows;  /* target rows (regions, @SQ lines or merged BED intervals)                       */
+    uint64_t n_bed_skipped;  /* BED rows that name a contig the header lacks                                   */
+    uint64_t table_bytes;    /* bytes of the depth table                                                       */
+    uint64_t n_runs;         /* rows of the whole result: valid once a result was taken (dhts_bam_bedgraph_next), 0 before */
+    int32_t status;          /* as in dhts_coverage_stats                                                      */
+    int32_t reserved;
+} dhts_bedgraph_stats;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows follow, 1 = the last page                                                                    */
+    int32_t n_cols;          /* DHTS_BEDGRAPH_COL_COUNT, in that order                                                                     */
+    const dhts_col *cols;    /* host array of descriptors, DEVICE pointers inside: fixed = int32 (chrom, depth) or int64 (start, end) per row,
+                                a null pointer for a column colmask left out; no row is NULL and valid stays a null pointer                 */
+} dhts_bedgraph_batch;
+/* after dhts_bam_open and the optional dhts_bam_set_regions / dhts_bam_load_index.  bed: NULL, or a second context on the same device prepared
+ * as for read_bed (dhts_bed_open); its projection belongs to bam_bedgraph from here on.  The target rows, the depth table and the counters,
+ * zeroed.  A second open starts a new count. */
+int dhts_bam_bedgraph_open(dhts_ctx *bam, const dhts_bedgraph_params *params, dhts_ctx *bed);
+/* the batch dhts_bam_next_batch returned LAST on this context, as in dhts_bam_depth_accumulate.  Starts a result over: the table and the
+ * counters stay intact, the next dhts_bam_bedgraph_next returns the first page of the new result. */
+int dhts_bam_bedgraph_accumulate(dhts_ctx *bam, const dhts_bam_batch *batch);
+/* dhts_bam_next_batch + accumulate to the end of the stream; returns as dhts_bam_coverage_scan does */
+int dhts_bam_bedgraph_scan(dhts_ctx *bam, int64_t max_blocks);
+int dhts_bam_bedgraph_stats(dhts_ctx *bam, dhts_bedgraph_stats *out);
+/* the next <= max_rows rows of the result (0 = 1,048,576 rows: 24 MiB with all four columns).  colmask: bit DHTS_BEDGRAPH_* set = the column
+ * is written and fetched.  The first call after open or accumulate counts the runs of the result from the table, which stays as it is.  The
+ * page's columns stay valid until the next call on the context. */
+int dhts_bam_bedgraph_next(dhts_ctx *bam, int64_t max_rows, uint32_t colmask, dhts_bedgraph_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst (null where the batch has none); the columns follow each other,
+ * each rounded up to 8 bytes */
+uint64_t dhts_bam_bedgraph_batch_host_bytes(const dhts_bedgraph_batch *b);
+int dhts_bam_bedgraph_batch_fetch(dhts_ctx *bam, const dhts_bedgraph_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
 /* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
  * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and

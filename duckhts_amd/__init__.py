@@ -141,6 +141,17 @@ class BedgraphStats(C.Structure):
                 ("n_runs", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DepthHistParams(C.Structure):
+    _fields_ = [("min_read_len", C.c_int64), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32), ("require_flags", C.c_int32), ("exclude_flags", C.c_int32),
+                ("include_flags", C.c_int32), ("include_deletions", C.c_int32), ("depth_cap", C.c_int32), ("per", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class DepthHistStats(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_flag_filtered", C.c_uint64), ("n_unplaced", C.c_uint64), ("n_short", C.c_uint64), ("n_low_mapq", C.c_uint64),
+                ("n_outside", C.c_uint64), ("n_counted", C.c_uint64), ("n_target_rows", C.c_uint64), ("n_groups", C.c_uint64), ("n_bed_skipped", C.c_uint64),
+                ("table_bytes", C.c_uint64), ("hist_bytes", C.c_uint64), ("n_result_rows", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TabixMap(C.Structure):
     _fields_ = [("pair_off", C.c_void_p), ("valid", C.c_void_p), ("n_pairs", C.c_uint64), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p), ("key_nbytes", C.c_uint64),
                 ("val_off", C.c_void_p), ("val_bytes", C.c_void_p), ("val_nbytes", C.c_uint64)]
@@ -211,6 +222,20 @@ BEDGRAPH_COLUMNS = ["tid", "start", "end", "depth"]
 BEDGRAPH_DTYPES = (np.int32, np.int64, np.int64, np.int32)                   # start 0-based, end exclusive
 BEDGRAPH_COLMASK = DEPTH_COLMASK                                            # the columns of the scan bam_bedgraph accumulates (no string column)
 BEDGRAPH_MAX_BREAKS = 16
+DEPTH_HIST_COLUMNS = ["tid", "start", "end", "depth", "n_positions", "n_at_least", "length"]
+DEPTH_HIST_DTYPES = (np.int32, np.int64, np.int64, np.int32, np.int64, np.int64, np.int64)   # start 0-based, end exclusive
+DEPTH_HIST_COLMASK = DEPTH_COLMASK                                          # the columns of the scan bam_depth_hist accumulates (no string column)
+DEPTH_HIST_PER = {"row": 0, "contig": 1}                                    # the C struct's per
+DEPTH_HIST_LDS_BINS = 4096                                                  # csrc/bam_depth_hist.hip: DHI_LDS_BINS, the bins the histogram pass counts in LDS
+DEPTH_HIST_GRID_TARGET = 2048                                               # ... DHI_GRID_TARGET, the workgroups the spans of tiles are cut for
+DEPTH_HIST_SPAN_MIN_TILES = 8                                               # ... DHI_SPAN_MIN_TILES, the shortest span
+
+
+def depth_hist_span_tiles(ntiles):
+    """the tiles (of 1,024 slots of the depth table) one workgroup of the histogram pass owns in a table of ntiles tiles"""
+    return max(DEPTH_HIST_SPAN_MIN_TILES, -(-int(ntiles) // DEPTH_HIST_GRID_TARGET))
+
+
 BEDCOV_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4)                # FLAG, RNAME, POS, MAPQ: no string column (the CIGARs are read in their binary form)
 BINS_COLMASK = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 7)        # FLAG, RNAME, POS, MAPQ, PNEXT: no string column
 
@@ -235,6 +260,7 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_bam_depth_open", "dhts_bam_depth_accumulate", "dhts_bam_depth_scan", "dhts_bam_depth_stats", "dhts_bam_depth_next", "dhts_bam_depth_batch_host_bytes", "dhts_bam_depth_batch_fetch",
            "dhts_bam_pileup_open", "dhts_bam_pileup_accumulate", "dhts_bam_pileup_scan", "dhts_bam_pileup_stats", "dhts_bam_pileup_next", "dhts_bam_pileup_batch_host_bytes", "dhts_bam_pileup_batch_fetch",
            "dhts_bam_bedgraph_open", "dhts_bam_bedgraph_accumulate", "dhts_bam_bedgraph_scan", "dhts_bam_bedgraph_stats", "dhts_bam_bedgraph_next", "dhts_bam_bedgraph_batch_host_bytes", "dhts_bam_bedgraph_batch_fetch",
+           "dhts_bam_hist_open", "dhts_bam_hist_accumulate", "dhts_bam_hist_scan", "dhts_bam_hist_stats", "dhts_bam_hist_next", "dhts_bam_hist_batch_host_bytes", "dhts_bam_hist_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
            "dhts_udf_upload", "dhts_udf_apply", "dhts_udf_result_host_bytes", "dhts_udf_fetch", "dhts_udf_seq_kmers", "dhts_udf_kmers_host_bytes", "dhts_udf_kmers_fetch"]
@@ -332,13 +358,14 @@ def lib():
         L.dhts_nuc_batch_host_bytes.restype = C.c_uint64
         L.dhts_nuc_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_nuc_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
-        # the six bam_* count functions: the stats structure and the arguments of open and next around the common ones
+        # the seven bam_* count functions: the stats structure and the arguments of open and next around the common ones
         for name, stats, open_args, next_args in (("bins", BinsStats, [C.POINTER(BinsParams)], [C.c_int64]),
                                                   ("bedcov", BedcovStats, [C.c_void_p, C.POINTER(BedcovParams)], [C.c_void_p, C.c_int64]),
                                                   ("coverage", CoverageStats, [C.POINTER(CoverageParams)], [C.c_int64]),
                                                   ("depth", DepthStats, [C.POINTER(DepthParams), C.c_void_p], [C.c_int64, C.c_uint32]),
                                                   ("pileup", PileupStats, [C.POINTER(PileupParams)], [C.c_int64, C.c_uint32]),
-                                                  ("bedgraph", BedgraphStats, [C.POINTER(BedgraphParams), C.c_void_p], [C.c_int64, C.c_uint32])):
+                                                  ("bedgraph", BedgraphStats, [C.POINTER(BedgraphParams), C.c_void_p], [C.c_int64, C.c_uint32]),
+                                                  ("hist", DepthHistStats, [C.POINTER(DepthHistParams), C.c_void_p], [C.c_int64, C.c_uint32])):
             f = {what: getattr(L, "dhts_bam_%s_%s" % (name, what)) for what in ("open", "accumulate", "scan", "stats", "next", "batch_host_bytes", "batch_fetch")}
             f["open"].argtypes = [C.c_void_p] + open_args
             f["accumulate"].argtypes = [C.c_void_p, C.POINTER(BamBatch)]
@@ -349,6 +376,10 @@ def lib():
             f["batch_host_bytes"].argtypes = [C.POINTER(BedBatch)]
             f["batch_fetch"].argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
         L.dhts_debug_pileup_add_form.argtypes = [C.c_void_p, C.c_int]
+        L.dhts_debug_hist_max_table_bytes.argtypes = [C.c_uint64]
+        L.dhts_debug_hist_max_table_bytes.restype = None
+        L.dhts_debug_hist_pass_ms.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.dhts_debug_hist_pass_ms.restype = C.c_double
         L.dhts_debug_coverage_max_table_bytes.restype = None
         L.dhts_debug_coverage_max_table_bytes.argtypes = [C.c_uint64]
         L.dhts_debug_bedcov_max_rows.restype = None
@@ -822,12 +853,13 @@ class Context:
         self._chk(self.L.dhts_nuc_intervals(self.h, t.ctypes.data, s.ctypes.data, e.ctypes.data, len(t), C.byref(b)))
         return self.nuc_batch_columns(b)
 
-    # ---- what the six bam_* count functions share (the batches have dhts_bed_batch's layout) ----
-    def _accum_scan(self, name, max_blocks):
+    # ---- what the seven bam_* count functions share (the batches have dhts_bed_batch's layout) ----
+    def _accum_scan(self, name, max_blocks, stats=None):
+        """name: the C entries' (dhts_bam_<name>_*); stats: the method that reads the stats where it is not bam_<name>_stats"""
         rc = getattr(self.L, "dhts_bam_%s_scan" % name)(self.h, max_blocks)
         if rc < 0:
             msg = self.L.dhts_error(self.h).decode()
-            if getattr(self, "bam_%s_stats" % name)()["status"] == 0:        # a call failed (a stream that ended on an error has set its status)
+            if (stats or getattr(self, "bam_%s_stats" % name))()["status"] == 0:        # a call failed (a stream that ended on an error has set its status)
                 raise DhtsError(msg)
         return rc
 
@@ -845,7 +877,7 @@ class Context:
         return arena, host, int(b.n_rows)
 
     def _fixed_cols(self, name, b, mask, names, dtypes):
-        """a page of bare fixed columns (bam_depth, bam_pileup, bam_bedgraph): None for a column the mask leaves out"""
+        """a page of bare fixed columns (bam_depth, bam_pileup, bam_bedgraph, bam_depth_hist): None for a column the mask leaves out"""
         arena, host, n = self._fetch_cols(name, b)
         out = {"n_rows": n}
         for i in range(b.n_cols):
@@ -1008,6 +1040,37 @@ class Context:
         b = BedBatch()
         self._chk(self.L.dhts_bam_bedgraph_next(self.h, max_rows, mask, C.byref(b)))
         return self._fixed_cols("bedgraph", b, mask, BEDGRAPH_COLUMNS, BEDGRAPH_DTYPES)
+
+    # ---- bam_depth_hist (C ABI: dhts_bam_hist_*) ----
+    def bam_depth_hist_open(self, bed_ctx=None, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0, include_deletions=0, depth_cap=1000,
+                            per="row"):
+        """after bam_open and the optional set_regions / load_index; bed_ctx: None, or a second Context on this device after bed_open.  The
+        target rows, their groups, the depth table, the histogram table and the counters, zeroed.  per: 'row' or 'contig' (or the C struct's
+        0 / 1).  The parameters are taken as given (the C ABI's rule): any other per travels as -1, which the C side refuses."""
+        per = DEPTH_HIST_PER.get(per, -1) if isinstance(per, (str, bytes)) else _clip(per, 31)
+        p = DepthHistParams(_clip(min_read_len, 63), _clip(min_mapq, 31), _clip(min_baseq, 31), _clip(require_flags, 31), _clip(exclude_flags, 31), _clip(include_flags, 31),
+                            _clip(include_deletions, 31), _clip(depth_cap, 31), per)
+        self._chk(self.L.dhts_bam_hist_open(self.h, C.byref(p), bed_ctx.h if bed_ctx is not None else None))
+
+    def bam_depth_hist_accumulate(self, b):
+        """b: the batch next_batch returned last on this context"""
+        self._chk(self.L.dhts_bam_hist_accumulate(self.h, C.byref(b)))
+
+    def bam_depth_hist_scan(self, max_blocks=0):
+        """the scan to the end of the stream; the status it ended on (1, or the negative status of a stream that ended on an error)"""
+        return self._accum_scan("hist", max_blocks, self.bam_depth_hist_stats)
+
+    def bam_depth_hist_stats(self):
+        return self._accum_stats("hist", DepthHistStats)
+
+    def bam_depth_hist_next(self, max_rows=0, columns=None):
+        """the next page of the result: ({"n_rows", "tid": int32, "start": int64 (0-based), "end": int64 (exclusive), "depth": int32, "n_positions",
+        "n_at_least", "length": int64 arrays; None for a column that `columns` (names of DEPTH_HIST_COLUMNS; None: all) leaves out -- the batch
+        has a null pointer there}, status)"""
+        mask = sum(1 << DEPTH_HIST_COLUMNS.index(k) for k in set(columns)) if columns is not None else 127
+        b = BedBatch()
+        self._chk(self.L.dhts_bam_hist_next(self.h, max_rows, mask, C.byref(b)))
+        return self._fixed_cols("hist", b, mask, DEPTH_HIST_COLUMNS, DEPTH_HIST_DTYPES)
 
     # ---- bam_bedcov ----
     def bam_bedcov_open(self, bed_ctx, min_mapq=0, require_flags=0, exclude_flags=0, include_flags=0, count_deletions=True, count_ref_skips=True):
@@ -2227,6 +2290,36 @@ def bam_bedgraph(src, region=None, index=None, bed=None, max_blocks=0, max_rows=
         out["pages"] = [p["n_rows"] for p in parts]
         out["contigs"] = [n.encode() if isinstance(n, str) else bytes(n) for n in hdr["ref_names"]]
         out["stats"] = {k: v for k, v in ctx.bam_bedgraph_stats().items() if k != "status"}
+        out["status"] = status
+        return out
+    finally:
+        if bctx is not None:
+            bctx.close()
+        ctx.close()
+
+
+def bam_depth_hist(src, region=None, index=None, bed=None, max_blocks=0, max_rows=0, columns=None, device=0, min_read_len=0, min_mapq=0, min_baseq=0,
+                   include_flags=0, require_flags=0, exclude_flags=0x704, include_deletions=0, depth_cap=1000, per="row"):
+    """bam_depth_hist(path, depth_cap :=, per :=, bed_path :=, region :=, index_path :=, min_read_len :=, min_mapq :=, min_baseq :=,
+    include_deletions :=, include_flags :=, require_flags :=, exclude_flags :=): the positions of every group of target rows on every depth,
+    binned and paged on the device (the contract: include/duckhts_amd.h) and concatenated here.  {"n_rows", "tid": int32 (the contig's id),
+    "start": int64 (0-based), "end": int64 (exclusive), "depth": int32 (the bin: min(depth, depth_cap)), "n_positions", "n_at_least", "length":
+    int64 arrays -- None for a column that `columns` leaves out --, "pages": the rows of every page, "contigs": the names by id, "stats": the
+    step counters, the target rows, the groups, the skipped BED rows, the bytes of the two tables and the result's rows, "status": how the
+    stream ended}.  per: 'row' or 'contig'; bed: a path or the file's bytes; index: BAI / CSI bytes narrowing the scan of a region query;
+    max_rows: rows per page."""
+    (ctx, hdr), bctx = _bam_ctx(src, device, region, index), None
+    try:
+        if bed is not None:
+            bctx = _bed_ctx(device, bed)
+        ctx.bam_depth_hist_open(bctx, min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, include_deletions, depth_cap, per)
+        status = ctx.bam_depth_hist_scan(max_blocks)
+        parts = _drain(lambda: ctx.bam_depth_hist_next(max_rows, columns))
+        out = {k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts]) for k in DEPTH_HIST_COLUMNS}
+        out["n_rows"] = sum(p["n_rows"] for p in parts)
+        out["pages"] = [p["n_rows"] for p in parts]
+        out["contigs"] = [n.encode() if isinstance(n, str) else bytes(n) for n in hdr["ref_names"]]
+        out["stats"] = {k: v for k, v in ctx.bam_depth_hist_stats().items() if k != "status"}
         out["status"] = status
         return out
     finally:

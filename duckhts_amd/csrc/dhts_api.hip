@@ -22,6 +22,7 @@
 #include "bam_depth.hip"
 #include "bam_pileup.hip"
 #include "bam_bedgraph.hip"
+#include "bam_depth_hist.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -205,7 +206,7 @@ struct NucState {
     DevBuf ents, names, table, cum, in_tid, in_start, in_end, tmp, keep, rank, src, rows, err, npieces, piece_off, counts;
     DevBuf name_len, name_off, name_bytes, name_valid, seq_len, seq_off32, seq_off64, seq_valid, ones, fixed[NUC_N_COLS];
 };
-// What the states of the six bam_* count functions start with (dhts_bam_accum.inc works on it): whether the function is open, the contigs of
+// What the states of the seven bam_* count functions start with (dhts_bam_accum.inc works on it): whether the function is open, the contigs of
 // the header, the status the scan's stream ended on, the step counters on the device and the columns of the last result batch
 struct AccumBase { bool open = false; int32_t n_ref = 0, status = 0; std::vector<dhts_col> out; DevBuf steps; };
 // bam_bin_counts (bam_bins.hip, dhts_bam_bins.inc): the parameters, the table of counters (two 64-bit words per bin) with the bins in front of
@@ -266,6 +267,16 @@ struct BedgraphState : AccumBase, DepLayout, DepPager {
     uint64_t n_bed_skipped = 0, n_runs = 0;
     DevBuf touched, row_tid, step, rlen, k0, k1, tsum, part, rowres, tnext, out_tid, out_start, out_end, out_depth;
 };
+// bam_depth_hist (bam_depth_hist.hip, dhts_bam_depth_hist.inc): the parameters, the layout, the group of every sorted row and the groups' contig,
+// start, end and length, the histogram table (hist: depth_cap + 1 64-bit words per group), of a result the depth in front of every tile (tsum)
+// and the result index in front of every group (gcnt; goff on the host), the result index the next page starts at, and the page's columns
+struct HistState : AccumBase, DepLayout {
+    bool res_ready = false; dhts_depth_hist_params P;
+    uint64_t n_bed_skipped = 0, n_groups = 0, hist_bytes = 0, n_result_rows = 0, o_next = 0;
+    std::vector<uint64_t> goff;
+    DevBuf touched, row_group, step, rlen, k0, k1, tsum, part, hist, gcnt, g_tid, g_beg, g_end, g_len, scratch;
+    DevBuf out_tid, out_start, out_end, out_depth, out_n, out_at_least, out_len;
+};
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
 struct UdfState {
@@ -315,6 +326,7 @@ struct dhts_ctx {
     DepthState dpt;
     PileupState pil;
     BedgraphState bdg;
+    HistState dhi;
     UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
@@ -625,6 +637,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_depth.inc"
 #include "dhts_bam_pileup.inc"
 #include "dhts_bam_bedgraph.inc"
+#include "dhts_bam_depth_hist.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

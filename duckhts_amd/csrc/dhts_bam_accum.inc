@@ -1,5 +1,5 @@
 // dhts_bam_accum.inc -- part of dhts_api.hip (included there in front of dhts_bam_bins.inc, inside its extern "C" block; not a translation unit
-// of its own): the host scaffold of the six bam_* count functions (bam_bin_counts, bam_bedcov, bam_coverage, bam_depth, bam_pileup, bam_bedgraph).  It owns
+// of its own): the host scaffold of the seven bam_* count functions (bam_bin_counts, bam_bedcov, bam_coverage, bam_depth, bam_pileup, bam_bedgraph, bam_depth_hist).  It owns
 // what carries none of the work and was the same in all of them: the checks in front of an accumulate, the scan loop, the read-out of the step
 // counters, the target rows and their layout in the table (dep_layout), the arguments of the depth kernels, the windows and tiles of a result
 // page, the reset of a result batch's columns, and the read-back of dhts_col columns.  A function keeps its own extern "C" entry points, its
@@ -95,7 +95,7 @@ static int bed_rows_read(dhts_ctx *c, dhts_ctx *b, uint64_t max_rows, std::vecto
     return 0;
 }
 
-// ---- the layout bam_coverage, bam_depth, bam_pileup and bam_bedgraph share ------------------------------------------------------------------------------
+// ---- the layout bam_coverage, bam_depth, bam_pileup, bam_bedgraph and bam_depth_hist share ------------------------------------------------------------------------------
 #define COVERAGE_MAX_TABLE_BYTES (16ull << 30)
 static uint64_t g_coverage_max_table_bytes = COVERAGE_MAX_TABLE_BYTES;
 // tests: the most bytes the table may take (0: the contract's 16 GiB)
@@ -114,7 +114,7 @@ static void dep_target_rows(const dhts_ctx *c, DepLayout &L, std::vector<size_t>
     } else for (size_t t = 0; t < c->ref_len.size(); t++) { L.o_tid.push_back((int32_t)t); L.o_beg.push_back(0); L.o_end.push_back((int64_t)c->ref_len[t]); }
 }
 
-// the target rows of a BED context b (bam_depth, bam_bedgraph): the union of its rows -- per contig in header order, sorted by start, rows that
+// the target rows of a BED context b (bam_depth, bam_bedgraph, bam_depth_hist): the union of its rows -- per contig in header order, sorted by start, rows that
 // overlap or touch merged, clipped to the contig, empty ones dropped.  n_skipped: the rows that name a contig the header lacks
 static int dep_bed_target_rows(dhts_ctx *c, dhts_ctx *b, DepLayout &L, uint64_t &n_skipped) {
     L.o_tid.clear(); L.o_beg.clear(); L.o_end.clear(); L.o_k.clear();
@@ -193,8 +193,8 @@ static int dep_layout(dhts_ctx *c, DepLayout &S, const char *fn, const std::vect
 
 extern "C++" {
 // the per-batch scratch and the arguments of the depth kernels (bam_depth_classify* and the add kernels of bam_coverage, bam_depth and
-// bam_pileup; bam_bedgraph launches bam_depth's) from the batch, the scan's stream, the layout and the function's filter; S: CoverageState, DepthState,
-// PileupState or BedgraphState
+// bam_pileup; bam_bedgraph and bam_depth_hist launch bam_depth's) from the batch, the scan's stream, the layout and the function's filter; S: CoverageState, DepthState,
+// PileupState, BedgraphState or HistState
 template <typename State> static int dep_args(dhts_ctx *c, State &S, const dhts_bam_batch *b, DepArgs &a) {
     const int64_t n = b->n_rows;
     ENSURE(c, S.step, (size_t)n + 64); ENSURE(c, S.rlen, (size_t)n * 8 + 64); ENSURE(c, S.k0, (size_t)n * 4 + 64); ENSURE(c, S.k1, (size_t)n * 4 + 64);
@@ -208,7 +208,7 @@ template <typename State> static int dep_args(dhts_ctx *c, State &S, const dhts_
     return 0;
 }
 
-// the seven counters dhts_coverage_stats, dhts_depth_stats, dhts_pileup_stats and dhts_bedgraph_stats share, from the DEP_N_STEPS step counters
+// the seven counters dhts_coverage_stats, dhts_depth_stats, dhts_pileup_stats, dhts_bedgraph_stats and dhts_depth_hist_stats share, from the DEP_N_STEPS step counters
 template <typename Stats> static void dep_stats_common(Stats *out, const uint64_t *s) {
     out->n_flag_filtered = s[DEP_STEP_FLAG]; out->n_unplaced = s[DEP_STEP_UNPLACED]; out->n_short = s[DEP_STEP_SHORT]; out->n_low_mapq = s[DEP_STEP_MAPQ];
     out->n_outside = s[DEP_STEP_OUTSIDE]; out->n_counted = s[DEP_STEP_COUNTED];

@@ -670,8 +670,8 @@ int dhts_bam_bedcov_batch_fetch(dhts_ctx *bam, const dhts_bedcov_batch *b, void 
  *     1,024 slots); beyond the cap (16 GiB; a human genome needs 12.4 GB) open fails with an error that states the bytes needed and the cap.
  *     A batch with status < 0 has its rows counted and the result carries that status.  A shard or a block range other than the whole file
  *     is refused.
- *   Not in this contract: bam_list (several files), reference / CRAM, the depth histogram, and max_depth (htslib's pileup cap depends on the
- *     order reads arrive in: it has no order-free definition).
+ *   Not in this contract: bam_list (several files), reference / CRAM and max_depth (htslib's pileup cap depends on the order reads arrive in:
+ *     it has no order-free definition).  The depth histogram is bam_depth_hist's (below).
  *   Method: a 32-bit difference table, two atomics per maximal run of counted bases; QUAL is read in aligned 16-byte pieces by eight lanes
  *     per read; the result is a scan of the table reduced per tile and summed per row (csrc/bam_coverage.hip).
  * Every call on a context in the wrong state fails with a dhts_error that names what is missing.  The kernels are timed as DHTS_K_BCF_CHECK. */
@@ -904,7 +904,8 @@ int dhts_bam_pileup_batch_fetch(dhts_ctx *bam, const dhts_pileup_batch *b, void 
  *     This ABI takes them as given; the table function and the Python function default exclude_flags to 0x704 and the rest to 0.
  *   Limits: bam_depth's -- 32-bit depth, the table cap and its error (dhts_debug_coverage_max_table_bytes applies here as well), a shard or
  *     block range refused, a stream that ends on an error has its rows counted and its status carried.
- *   Not in this contract: a mean depth per class run, the depth histogram, suppress_overlaps, several input files, reference / CRAM, max_depth.
+ *   Not in this contract: a mean depth per class run, suppress_overlaps, several input files, reference / CRAM, max_depth.  The depth
+ *     histogram is bam_depth_hist's (below).
  *   Method: bam_depth's add pass; per tile the emitted boundaries and its first boundary of any class, a suffix minimum in two levels for the
  *     next boundary behind every tile and a carry in two levels for the result index in front of it; a page is a window of result indices,
  *     emitted by the tiles that hold it, and a run that leaves its tile ends where the suffix minimum says, clipped to its row
@@ -956,6 +957,93 @@ int dhts_bam_bedgraph_next(dhts_ctx *bam, int64_t max_rows, uint32_t colmask, dh
  * each rounded up to 8 bytes */
 uint64_t dhts_bam_bedgraph_batch_host_bytes(const dhts_bedgraph_batch *b);
 int dhts_bam_bedgraph_batch_fetch(dhts_ctx *bam, const dhts_bedgraph_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
+/* ---- bam_depth_hist ---------------------------------------------------------------------------
+ * Per group of target rows and per depth: the number of positions on that depth -- mosdepth's *.dist.txt, the COV section of `samtools stats`,
+ * "what fraction of the target is covered at >= 20x" -- binned on the device out of the depth table bam_depth's add pass fills in HBM.  The
+ * per-base result never leaves the device; the answer is a few thousand rows.  The reference has no counterpart, so this is the specification.
+ *   Input, the six steps with their 64-bit counters, the read interval, the effective CIGAR, the counted bases (include_deletions: every
+ *     reference position of a D operation inside a row counts; N and P never count) and the target rows -- one per @SQ, one per region in the
+ *     order given, or the merged intervals of a BED (n_bed_skipped; a row's span is padded to 1,024 slots): exactly bam_depth's.  A BED
+ *     together with regions is refused by name; regions that overlap are refused.
+ *   Groups: per = 0 ('row'): a group is one target row, in the order answered.  per = 1 ('contig'): a group is all non-empty target rows of one
+ *     contig, with the contigs in header order; a contig without a non-empty target row has no group.  A target row that is empty after
+ *     clipping contributes nothing under either value.  Any other value: "bam_depth_hist: per must be 'row' or 'contig'".
+ *   Bins: bin(d) = min(d, depth_cap), so the last bin holds every position of depth >= depth_cap (`samtools stats`' [1000<]).  depth_cap is an
+ *     integer in 1 .. 1,048,575; otherwise "bam_depth_hist: depth_cap must be between 1 and 1048575".
+ *   The identity that defines correctness: for every group g and every d in 0 .. depth_cap, n_positions(g, d) is the number of positions p in
+ *     g's rows with bin(depth(p)) == d, where depth(p) is what bam_depth with all_positions = 2 answers for p on the same input and parameters.
+ *     Padding slots of a row's span never count.
+ *   Result: one row per group and per bin with n_positions > 0, ordered by group and then by depth ascending: chrom (here: the contig's id,
+ *     int32), start (0-based, int64; with 'contig' the least start of the group's rows), end (exclusive, int64; with 'contig' the greatest
+ *     end), depth (int32, the bin), n_positions (int64), n_at_least (int64: the sum of n_positions over the bins >= this one in the group) and
+ *     length (int64: the positions of the group, the sum of its rows' end - start).  No column is ever NULL.  An untouched contig of length L
+ *     gives the single row (chrom, 0, L, 0, L, L, L).  The table function adds fraction_at_least = n_at_least / length from the two integers.
+ *   The histogram table: groups x (depth_cap + 1) 64-bit words, zeroed at open, at most 1 GiB (dhts_debug_hist_max_table_bytes sets the cap
+ *     for tests).  Past the cap open fails with "bam_depth_hist: the histogram needs N bytes (8 per bin of every group); at most C are
+ *     supported (per := 'contig' or a smaller depth_cap)": 200,000 exome targets at the default cap exceed it per row and fit per contig.
+ *   Reaccumulate: an accumulate after a page was taken starts the result over.  The depth table and the counters stay; the histogram is
+ *     zeroed and made again from the depth table, of which it is a pure function.
+ *   Parameters: min_read_len >= 0; min_mapq, min_baseq 0..255; the three masks 0..65535; include_deletions 0..1; depth_cap; per 0..1.  This
+ *     ABI takes them as given; the table function and the Python function default exclude_flags to 0x704, depth_cap to 1000, per to 'row'.
+ *   Limits: bam_depth's -- 32-bit depth, the 16 GiB cap of the depth table and its error (dhts_debug_coverage_max_table_bytes applies here as
+ *     well), a shard or block range refused, a stream that ends on an error has its rows counted and its status carried.
+ *   Not in this contract: a 'total' group (SQL sums the contigs), dense output of empty bins, mosdepth --thresholds per BED row,
+ *     suppress_overlaps, several input files, reference / CRAM, max_depth.
+ *   Method: bam_depth's add pass; tile sums and their carry; one read of the table by workgroups that own a span of tiles and count into an
+ *     LDS histogram of 4,096 bins, flushed into the table where the group changes; per group the non-empty bins and their carry; a page is a
+ *     window of result indices, emitted by the groups that hold it from the top bin down behind a suffix sum (csrc/bam_depth_hist.hip,
+ *     DESIGN.md 4o).
+ * The entries are dhts_bam_hist_*: the names that begin dhts_bam_depth_ are bam_depth's own.
+ * All errors are prefixed "bam_depth_hist:".  Every call on a context in the wrong state fails with a dhts_error that names what is missing. */
+enum { DHTS_DEPTH_HIST_CHROM = 0, DHTS_DEPTH_HIST_START, DHTS_DEPTH_HIST_END, DHTS_DEPTH_HIST_DEPTH, DHTS_DEPTH_HIST_N_POSITIONS, DHTS_DEPTH_HIST_N_AT_LEAST,
+       DHTS_DEPTH_HIST_LENGTH, DHTS_DEPTH_HIST_COL_COUNT };
+typedef struct {
+    int64_t min_read_len;    /* >= 0                                                                          */
+    int32_t min_mapq;        /* 0..255                                                                        */
+    int32_t min_baseq;       /* 0..255                                                                        */
+    int32_t require_flags, exclude_flags, include_flags;   /* 0..65535                                        */
+    int32_t include_deletions;                             /* 0 or 1                                          */
+    int32_t depth_cap;                                     /* 1..1048575: the last bin                        */
+    int32_t per;                                           /* 0 = 'row', 1 = 'contig'                         */
+    int32_t reserved[2];
+} dhts_depth_hist_params;
+typedef struct {
+    uint64_t n_rows, n_flag_filtered, n_unplaced, n_short, n_low_mapq, n_outside, n_counted;
+    uint64_t n_target_rows;  /* target rows (regions, @SQ lines or merged BED intervals)                       */
+    uint64_t n_groups;       /* groups: the non-empty target rows, or the contigs that have one                */
+    uint64_t n_bed_skipped;  /* BED rows that name a contig the header lacks                                   */
+    uint64_t table_bytes;    /* bytes of the depth table                                                       */
+    uint64_t hist_bytes;     /* bytes of the histogram table                                                   */
+    uint64_t n_result_rows;  /* rows of the whole result: valid once a result was taken (dhts_bam_hist_next), 0 before */
+    int32_t status;          /* as in dhts_coverage_stats                                                      */
+    int32_t reserved;
+} dhts_depth_hist_stats;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows follow, 1 = the last page                                                                    */
+    int32_t n_cols;          /* DHTS_DEPTH_HIST_COL_COUNT, in that order                                                                   */
+    const dhts_col *cols;    /* host array of descriptors, DEVICE pointers inside: fixed = int32 (chrom, depth) or int64 (the rest) per row,
+                                a null pointer for a column colmask left out; no row is NULL and valid stays a null pointer                 */
+} dhts_depth_hist_batch;
+/* after dhts_bam_open and the optional dhts_bam_set_regions / dhts_bam_load_index.  bed: NULL, or a second context on the same device prepared
+ * as for read_bed (dhts_bed_open); its projection belongs to bam_depth_hist from here on.  The target rows, the groups, the two tables and the
+ * counters, zeroed.  A second open starts a new count. */
+int dhts_bam_hist_open(dhts_ctx *bam, const dhts_depth_hist_params *params, dhts_ctx *bed);
+/* the batch dhts_bam_next_batch returned LAST on this context, as in dhts_bam_depth_accumulate.  Starts a result over: the depth table and the
+ * counters stay intact, the next dhts_bam_hist_next makes the histogram anew and returns the first page of the new result. */
+int dhts_bam_hist_accumulate(dhts_ctx *bam, const dhts_bam_batch *batch);
+/* dhts_bam_next_batch + accumulate to the end of the stream; returns as dhts_bam_coverage_scan does */
+int dhts_bam_hist_scan(dhts_ctx *bam, int64_t max_blocks);
+int dhts_bam_hist_stats(dhts_ctx *bam, dhts_depth_hist_stats *out);
+/* the next <= max_rows rows of the result (0 = 1,048,576 rows: 48 MiB with all seven columns).  colmask: bit DHTS_DEPTH_HIST_* set = the
+ * column is written and fetched.  The first call after open or accumulate reads the depth table, which stays as it is, into the histogram.
+ * The page's columns stay valid until the next call on the context. */
+int dhts_bam_hist_next(dhts_ctx *bam, int64_t max_rows, uint32_t colmask, dhts_depth_hist_batch *out);
+/* read-back: out_cols[b->n_cols] = b->cols with HOST pointers into dst (null where the batch has none); the columns follow each other,
+ * each rounded up to 8 bytes */
+uint64_t dhts_bam_hist_batch_host_bytes(const dhts_depth_hist_batch *b);
+int dhts_bam_hist_batch_fetch(dhts_ctx *bam, const dhts_depth_hist_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
 /* ---- read_tabix / read_gtf / read_gff ---------------------------------------------------------
  * src/tabix_reader.c.  The context is prepared as for read_bed (dhts_open_path[_segments] + dhts_bgzf_index): BGZF, plain gzip and

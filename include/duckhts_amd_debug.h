@@ -31,6 +31,12 @@ void dhts_debug_bedcov_max_rows(uint64_t n);
 /* tests: the most bytes the depth table of dhts_bam_coverage_open or dhts_bam_depth_open, or the count table of dhts_bam_pileup_open, may take,
  * for the whole process (0: the contract's 16 GiB) */
 void dhts_debug_coverage_max_table_bytes(uint64_t n);
+/* tests: the most bytes the histogram table of dhts_bam_depth_hist_open may take, for the whole process (0: the contract's 1 GiB) */
+void dhts_debug_hist_max_table_bytes(uint64_t n);
+/* tests, tools/bench_depth_hist.py: the device time in ms per launch of one pass over the depth table of the context's open bam_depth_hist, `reps`
+ * launches between two events: which 0 = dep_tile_reduce (bam_coverage's read of the table), 1 = dhi_hist (the histogram pass).  The next
+ * dhts_bam_depth_hist_next makes its result anew.  < 0 with dhts_error set when a call failed. */
+double dhts_debug_hist_pass_ms(dhts_ctx *, int which, int reps);
 /* tests, tools/bench_pileup.py: the form of bam_pileup's add kernel on this context from the next accumulate on: 0 the default (the window form), 1 direct (one
  * atomic add per counted base into the table), 2 window (the workgroup counts 512 positions of one row in LDS and adds the non-zero words to
  * the table when the window moves).  Any other value fails with a dhts_error. */

@@ -662,6 +662,7 @@ class Context:
     def aux_table(self, b):
         """AUXILIARY_TAGS of one batch: typed device entries -> keys / rendered value text (bam_aux_to_string, src/bam_reader.c:140-183;
         the %g / %lld text is host-side formatting) as two LIST(VARCHAR) columns in the canonical layout"""
+        import math
         import struct as st_
         n = int(b.n_rows)
         am = C.cast(b.aux_map, C.POINTER(AuxMap)).contents
@@ -674,6 +675,7 @@ class Context:
         po = self.d2h(am.pay_off, ne + 1, np.uint32) if n else np.zeros(1, np.uint32)
         pay = self.d2h(am.payload, int(am.payload_bytes), np.uint8).tobytes()
         keys, vals = [], []
+        g = lambda x: (b"-nan" if math.copysign(1.0, x) < 0 else b"nan") if x != x else b"%g" % x      # printf prints a NaN with its sign, Python's %g without
         for i in range(ne):
             kb = bytes([int(key[i]) & 0xff, int(key[i]) >> 8]).split(b"\0")[0]
             p = pay[int(po[i]):int(po[i + 1])]
@@ -681,13 +683,13 @@ class Context:
             if k == 0:
                 v = b"%d" % st_.unpack("<q", p)[0]
             elif k == 1:
-                v = (b"%g" % st_.unpack("<d", p)[0])
+                v = g(st_.unpack("<d", p)[0])
             elif k in (2, 3):
                 v = p
             elif k == 4:
                 v = bytes([int(sub[i])]) + b"".join(b",%d" % x for x in st_.unpack("<%dq" % (len(p) // 8), p))
             elif k == 5:
-                v = bytes([int(sub[i])]) + b"".join(b",%g" % x for x in st_.unpack("<%dd" % (len(p) // 8), p))
+                v = bytes([int(sub[i])]) + b"".join(b"," + g(x) for x in st_.unpack("<%dd" % (len(p) // 8), p))
             else:
                 v = b""
             keys.append(kb)

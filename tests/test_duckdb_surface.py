@@ -333,7 +333,8 @@ def test_read_bcf_region_through_the_surface(tmp_path):
 def test_read_bam_standard_tags_through_the_surface(tmp_path):
     """read_bam(standard_tags := true): 13 + 56 columns (bam_reader.c:527-537), typed per bam_std_tag_type; duckhts.test:179-185 values"""
     import tag_cases
-    for data in (tag_cases.aux_tags_sam_equivalent(), tag_cases.type_matrix(), tag_cases.fuzz(n=5000)):
+    import tag_corpus
+    for data in (tag_cases.aux_tags_sam_equivalent(), tag_cases.type_matrix(), tag_cases.fuzz(n=5000)) + tag_corpus.files():      # (the hostile corpus: both block sizes)
         fn = os.path.join(str(tmp_path), "t.bam")
         open(fn, "wb").write(data)
         exp = orc.bam_read_std_tags(data)
@@ -374,7 +375,8 @@ MAP = 26
 def test_read_bam_auxiliary_tags_through_the_surface(tmp_path):
     """duckhts.test:179-185: RG = x1, NM = 2, map_extract(AUXILIARY_TAGS, 'XZ') = [foo] with standard_tags + auxiliary_tags"""
     import tag_cases
-    for data in (tag_cases.aux_tags_sam_equivalent(), tag_cases.type_matrix(), tag_cases.fuzz(n=3000)):
+    import tag_corpus
+    for data in (tag_cases.aux_tags_sam_equivalent(), tag_cases.type_matrix(), tag_cases.fuzz(n=3000)) + tag_corpus.files():      # (the only way through the snprintf renderer)
         fn = os.path.join(str(tmp_path), "a.bam")
         open(fn, "wb").write(data)
         for std in (True, False):

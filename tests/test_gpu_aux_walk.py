@@ -15,6 +15,7 @@ import pytest
 import bamwriter as BW
 import duckhts_amd
 import orc
+from tag_corpus import FIXED, barray, cg_record, cg_tag, field
 
 pytestmark = pytest.mark.gpu
 
@@ -22,23 +23,6 @@ TILE = 8192
 COLS = duckhts_amd.BAM_COLUMNS
 TEXT = "@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:chr1\tLN:100000000\n@RG\tID:grp1\tSM:s1\n@RG\tID:grp2\tSM:s2\n@RG\tID:\tSM:s3\n"
 RG = b"RGZgrp1\0"
-FIXED = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4, "d": 8}
-
-
-def field(type_byte, tag=b"XT"):
-    """a field of that type with a payload of the right size where the type has one (4 bytes otherwise)"""
-    t = bytes([type_byte]); ch = chr(type_byte)
-    if ch in FIXED:
-        return tag + t + bytes(range(1, 1 + FIXED[ch]))
-    if ch in "ZH":
-        return tag + t + b"ab\0"
-    if ch == "B":
-        return tag + t + b"c" + struct.pack("<I", 2) + b"\x01\x02"
-    return tag + t + b"\x01\x02\x03\x04"
-
-
-def barray(sub, n):
-    return b"XBB" + sub.encode() + struct.pack("<I", n) + bytes((7 * k + 1) & 0x7f for k in range(FIXED[sub] * n))
 
 
 def aux_cases():
@@ -76,19 +60,6 @@ def plain(i, aux, far):
     rnd = random.Random(i)
     return BW.record(qname="r%d" % i, flag=0, tid=0, pos=i, mapq=20, cigar="%dM" % n, seq="".join(rnd.choice("ACGT") for _ in range(n)),
                      qual=bytes(rnd.randrange(1, 60) for _ in range(n)), raw_aux=aux)
-
-
-def cg_record(i, aux, far, n_real=3):
-    """a record whose CIGAR is the placeholder <l_seq>S<ref>N: the CG walk runs over its aux data"""
-    n = 900 if far else 40
-    rnd = random.Random(i)
-    return BW.record(qname="c%d" % i, flag=0, tid=0, pos=i, mapq=20, raw_cigar=[(n << 4) | 4, (n << 4) | 3], seq="".join(rnd.choice("ACGT") for _ in range(n)),
-                     qual=bytes(rnd.randrange(1, 60) for _ in range(n)), raw_aux=aux)
-
-
-def cg_tag(n):
-    ops = [(10 << 4) | 0] * (n // 10) + ([((n % 10) << 4) | 0] if n % 10 else [])
-    return b"CGBI" + struct.pack("<I", len(ops)) + b"".join(struct.pack("<I", o) for o in ops)
 
 
 def layout(records, far):

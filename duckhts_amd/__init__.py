@@ -376,6 +376,7 @@ def lib():
             f["batch_host_bytes"].argtypes = [C.POINTER(BedBatch)]
             f["batch_fetch"].argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
         L.dhts_debug_pileup_add_form.argtypes = [C.c_void_p, C.c_int]
+        L.dhts_debug_carry.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64]
         L.dhts_debug_hist_max_table_bytes.argtypes = [C.c_uint64]
         L.dhts_debug_hist_max_table_bytes.restype = None
         L.dhts_debug_hist_pass_ms.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -588,6 +589,18 @@ class Context:
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
         self._chk(f(self.h, cnt.ctypes.data, cnt.shape[1], maxbits, cnt.shape[0], lens.ctypes.data, codes.ctypes.data))
         return lens, codes
+
+    def debug_carry(self, kind, v, seed=0):
+        """the carry in two levels alone (dhts_debug_carry) on a copy of v: uint32[n] (kind 0), uint64[n] (1, 2) or uint64[n, 4] (3).  Returns
+        the scanned array; kinds 0, 1 and 3 return n + 1 elements, the total last.  The element behind the last goes to the device as one
+        that would change every answer it took part in (0 for the minimum, all ones for the sums)."""
+        a = np.ascontiguousarray(v, dtype=np.uint32 if kind == 0 else np.uint64)
+        n = a.shape[0]
+        out = np.empty((n + 1,) + a.shape[1:], a.dtype)
+        out[:n] = a
+        out[n] = 0 if kind == 2 else np.iinfo(a.dtype).max
+        self._chk(self.L.dhts_debug_carry(self.h, kind, out.ctypes.data, n, seed))
+        return out[:n] if kind == 2 else out
 
     def header(self):
         h = BamHeader()

@@ -8,11 +8,12 @@
 //                first breakpoint > p and 1 to RE at the first breakpoint >= q.  All sums wrap in 64 bits.
 //   classify     one lane per row: the step the row falls out at, the reference length and the number of depth segments of its CIGAR
 //   add          rounds over the segments of a wave's rows; runs of neighbouring lanes with one counter index become one atomic per word
-//   scan         inclusive 64-bit prefix sums of the four words over the whole concatenation: tile sums, a scan of the sums, add-back
+//   scan         64-bit prefix sums of the four words over the whole concatenation: a copy of cnt, scanned in place by dev_scan.hip's carry_*
 //   emit         F[k] = X[k] * sum C[k] - sum S[k]; bases_covered = F[ke] - F[ks], read_count = sum RS[ke] - sum RE[ks]
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dev_scan.hip"
 
 enum { COV_STEP_FLAG = 0, COV_STEP_UNPLACED, COV_STEP_MAPQ, COV_STEP_COUNTED, COV_N_STEPS, COV_STEP_NONE = 7 };
 enum { COV_C = 0, COV_S, COV_RS, COV_RE, COV_WORDS };
@@ -153,63 +154,15 @@ __global__ void __launch_bounds__(256) bam_cov_add(CovArgs a, unsigned long long
     if (threadIdx.x < COV_N_STEPS && block_steps[threadIdx.x]) atomicAdd(&steps[threadIdx.x], block_steps[threadIdx.x]);
 }
 
-// ---- inclusive 64-bit scan of n elements of COV_WORDS words each: out[e][k] = sum of in[0 .. e][k] ---------------------------------------
-// A tile is 1,024 elements, four per thread.  cov_scan_reduce leaves every tile's sums, cov_scan_partials turns them into the sums in front
-// of every tile (one workgroup, 256 tiles at a time), cov_scan_apply scans inside the tile and adds them back.
-#define COV_TILE 1024u
+// ---- the prefix sums of the counters: an element is the COV_WORDS words of a breakpoint index, added word by word ------------------------
+// The host copies cnt into sums and scans sums in place with the carry in two levels (dev_scan.hip, four elements per thread, so a chunk is
+// 1,024 elements): sums[i] = the sum of cnt[0 .. i), so the inclusive sums of index i lie in sums[i + 1].  cnt stays: a later batch adds to it.
 struct CovVec { unsigned long long w[COV_WORDS]; };
-__device__ __forceinline__ void cov_block_scan(CovVec &v, unsigned long long (*sh)[256]) {      // inclusive over the 256 threads of the workgroup
-    const uint32_t t = threadIdx.x;
+__device__ __forceinline__ CovVec operator+(const CovVec &a, const CovVec &b) {
+    CovVec r;
 #pragma unroll
-    for (int k = 0; k < COV_WORDS; k++) sh[k][t] = v.w[k];
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-        CovVec y;
-#pragma unroll
-        for (int k = 0; k < COV_WORDS; k++) y.w[k] = t >= d ? sh[k][t - d] : 0ull;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < COV_WORDS; k++) sh[k][t] += y.w[k];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < COV_WORDS; k++) v.w[k] = sh[k][t];
-    __syncthreads();
-}
-__global__ void __launch_bounds__(256) cov_scan_reduce(const unsigned long long *__restrict__ in, uint64_t n, unsigned long long *__restrict__ partial) {
-    __shared__ unsigned long long sh[COV_WORDS][256];
-    CovVec v = {{0, 0, 0, 0}};
-    const uint64_t e0 = (uint64_t)blockIdx.x * COV_TILE + threadIdx.x * 4u;
-    for (uint32_t q = 0; q < 4u; q++) if (e0 + q < n) for (int k = 0; k < COV_WORDS; k++) v.w[k] += in[(e0 + q) * COV_WORDS + k];
-    cov_block_scan(v, sh);
-    if (threadIdx.x == 255u) for (int k = 0; k < COV_WORDS; k++) partial[(uint64_t)blockIdx.x * COV_WORDS + k] = v.w[k];
-}
-__global__ void __launch_bounds__(256) cov_scan_partials(unsigned long long *__restrict__ partial, uint64_t ntiles) {
-    __shared__ unsigned long long sh[COV_WORDS][256];
-    CovVec carry = {{0, 0, 0, 0}};
-    for (uint64_t t0 = 0; t0 < ntiles; t0 += 256u) {
-        const uint64_t t = t0 + threadIdx.x;
-        CovVec own = {{0, 0, 0, 0}};
-        if (t < ntiles) for (int k = 0; k < COV_WORDS; k++) own.w[k] = partial[t * COV_WORDS + k];
-        CovVec v = own;
-        cov_block_scan(v, sh);
-        if (t < ntiles) for (int k = 0; k < COV_WORDS; k++) partial[t * COV_WORDS + k] = carry.w[k] + v.w[k] - own.w[k];
-        // (every thread reads the chunk's total out of the last thread's entry)
-        for (int k = 0; k < COV_WORDS; k++) sh[k][threadIdx.x] = v.w[k];
-        __syncthreads();
-        for (int k = 0; k < COV_WORDS; k++) carry.w[k] += sh[k][255];
-        __syncthreads();
-    }
-}
-__global__ void __launch_bounds__(256) cov_scan_apply(const unsigned long long *__restrict__ in, uint64_t n, const unsigned long long *__restrict__ partial, unsigned long long *__restrict__ out) {
-    __shared__ unsigned long long sh[COV_WORDS][256];
-    const uint64_t e0 = (uint64_t)blockIdx.x * COV_TILE + threadIdx.x * 4u;
-    CovVec el[4], tot = {{0, 0, 0, 0}};
-    for (uint32_t q = 0; q < 4u; q++) for (int k = 0; k < COV_WORDS; k++) { el[q].w[k] = e0 + q < n ? in[(e0 + q) * COV_WORDS + k] : 0ull; tot.w[k] += el[q].w[k]; el[q].w[k] = tot.w[k]; }
-    CovVec v = tot;
-    cov_block_scan(v, sh);
-    for (uint32_t q = 0; q < 4u; q++) if (e0 + q < n) for (int k = 0; k < COV_WORDS; k++)
-        out[(e0 + q) * COV_WORDS + k] = partial[(uint64_t)blockIdx.x * COV_WORDS + k] + (v.w[k] - tot.w[k]) + el[q].w[k];
+    for (int k = 0; k < COV_WORDS; k++) r.w[k] = a.w[k] + b.w[k];
+    return r;
 }
 
 // rows [row0, row0 + n) of the BED: ks / ke are the global breakpoint indices of the row's start and end, COV_NO_IDX for a row that answers 0
@@ -220,7 +173,7 @@ __global__ void __launch_bounds__(256) bam_cov_emit(const unsigned long long *__
     const uint32_t s = ks[row0 + r], e = ke[row0 + r];
     unsigned long long b = 0, c = 0;
     if (s != COV_NO_IDX && e != COV_NO_IDX) {
-        const unsigned long long *ps = sums + (uint64_t)COV_WORDS * s, *pe = sums + (uint64_t)COV_WORDS * e;
+        const unsigned long long *ps = sums + (uint64_t)COV_WORDS * (s + 1ull), *pe = sums + (uint64_t)COV_WORDS * (e + 1ull);     // (the inclusive sums)
         const unsigned long long fs = (unsigned long long)X[s] * ps[COV_C] - ps[COV_S], fe = (unsigned long long)X[e] * pe[COV_C] - pe[COV_S];
         b = fe - fs; c = pe[COV_RS] - ps[COV_RE];
     }

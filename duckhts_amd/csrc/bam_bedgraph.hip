@@ -8,7 +8,7 @@
 //                front of a tile is tcarry[tile] (dep_tile_sum + the 32-bit carry).  A boundary is emitted iff its class is > 0 or zero_runs is on.
 //   count        per tile the emitted boundaries (tcnt, which the 64-bit carry turns into the result index in front of every tile) and the
 //                global slot of its first boundary of any class (tfirst; `none` where it has no boundary)
-//   suffix       tfirst[t] becomes tnext[t], the least tfirst behind t, or `none`: the carry's two levels mirrored, with min for +.  It needs
+//   suffix       tfirst[t] becomes tnext[t], the least tfirst behind t, or `none`: dev_scan.hip's carry_* in reverse with ScanMin.  It needs
 //                no segmentation: a row's first slot is always a boundary, and the user clips to the end of its own row.
 //   emit         a window [o_a, o_b) of result indices and the contiguous tiles that hold it: a workgroup rescans its tile, compacts all
 //                boundaries into LDS and of the emitted ones their index among all and their class's depth.  A run ends at the next boundary of
@@ -34,7 +34,7 @@ __device__ __forceinline__ BdgLane bdg_lane(const int32_t *__restrict__ diff, ui
     const int4 v = *(const int4 *)(diff + tile * DEP_TILE + threadIdx.x * 4u);
     const uint32_t d[4] = {(uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w};
     const uint32_t tot = d[0] + d[1] + d[2] + d[3];
-    uint32_t run = carry + dep_block_scan(tot, sh) - tot, prev = bdg_class(c, run);
+    uint32_t run = carry + block_scan<uint32_t, ScanSum>(tot, sh) - tot, prev = bdg_class(c, run);
     const uint64_t p0 = tp + threadIdx.x * 4u;
     BdgLane r; r.bnd = 0; r.em = 0;
 #pragma unroll
@@ -75,66 +75,6 @@ __global__ void __launch_bounds__(256) bdg_tile_count(const int32_t *__restrict_
     }
 }
 
-// ---- the suffix minimum in two levels: dep_carry_* mirrored (element i of a chunk is visited as DEPC_CHUNK - 1 - i) ------------------------
-__device__ __forceinline__ unsigned long long bdg_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned long long bdg_block_scan_min(unsigned long long v, unsigned long long *sh) {          // inclusive over the 256 threads
-    const uint32_t t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-        const unsigned long long y = t >= d ? sh[t - d] : ~0ull;
-        __syncthreads();
-        sh[t] = bdg_min(sh[t], y);
-        __syncthreads();
-    }
-    const unsigned long long r = sh[t];
-    __syncthreads();
-    return r;
-}
-// part[b] = the minimum of chunk b of v[0 .. n)
-__global__ void __launch_bounds__(256) bdg_suffix_reduce(const unsigned long long *__restrict__ v, uint64_t n, unsigned long long *__restrict__ part) {
-    __shared__ unsigned long long sh[256];
-    const uint64_t b = (uint64_t)blockIdx.x * DEPC_CHUNK + threadIdx.x * DEPC_PER_THREAD;
-    unsigned long long m = ~0ull;
-#pragma unroll
-    for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) m = bdg_min(m, b + e < n ? v[b + e] : ~0ull);
-    const unsigned long long incl = bdg_block_scan_min(m, sh);
-    if (threadIdx.x == 255u) part[blockIdx.x] = incl;
-}
-// part[b] becomes the minimum of part(b .. np), `none` for the last: one workgroup, DEPC_CHUNK words a turn, from the end
-__global__ void __launch_bounds__(256) bdg_suffix_scan(unsigned long long *__restrict__ part, uint64_t np, unsigned long long none) {
-    __shared__ unsigned long long sh[256];
-    unsigned long long carry = none;
-    for (uint64_t r0 = 0; r0 < np; r0 += DEPC_CHUNK) {
-        const uint64_t r = r0 + threadIdx.x * DEPC_PER_THREAD;                                     // reversed index: element np - 1 - r
-        unsigned long long own[DEPC_PER_THREAD], m = ~0ull;
-#pragma unroll
-        for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) { own[e] = r + e < np ? part[np - 1u - (r + e)] : ~0ull; m = bdg_min(m, own[e]); }
-        const unsigned long long incl = bdg_block_scan_min(m, sh);
-        sh[threadIdx.x] = incl;
-        __syncthreads();
-        unsigned long long run = bdg_min(carry, threadIdx.x ? sh[threadIdx.x - 1u] : ~0ull);
-        carry = bdg_min(carry, sh[255]);
-        __syncthreads();
-#pragma unroll
-        for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) if (r + e < np) { part[np - 1u - (r + e)] = run; run = bdg_min(run, own[e]); }
-    }
-}
-// v[i] becomes the minimum of v(i .. n), `none` where nothing lies behind it
-__global__ void __launch_bounds__(256) bdg_suffix_apply(unsigned long long *__restrict__ v, uint64_t n, const unsigned long long *__restrict__ part) {
-    __shared__ unsigned long long sh[256];
-    const uint64_t last = (uint64_t)blockIdx.x * DEPC_CHUNK + (DEPC_CHUNK - 1u), r = threadIdx.x * DEPC_PER_THREAD;   // reversed index: element last - r
-    unsigned long long own[DEPC_PER_THREAD], m = ~0ull;
-#pragma unroll
-    for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) { own[e] = last - (r + e) < n ? v[last - (r + e)] : ~0ull; m = bdg_min(m, own[e]); }
-    const unsigned long long incl = bdg_block_scan_min(m, sh);
-    sh[threadIdx.x] = incl;
-    __syncthreads();
-    unsigned long long run = bdg_min(part[blockIdx.x], threadIdx.x ? sh[threadIdx.x - 1u] : ~0ull);
-#pragma unroll
-    for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) if (last - (r + e) < n) { v[last - (r + e)] = run; run = bdg_min(run, own[e]); }
-}
-
 // ---- emit --------------------------------------------------------------------------------------------------------------------------------------
 struct BdgEmitArgs {
     const int32_t *diff; const uint32_t *tcarry; const unsigned long long *toff, *tnext;          // the table; the depth, the result index and the next boundary behind every tile
@@ -154,9 +94,9 @@ __global__ void __launch_bounds__(256) bdg_emit(BdgEmitArgs a) {
     const uint64_t len = (uint64_t)(a.rend[k] - a.rbeg[k]), tp = tile * DEP_TILE - a.rbase[k];
     const BdgLane r = bdg_lane(a.diff, tile, a.tcarry[tile], tp, len, a.c, sh);
     const uint32_t nb = (uint32_t)__popc(r.bnd), ne = (uint32_t)__popc(r.em);
-    const uint32_t ib = dep_block_scan(nb, sh);
+    const uint32_t ib = block_scan<uint32_t, ScanSum>(nb, sh);
     if (threadIdx.x == 255u) lpos[DEP_TILE] = (uint16_t)ib;                                        // the tile's boundaries of any class (<= DEP_TILE)
-    uint32_t at_b = ib - nb, at_e = dep_block_scan(ne, sh) - ne;                                    // (ends in a barrier)
+    uint32_t at_b = ib - nb, at_e = block_scan<uint32_t, ScanSum>(ne, sh) - ne;                                    // (ends in a barrier)
 #pragma unroll
     for (uint32_t e = 0; e < 4u; e++) {
         if (!((r.bnd >> e) & 1u)) continue;

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bam_bedcov.hip"
+#include "dev_scan.hip"
 
 enum { DEP_STEP_FLAG = 0, DEP_STEP_UNPLACED, DEP_STEP_SHORT, DEP_STEP_MAPQ, DEP_STEP_OUTSIDE, DEP_STEP_COUNTED, DEP_N_STEPS, DEP_STEP_NONE = 15 };
 enum { DEP_W_READS = 0, DEP_W_MAPQ, DEP_W_BASEQ, DEP_W_SPARE };           // = COV_WORDS words per row
@@ -231,43 +232,13 @@ template <bool BQ> __global__ void __launch_bounds__(256) bam_depth_add(DepArgs 
 }
 
 // ---- the result: depth = the inclusive scan of diff; nothing of it is written back ------------------------------------------------------
-// (32-bit sums wrap; the depth in front of a tile and inside it is what the contract bounds by 32 bits)
-__device__ __forceinline__ uint32_t dep_block_scan(uint32_t v, uint32_t *sh) {                   // inclusive over the 256 threads
-    const uint32_t t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-        const uint32_t y = t >= d ? sh[t - d] : 0u;
-        __syncthreads();
-        sh[t] += y;
-        __syncthreads();
-    }
-    const uint32_t r = sh[t];
-    __syncthreads();
-    return r;
-}
+// (32-bit sums wrap; the depth in front of a tile and inside it is what the contract bounds by 32 bits.  The tile sums become the depth in
+// front of every tile by the carry in two levels, dev_scan.hip)
 __global__ void __launch_bounds__(256) dep_tile_sum(const int32_t *__restrict__ diff, uint32_t *__restrict__ tsum) {
     __shared__ uint32_t sh[256];
     const int4 v = *(const int4 *)(diff + (uint64_t)blockIdx.x * DEP_TILE + threadIdx.x * 4u);
-    const uint32_t tot = dep_block_scan((uint32_t)v.x + (uint32_t)v.y + (uint32_t)v.z + (uint32_t)v.w, sh);
+    const uint32_t tot = block_scan<uint32_t, ScanSum>((uint32_t)v.x + (uint32_t)v.y + (uint32_t)v.z + (uint32_t)v.w, sh);
     if (threadIdx.x == 255u) tsum[blockIdx.x] = tot;
-}
-// tsum[t] becomes the sum of the tiles in front of t: one workgroup, 4,096 tiles a turn (16 per thread)
-__global__ void __launch_bounds__(256) dep_tile_carry(uint32_t *__restrict__ tsum, uint64_t ntiles) {
-    __shared__ uint32_t sh[256];
-    uint32_t carry = 0;
-    for (uint64_t t0 = 0; t0 < ntiles; t0 += 4096u) {
-        const uint64_t b = t0 + threadIdx.x * 16u;
-        uint32_t own[16], tot = 0;
-        for (uint32_t e = 0; e < 16u; e++) { own[e] = b + e < ntiles ? tsum[b + e] : 0u; tot += own[e]; }
-        const uint32_t incl = dep_block_scan(tot, sh);
-        uint32_t run = carry + incl - tot;
-        for (uint32_t e = 0; e < 16u; e++) if (b + e < ntiles) { tsum[b + e] = run; run += own[e]; }
-        sh[threadIdx.x] = incl;
-        __syncthreads();
-        carry += sh[255];
-        __syncthreads();
-    }
 }
 // per tile: the positions of its row with depth >= min_depth, and the sum of their depths (a tile belongs to one row: the spans are padded)
 __global__ void __launch_bounds__(256) dep_tile_reduce(const int32_t *__restrict__ diff, const uint32_t *__restrict__ tcarry, const uint32_t *__restrict__ tile_row,
@@ -279,7 +250,7 @@ __global__ void __launch_bounds__(256) dep_tile_reduce(const int32_t *__restrict
     const int4 v = *(const int4 *)(diff + e0);
     const uint32_t d[4] = {(uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w};
     const uint32_t tot = d[0] + d[1] + d[2] + d[3];
-    uint32_t run = tcarry[blockIdx.x] + dep_block_scan(tot, sh) - tot;
+    uint32_t run = tcarry[blockIdx.x] + block_scan<uint32_t, ScanSum>(tot, sh) - tot;
     const uint32_t k = tile_row[blockIdx.x];
     const uint64_t len = (uint64_t)(rend[k] - rbeg[k]), p0 = e0 - rbase[k];
     uint32_t cov = 0; unsigned long long sum = 0;

@@ -4,8 +4,7 @@
 //
 //   add          dep_add_body without the per-row words, with or without D as counted positions; a counted read marks its contig in touched
 //   carry        an exclusive scan in place in two levels, for 32-bit (the depth in front of every tile) and 64-bit words (the result index in
-//                front of every tile): chunks of DEPC_CHUNK words are reduced per workgroup, the chunk sums scanned by one workgroup, and
-//                every workgroup scans its chunk again behind its sum.  The total lands behind the last word.
+//                front of every tile): dev_scan.hip's carry_* with ScanSum, launched by depth_carry.  The total lands behind the last word.
 //   count        per tile the positions it emits: those of its row (none behind the row's end) with depth > 0, or all of them when the mode
 //                and touched say so -- then the tile's table is not read
 //   emit         a window [o_a, o_b) of result indices and the contiguous tiles that hold it: a workgroup rescans its tile, compacts the
@@ -19,67 +18,6 @@ template <bool BQ, bool DEL> __global__ void __launch_bounds__(256) bam_depth_ad
     dep_add_body<BQ, DEL, false>(a, diff, nullptr, touched, steps);
 }
 __global__ void __launch_bounds__(256) bam_depth_classify_del(DepArgs a) { dep_classify_body<true>(a); }
-
-// ---- the carry in two levels -----------------------------------------------------------------------------------------------------------------
-#define DEPC_PER_THREAD 16u
-#define DEPC_CHUNK (256u * DEPC_PER_THREAD)
-template <typename T> __device__ __forceinline__ T depc_block_scan(T v, T *sh) {                  // inclusive over the 256 threads
-    const uint32_t t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-        const T y = t >= d ? sh[t - d] : (T)0;
-        __syncthreads();
-        sh[t] += y;
-        __syncthreads();
-    }
-    const T r = sh[t];
-    __syncthreads();
-    return r;
-}
-// part[b] = the sum of chunk b of v[0 .. n)
-template <typename T> __global__ void __launch_bounds__(256) dep_carry_reduce(const T *__restrict__ v, uint64_t n, T *__restrict__ part) {
-    __shared__ T sh[256];
-    const uint64_t b = (uint64_t)blockIdx.x * DEPC_CHUNK + threadIdx.x * DEPC_PER_THREAD;
-    T tot = 0;
-#pragma unroll
-    for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) tot += b + e < n ? v[b + e] : (T)0;
-    const T incl = depc_block_scan<T>(tot, sh);
-    if (threadIdx.x == 255u) part[blockIdx.x] = incl;
-}
-// part[0 .. np) becomes its exclusive scan, part[np] the total: one workgroup, DEPC_CHUNK sums a turn
-template <typename T> __global__ void __launch_bounds__(256) dep_carry_scan(T *__restrict__ part, uint64_t np) {
-    __shared__ T sh[256];
-    T carry = 0;
-    for (uint64_t t0 = 0; t0 < np; t0 += DEPC_CHUNK) {
-        const uint64_t b = t0 + threadIdx.x * DEPC_PER_THREAD;
-        T own[DEPC_PER_THREAD], tot = 0;
-#pragma unroll
-        for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) { own[e] = b + e < np ? part[b + e] : (T)0; tot += own[e]; }
-        const T incl = depc_block_scan<T>(tot, sh);
-        T run = carry + incl - tot;
-#pragma unroll
-        for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) if (b + e < np) { part[b + e] = run; run += own[e]; }
-        sh[threadIdx.x] = incl;
-        __syncthreads();
-        carry += sh[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[np] = carry;
-}
-// v[i] becomes the sum of v[0 .. i), and v[n] the total (the buffer has n + 1 words)
-template <typename T> __global__ void __launch_bounds__(256) dep_carry_apply(T *__restrict__ v, uint64_t n, const T *__restrict__ part, uint64_t np) {
-    __shared__ T sh[256];
-    const uint64_t b = (uint64_t)blockIdx.x * DEPC_CHUNK + threadIdx.x * DEPC_PER_THREAD;
-    T own[DEPC_PER_THREAD], tot = 0;
-#pragma unroll
-    for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) { own[e] = b + e < n ? v[b + e] : (T)0; tot += own[e]; }
-    const T incl = depc_block_scan<T>(tot, sh);
-    T run = part[blockIdx.x] + incl - tot;
-#pragma unroll
-    for (uint32_t e = 0; e < DEPC_PER_THREAD; e++) if (b + e < n) { v[b + e] = run; run += own[e]; }
-    if (blockIdx.x == 0 && threadIdx.x == 0) v[n] = part[np];
-}
 
 // ---- count and emit ----------------------------------------------------------------------------------------------------------------------------
 struct DepEmitArgs {
@@ -104,11 +42,11 @@ __global__ void __launch_bounds__(256) dep_tile_count(const int32_t *__restrict_
     const int4 v = *(const int4 *)(diff + (uint64_t)blockIdx.x * DEP_TILE + threadIdx.x * 4u);
     const uint32_t d[4] = {(uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w};
     const uint32_t tot = d[0] + d[1] + d[2] + d[3];
-    uint32_t run = tcarry[blockIdx.x] + dep_block_scan(tot, sh) - tot, cnt = 0;
+    uint32_t run = tcarry[blockIdx.x] + block_scan<uint32_t, ScanSum>(tot, sh) - tot, cnt = 0;
     const uint64_t p0 = tp + threadIdx.x * 4u;
 #pragma unroll
     for (uint32_t e = 0; e < 4u; e++) { run += d[e]; cnt += p0 + e < len && (int32_t)run > 0 ? 1u : 0u; }
-    const uint32_t incl = dep_block_scan(cnt, sh);
+    const uint32_t incl = block_scan<uint32_t, ScanSum>(cnt, sh);
     if (threadIdx.x == 255u) tcnt[blockIdx.x] = incl;
 }
 // out[k] = the result index in front of row k (k = n_rows: the number of positions of the whole result)
@@ -138,10 +76,10 @@ __global__ void __launch_bounds__(256) dep_emit(DepEmitArgs a) {
     const int4 v = *(const int4 *)(a.diff + tile * DEP_TILE + threadIdx.x * 4u);
     const uint32_t d[4] = {(uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w};
     const uint32_t tot = d[0] + d[1] + d[2] + d[3];
-    uint32_t run = a.tcarry[tile] + dep_block_scan(tot, sh) - tot, dep[4], em = 0, cnt = 0;
+    uint32_t run = a.tcarry[tile] + block_scan<uint32_t, ScanSum>(tot, sh) - tot, dep[4], em = 0, cnt = 0;
 #pragma unroll
     for (uint32_t e = 0; e < 4u; e++) { run += d[e]; dep[e] = run; if (p0 + e < len && (all || (int32_t)run > 0)) { em |= 1u << e; cnt++; } }
-    uint32_t at = dep_block_scan(cnt, sh) - cnt;                                                   // (ends in a barrier)
+    uint32_t at = block_scan<uint32_t, ScanSum>(cnt, sh) - cnt;                                                   // (ends in a barrier)
 #pragma unroll
     for (uint32_t e = 0; e < 4u; e++) if ((em >> e) & 1u) { ldep[at] = dep[e]; lpos[at] = (uint16_t)(threadIdx.x * 4u + e); at++; }
     __syncthreads();

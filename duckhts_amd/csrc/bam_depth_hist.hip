@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(256) dhi_hist(const int32_t *__restrict__ diff
         const int4 v = *(const int4 *)(diff + tile * DEP_TILE + threadIdx.x * 4u);
         const uint32_t d[4] = {(uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w};
         const uint32_t tot = d[0] + d[1] + d[2] + d[3];
-        uint32_t run = tcarry[tile] + dep_block_scan(tot, sh) - tot, dep[4];
+        uint32_t run = tcarry[tile] + block_scan<uint32_t, ScanSum>(tot, sh) - tot, dep[4];
 #pragma unroll
         for (uint32_t e = 0; e < 4u; e++) { run += d[e]; dep[e] = run; }
         const uint64_t p0 = tp + threadIdx.x * 4u;
@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(256) dhi_group_count(const unsigned long long 
     const unsigned long long *row = table + (uint64_t)blockIdx.x * ((uint64_t)cap + 1u);
     uint32_t cnt = 0;
     for (uint64_t b = threadIdx.x; b <= cap; b += 256u) cnt += row[b] != 0ull ? 1u : 0u;
-    const uint32_t incl = dep_block_scan(cnt, sh);
+    const uint32_t incl = block_scan<uint32_t, ScanSum>(cnt, sh);
     if (threadIdx.x == 255u) gcnt[blockIdx.x] = incl;
 }
 
@@ -124,8 +124,8 @@ __global__ void __launch_bounds__(256) dhi_emit(DhiEmitArgs a) {
             v[e] = b >= 0 ? row[b] : 0ull;
             tot += v[e]; cnt += v[e] != 0ull ? 1u : 0u;
         }
-        const unsigned long long incl_sum = depc_block_scan<unsigned long long>(tot, sh64);
-        const uint32_t incl_cnt = dep_block_scan(cnt, sh);
+        const unsigned long long incl_sum = block_scan<unsigned long long, ScanSum>(tot, sh64);
+        const uint32_t incl_cnt = block_scan<uint32_t, ScanSum>(cnt, sh);
         unsigned long long run_sum = above_sum + incl_sum - tot, run_cnt = above_cnt + incl_cnt - cnt;
 #pragma unroll
         for (uint32_t e = 0; e < 4u; e++) {

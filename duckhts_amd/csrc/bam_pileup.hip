@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(256) pil_tile_count(const uint32_t *__restrict
     const uint32_t k = tile_row[((uint64_t)blockIdx.x * PIL_TILE >> sshift) / DEP_TILE];           // (a tile of words lies inside one tile of positions)
     const uint4 v = *(const uint4 *)(table + w0);
     const uint32_t cnt = (uint32_t)__popc(pil_emit_mask(v, w0, sshift, rbase[k], (uint64_t)(rend[k] - rbeg[k]), min_count));
-    const uint32_t incl = dep_block_scan(cnt, sh);
+    const uint32_t incl = block_scan<uint32_t, ScanSum>(cnt, sh);
     if (threadIdx.x == 255u) tcnt[blockIdx.x] = incl;
 }
 // out[k] = the result index in front of row k (k = n_rows: the rows of the whole result)
@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(256) pil_emit(PilEmitArgs a) {
     const uint4 v = *(const uint4 *)(a.table + w0);
     const uint32_t d[4] = {v.x, v.y, v.z, v.w};
     const uint32_t em = pil_emit_mask(v, w0, a.sshift, rb, (uint64_t)(a.rend[k] - a.rbeg[k]), a.min_count), cnt = (uint32_t)__popc(em);
-    uint32_t at = dep_block_scan(cnt, sh) - cnt;                                                   // (ends in a barrier)
+    uint32_t at = block_scan<uint32_t, ScanSum>(cnt, sh) - cnt;                                                   // (ends in a barrier)
 #pragma unroll
     for (uint32_t e = 0; e < 4u; e++) if ((em >> e) & 1u) { lcnt[at] = d[e]; lidx[at] = (uint16_t)(threadIdx.x * 4u + e); at++; }
     __syncthreads();

@@ -13,6 +13,7 @@
 // from a prefix sum of per-tile counts; string columns are written with a length pass +
 // prefix sums + a 16-lanes-per-record write pass.  Integer/byte work only.
 #include "dhts_common.h"
+#include "dev_scan.hip"
 
 #define REC_OK 0
 #define REC_INVALID 1
@@ -283,8 +284,7 @@ extern "C" __global__ void __launch_bounds__(1024) scan_partials(ScanArgs a, int
     for (int64_t base = 0; base < nparts; base += 1024) {
         int64_t i = base + threadIdx.x;
         uint64_t v = i < nparts ? p[i] : 0;
-        sh[threadIdx.x] = v; __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) { uint64_t t = ((int)threadIdx.x >= d) ? sh[threadIdx.x - d] : 0; __syncthreads(); sh[threadIdx.x] += t; __syncthreads(); }
+        block_scan<uint64_t, ScanSum, 1024>(v, sh);
         if (i < nparts) p[i] = carry + sh[threadIdx.x] - v;
         __syncthreads();
         if (threadIdx.x == 1023) carry += sh[1023];
@@ -300,8 +300,7 @@ extern "C" __global__ void __launch_bounds__(256) scan_apply(ScanArgs a) {
     uint32_t v[16]; uint32_t s = 0;
 #pragma unroll
     for (int k = 0; k < 16; k++) { int64_t i = base + k; v[k] = i < n ? in[i] : 0; s += v[k]; }
-    sh[threadIdx.x] = s; __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) { uint32_t t = ((int)threadIdx.x >= d) ? sh[threadIdx.x - d] : 0; __syncthreads(); sh[threadIdx.x] += t; __syncthreads(); }
+    block_scan<uint32_t, ScanSum, 256>(s, sh);
     uint64_t run = a.partial[arr][blockIdx.x] + sh[threadIdx.x] - s;
 #pragma unroll
     for (int k = 0; k < 16; k++) {

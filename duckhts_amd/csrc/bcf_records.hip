@@ -17,6 +17,7 @@
 //   4. matrix prefix sums over those counts, then bcf_cells<true> writes list children and string bytes in place.
 #pragma once
 #include "dhts_common.h"
+#include "dev_scan.hip"
 
 struct BcfStream {
     const uint8_t *u; uint64_t ulen;
@@ -790,8 +791,7 @@ extern "C" __global__ void __launch_bounds__(1024) mscan_partials(MScanArgs a) {
     for (int64_t base = 0; base < a.nparts; base += 1024) {
         int64_t i = base + threadIdx.x;
         uint64_t v = i < a.nparts ? p[i] : 0;
-        sh[threadIdx.x] = v; __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) { uint64_t t = ((int)threadIdx.x >= d) ? sh[threadIdx.x - d] : 0; __syncthreads(); sh[threadIdx.x] += t; __syncthreads(); }
+        block_scan<uint64_t, ScanSum, 1024>(v, sh);
         if (i < a.nparts) p[i] = carry + sh[threadIdx.x] - v;
         __syncthreads();
         if (threadIdx.x == 1023) carry += sh[1023];
@@ -806,8 +806,7 @@ extern "C" __global__ void __launch_bounds__(256) mscan_apply(MScanArgs a) {
     uint32_t v[16]; uint32_t s = 0;
 #pragma unroll
     for (int k = 0; k < 16; k++) { int64_t i = base + k; v[k] = i < a.n ? in[i] : 0; s += v[k]; }
-    sh[threadIdx.x] = s; __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) { uint32_t t = ((int)threadIdx.x >= d) ? sh[threadIdx.x - d] : 0; __syncthreads(); sh[threadIdx.x] += t; __syncthreads(); }
+    block_scan<uint32_t, ScanSum, 256>(s, sh);
     uint64_t run = a.partial[(size_t)blockIdx.y * a.nparts + blockIdx.x] + sh[threadIdx.x] - s;
 #pragma unroll
     for (int k = 0; k < 16; k++) { int64_t i = base + k; if (i <= a.n) out[i] = (uint32_t)run; run += v[k]; }

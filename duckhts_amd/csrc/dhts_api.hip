@@ -242,7 +242,7 @@ struct CoverageState : AccumBase, DepLayout {
     bool res_ready = false; dhts_coverage_params P;
     uint64_t row_next = 0;
     std::vector<int64_t> h_cols[DHTS_COVERAGE_COL_COUNT];
-    DevBuf words, step, rlen, k0, k1, tsum, tcov, tdepth, res, ones, cols[DHTS_COVERAGE_COL_COUNT];
+    DevBuf words, step, rlen, k0, k1, tsum, part, tcov, tdepth, res, ones, cols[DHTS_COVERAGE_COL_COUNT];
 };
 // bam_depth (bam_depth.hip, dhts_bam_depth.inc): the parameters, the layout, the touched contigs and the step counters, per-batch scratch, and
 // of a result the depth (tsum) and the result index (toff) in front of every tile, the result index in front of every sorted row (row_off),

@@ -215,15 +215,41 @@ template <typename Stats> static void dep_stats_common(Stats *out, const uint64_
     for (int k = 0; k < DEP_N_STEPS; k++) out->n_rows += s[k];
 }
 
-// an exclusive scan of v[0 .. n) in place, the total in v[n]: the carry in two levels (part: scratch)
-template <typename T> static int depth_carry(dhts_ctx *c, DevBuf &part, T *v, uint64_t n) {
-    const uint64_t np = (n + DEPC_CHUNK - 1) / DEPC_CHUNK;
+// the carry in two levels (dev_scan.hip) over v[0 .. n) in place: v[i] = seed combined with the elements in front of i, the total in v[n]
+// (the buffer has n + 1 elements); REV: with the elements behind i, and no total.  part: scratch
+template <typename T, typename Op, bool REV, uint32_t PER = 16u> static int scan_carry(dhts_ctx *c, DevBuf &part, T *v, uint64_t n, T seed) {
+    const uint64_t np = (n + 256u * PER - 1) / (256u * PER);
     ENSURE(c, part, (size_t)(np + 1) * sizeof(T) + 64);
-    hipLaunchKernelGGL(dep_carry_reduce<T>, dim3((unsigned)np), dim3(256), 0, c->stream, (const T *)v, n, (T *)part.p);
-    hipLaunchKernelGGL(dep_carry_scan<T>, dim3(1), dim3(256), 0, c->stream, (T *)part.p, np);
-    hipLaunchKernelGGL(dep_carry_apply<T>, dim3((unsigned)np), dim3(256), 0, c->stream, v, n, (const T *)part.p, np);
+    hipLaunchKernelGGL((carry_reduce<T, Op, PER>), dim3((unsigned)np), dim3(256), 0, c->stream, (const T *)v, n, (T *)part.p);
+    hipLaunchKernelGGL((carry_scan<T, Op, REV, PER>), dim3(1), dim3(256), 0, c->stream, (T *)part.p, np, seed);
+    hipLaunchKernelGGL((carry_apply<T, Op, REV, PER>), dim3((unsigned)np), dim3(256), 0, c->stream, v, n, (const T *)part.p, np);
     return 0;
 }
+// an exclusive sum of v[0 .. n) in place, the total in v[n]
+template <typename T> static int depth_carry(dhts_ctx *c, DevBuf &part, T *v, uint64_t n) { return scan_carry<T, ScanSum, false>(c, part, v, n, (T)0); }
+}
+
+// tests: the carry alone, through the launcher the count functions call, on host_v (n elements in; the forward kinds return n + 1, the total
+// last).  kind 0: uint32_t sum; 1: uint64 sum; 2: uint64 suffix minimum, seeded; 3: CovVec sum, four elements per thread.  The data and the
+// chunk values lie in the context's compressor scratch (z_in, z_tok).  host_v has room for n + 1 elements and element n goes to the device
+// as it is: the carry must not read it, so the caller puts a value there that would show.
+int dhts_debug_carry(dhts_ctx *c, int kind, void *host_v, uint64_t n, uint64_t seed) {
+    if (!c) return -1;
+    if (kind < 0 || kind > 3 || !host_v || n == 0 || n > (1ull << 28)) return fail(c, "debug_carry: arguments out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t esz = kind == 0 ? 4 : kind == 3 ? sizeof(CovVec) : 8, n_out = (size_t)n + (kind == 2 ? 0 : 1);
+    ENSURE(c, c->z_in, ((size_t)n + 1) * esz + 64);
+    HIPCHK(c, hipMemcpyAsync(c->z_in.p, host_v, ((size_t)n + 1) * esz, hipMemcpyHostToDevice, c->stream));
+    int rc;
+    if (kind == 0) rc = depth_carry<uint32_t>(c, c->z_tok, (uint32_t *)c->z_in.p, n);
+    else if (kind == 1) rc = depth_carry<unsigned long long>(c, c->z_tok, (unsigned long long *)c->z_in.p, n);
+    else if (kind == 2) rc = scan_carry<unsigned long long, ScanMin, true>(c, c->z_tok, (unsigned long long *)c->z_in.p, n, (unsigned long long)seed);
+    else rc = scan_carry<CovVec, ScanSum, false, 4u>(c, c->z_tok, (CovVec *)c->z_in.p, n, CovVec{});
+    if (rc) return -1;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(host_v, c->z_in.p, n_out * esz, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 // ---- a page of a result that is emitted out of the table (bam_depth, bam_pileup, bam_bedgraph) ----------------------------------------------------------

@@ -109,16 +109,16 @@ int dhts_bam_bedcov_stats(dhts_ctx *c, dhts_bedcov_stats *out) {
     return 0;
 }
 
-// inclusive prefix sums of the four counter words over the whole concatenation, into S.sums (the counters stay: a later batch adds to them)
+// prefix sums of the four counter words over the whole concatenation, in S.sums: a copy of the counters (they stay: a later batch adds to
+// them) scanned in place, so sums[i] = the sum in front of i and the inclusive sums of i lie in sums[i + 1]
 static int bedcov_sums(dhts_ctx *c) {
     BedcovState &S = c->cov;
     if (S.sums_ready) return 0;
-    const uint64_t n = S.n_points + 1, ntiles = (n + COV_TILE - 1) / COV_TILE;
-    ENSURE(c, S.sums, (size_t)n * COV_WORDS * 8 + 64); ENSURE(c, S.partial, (size_t)ntiles * COV_WORDS * 8 + 64);
+    const uint64_t n = S.n_points + 1;
+    ENSURE(c, S.sums, (size_t)(n + 1) * sizeof(CovVec) + 64);
     KTimer tm(c, DHTS_K_SCAN);
-    hipLaunchKernelGGL(cov_scan_reduce, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const unsigned long long *)S.cnt.p, n, (unsigned long long *)S.partial.p);
-    hipLaunchKernelGGL(cov_scan_partials, dim3(1), dim3(256), 0, c->stream, (unsigned long long *)S.partial.p, ntiles);
-    hipLaunchKernelGGL(cov_scan_apply, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const unsigned long long *)S.cnt.p, n, (const unsigned long long *)S.partial.p, (unsigned long long *)S.sums.p);
+    HIPCHK(c, hipMemcpyAsync(S.sums.p, S.cnt.p, (size_t)n * sizeof(CovVec), hipMemcpyDeviceToDevice, c->stream));
+    if (scan_carry<CovVec, ScanSum, false, 4u>(c, S.partial, (CovVec *)S.sums.p, n, CovVec{})) return -1;
     HIPCHK(c, hipGetLastError());
     S.sums_ready = true;
     return 0;

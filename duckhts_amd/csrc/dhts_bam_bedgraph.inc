@@ -92,16 +92,6 @@ static BdgClasses bedgraph_classes(const dhts_bedgraph_params &P) {
     return k;
 }
 
-// the suffix minimum of v[0 .. n) in place: v[i] = the least word behind i, `none` where there is none (part: scratch)
-static int bedgraph_suffix(dhts_ctx *c, DevBuf &part, unsigned long long *v, uint64_t n, unsigned long long none) {
-    const uint64_t np = (n + DEPC_CHUNK - 1) / DEPC_CHUNK;
-    ENSURE(c, part, (size_t)(np + 1) * 8 + 64);
-    hipLaunchKernelGGL(bdg_suffix_reduce, dim3((unsigned)np), dim3(256), 0, c->stream, (const unsigned long long *)v, n, (unsigned long long *)part.p);
-    hipLaunchKernelGGL(bdg_suffix_scan, dim3(1), dim3(256), 0, c->stream, (unsigned long long *)part.p, np, none);
-    hipLaunchKernelGGL(bdg_suffix_apply, dim3((unsigned)np), dim3(256), 0, c->stream, v, n, (const unsigned long long *)part.p);
-    return 0;
-}
-
 // the count: the depth, the result index and the next boundary around every tile, and the result index in front of every sorted row on the host
 static int bedgraph_result(dhts_ctx *c) {
     BedgraphState &S = c->bdg;
@@ -118,7 +108,8 @@ static int bedgraph_result(dhts_ctx *c) {
             hipLaunchKernelGGL(bdg_tile_count, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const int32_t *)S.diff.p, (const uint32_t *)S.tsum.p, (const uint32_t *)S.tile_row.p,
                                (const unsigned long long *)S.rbase.p, (const long long *)S.rbeg.p, (const long long *)S.rend.p, bedgraph_classes(S.P), (unsigned long long)S.slots,
                                (unsigned long long *)S.toff.p, (unsigned long long *)S.tnext.p);
-            if (bedgraph_suffix(c, S.part, (unsigned long long *)S.tnext.p, ntiles, (unsigned long long)S.slots)) return -1;
+            // the suffix minimum in place: tnext[t] = the least tfirst behind t, `none` (the slots of the table) where there is none
+            if (scan_carry<unsigned long long, ScanMin, true>(c, S.part, (unsigned long long *)S.tnext.p, ntiles, (unsigned long long)S.slots)) return -1;
             if (depth_carry<unsigned long long>(c, S.part, (unsigned long long *)S.toff.p, ntiles)) return -1;
             hipLaunchKernelGGL(dep_row_offsets, dim3((unsigned)((R + 1 + 255) / 256)), dim3(256), 0, c->stream, (const unsigned long long *)S.toff.p, (const unsigned long long *)S.rbase.p,
                                (uint64_t)R, ntiles, (unsigned long long *)S.rowres.p);

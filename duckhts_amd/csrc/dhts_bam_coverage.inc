@@ -74,11 +74,11 @@ static int coverage_result(dhts_ctx *c) {
     const size_t R = (size_t)S.n_sorted, n_out = S.o_tid.size(); const uint64_t ntiles = S.slots / DEP_TILE;
     std::vector<uint64_t> res(R * DEP_RES_WORDS + 1, 0);
     if (R) {
-        ENSURE(c, S.tsum, (size_t)ntiles * 4 + 64); ENSURE(c, S.tcov, (size_t)ntiles * 4 + 64); ENSURE(c, S.tdepth, (size_t)ntiles * 8 + 64); ENSURE(c, S.res, R * DEP_RES_WORDS * 8 + 64);
+        ENSURE(c, S.tsum, (size_t)(ntiles + 1) * 4 + 64); ENSURE(c, S.tcov, (size_t)ntiles * 4 + 64); ENSURE(c, S.tdepth, (size_t)ntiles * 8 + 64); ENSURE(c, S.res, R * DEP_RES_WORDS * 8 + 64);
         {
             KTimer tm(c, DHTS_K_SCAN);
             hipLaunchKernelGGL(dep_tile_sum, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const int32_t *)S.diff.p, (uint32_t *)S.tsum.p);
-            hipLaunchKernelGGL(dep_tile_carry, dim3(1), dim3(256), 0, c->stream, (uint32_t *)S.tsum.p, ntiles);
+            if (depth_carry<uint32_t>(c, S.part, (uint32_t *)S.tsum.p, ntiles)) return -1;
             hipLaunchKernelGGL(dep_tile_reduce, dim3((unsigned)ntiles), dim3(256), 0, c->stream, (const int32_t *)S.diff.p, (const uint32_t *)S.tsum.p, (const uint32_t *)S.tile_row.p,
                                (const unsigned long long *)S.rbase.p, (const long long *)S.rbeg.p, (const long long *)S.rend.p, (long long)S.P.min_depth, (uint32_t *)S.tcov.p, (unsigned long long *)S.tdepth.p);
             hipLaunchKernelGGL(dep_row_sum, dim3((unsigned)R), dim3(256), 0, c->stream, (const uint32_t *)S.tcov.p, (const unsigned long long *)S.tdepth.p, (const unsigned long long *)S.rbase.p,

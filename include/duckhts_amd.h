@@ -909,7 +909,7 @@ int dhts_bam_pileup_batch_fetch(dhts_ctx *bam, const dhts_pileup_batch *b, void 
  *   Method: bam_depth's add pass; per tile the emitted boundaries and its first boundary of any class, a suffix minimum in two levels for the
  *     next boundary behind every tile and a carry in two levels for the result index in front of it; a page is a window of result indices,
  *     emitted by the tiles that hold it, and a run that leaves its tile ends where the suffix minimum says, clipped to its row
- *     (csrc/bam_bedgraph.hip, DESIGN.md 4n).
+ *     (csrc/bam_bedgraph.hip, DESIGN.md 4o).
  * All errors are prefixed "bam_bedgraph:".  Every call on a context in the wrong state fails with a dhts_error that names what is missing. */
 enum { DHTS_BEDGRAPH_CHROM = 0, DHTS_BEDGRAPH_START, DHTS_BEDGRAPH_END, DHTS_BEDGRAPH_DEPTH, DHTS_BEDGRAPH_COL_COUNT };
 typedef struct {
@@ -993,7 +993,7 @@ int dhts_bam_bedgraph_batch_fetch(dhts_ctx *bam, const dhts_bedgraph_batch *b, v
  *   Method: bam_depth's add pass; tile sums and their carry; one read of the table by workgroups that own a span of tiles and count into an
  *     LDS histogram of 4,096 bins, flushed into the table where the group changes; per group the non-empty bins and their carry; a page is a
  *     window of result indices, emitted by the groups that hold it from the top bin down behind a suffix sum (csrc/bam_depth_hist.hip,
- *     DESIGN.md 4o).
+ *     DESIGN.md 4p).
  * The entries are dhts_bam_hist_*: the names that begin dhts_bam_depth_ are bam_depth's own.
  * All errors are prefixed "bam_depth_hist:".  Every call on a context in the wrong state fails with a dhts_error that names what is missing. */
 enum { DHTS_DEPTH_HIST_CHROM = 0, DHTS_DEPTH_HIST_START, DHTS_DEPTH_HIST_END, DHTS_DEPTH_HIST_DEPTH, DHTS_DEPTH_HIST_N_POSITIONS, DHTS_DEPTH_HIST_N_AT_LEAST,

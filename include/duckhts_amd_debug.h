@@ -52,6 +52,12 @@ int dhts_debug_meta(dhts_ctx *, int64_t s, uint32_t *out4);
  * symbols (host arrays, case after case); lens_out: ncases * nsym code lengths, codes_out: the table words (bit-reversed code | length << 16).
  * Only for count vectors the builder's loops are known to end on (tests/deflate_code_ref.py). */
 int dhts_debug_deflate_codes(dhts_ctx *, const uint32_t *counts, uint32_t nsym, uint32_t maxbits, int64_t ncases, uint8_t *lens_out, uint32_t *codes_out);
+/* tests: the carry in two levels alone (dev_scan.hip), through the launcher the bam_* count functions call.  kind 0: uint32_t sum, 1: uint64
+ * sum, 2: uint64 suffix minimum (host_v[i] = the least element behind i, seed where there is none), 3: sum of elements of four uint64 words
+ * added word by word, four elements per thread.  host_v holds n >= 1 elements on entry and the scanned n on return; the sums are exclusive,
+ * start at 0 (seed is unused) and return n + 1 elements, the total last.  host_v has room for n + 1 elements of every kind; element n is
+ * uploaded as it is and must not change an answer. */
+int dhts_debug_carry(dhts_ctx *, int kind, void *host_v, uint64_t n, uint64_t seed);
 /* tests: what the record stage's repair and retry paths did since the context was opened or rewound (host-side counters, read_bam and
  * read_bcf alike).  out[0] tiles changed by the repair rounds and by the sequential fallback, summed over rounds and batches;
  * out[1] repair rounds that changed a tile (the two rounds read_bam always queues count only when they repaired something, so a file that

@@ -121,6 +121,14 @@ def test_the_sources_are_part_of_the_build():
     assert ext.index("register_bam_bedgraph_function(conn)") > ext.index("register_bam_pileup_function(conn)") and 'getenv("DHTS_BEDGRAPH_FUNCTIONS")' in ext
     hip = source("bam_bedgraph.hip")
     assert '#include "bam_depth.hip"' in hip
-    for kernel in ("bdg_tile_count", "bdg_suffix_reduce", "bdg_suffix_scan", "bdg_suffix_apply", "bdg_emit"):
+    for kernel in ("bdg_tile_count", "bdg_emit"):
         assert re.search(r"__global__ void __launch_bounds__\(256\) " + kernel + r"\(", hip), kernel
         assert kernel in source("dhts_bam_bedgraph.inc")
+    # the suffix minimum is the shared carry in its reverse / min form: the three kernels of dev_scan.hip, one launcher, no copy of them left
+    scan = source("dev_scan.hip")
+    for kernel in ("carry_reduce", "carry_scan", "carry_apply"):
+        assert re.search(r"template <[^>]*> __global__ void __launch_bounds__\(256\) " + kernel + r"\(", scan), kernel
+        assert source("dhts_bam_accum.inc").count("(" + kernel + "<T, Op, ") == 1
+    assert source("dhts_bam_bedgraph.inc").count("scan_carry<unsigned long long, ScanMin, true>(c, S.part, (unsigned long long *)S.tnext.p, ntiles, (unsigned long long)S.slots)") == 1
+    csrc = os.path.join(ROOT, "duckhts_amd", "csrc")
+    assert not [f for f in sorted(os.listdir(csrc)) if "bdg_suffix_" in source(f)]

@@ -117,6 +117,20 @@ def test_the_sources_are_part_of_the_build():
         assert source(f"dhts_bam_{name}.inc").count(f'bam_filter_check(m, "{fn}", ') == 1 and source(f"duckdb_{name}.inc").count(f'bam_filter_check(m, "{fn}", ') == 1
     assert ext.index('#include "duckdb_depth.inc"') > ext.index('#include "duckdb_coverage.inc"')
     assert '#include "bam_coverage.hip"' in source("bam_depth.hip")
-    # bam_coverage launches what it launched: the two instantiations of bam_depth_add, and dep_tile_carry in its result
+    # bam_coverage launches what it launched: the two instantiations of bam_depth_add; its result takes the carry in two levels like the
+    # others, and the single-workgroup carry is gone
     cov = source("dhts_bam_coverage.inc")
-    assert "bam_depth_add<true>" in cov and "bam_depth_add<false>" in cov and "dep_tile_carry" in cov and "nowords" not in cov
+    assert "bam_depth_add<true>" in cov and "bam_depth_add<false>" in cov and "depth_carry<uint32_t>" in cov and "nowords" not in cov
+    csrc = os.path.join(ROOT, "duckhts_amd", "csrc")
+    assert not [f for f in sorted(os.listdir(csrc)) if "dep_tile_carry" in source(f)]
+
+
+def test_the_workgroup_scan_through_lds_is_written_once():
+    """the Hillis-Steele loop over the 256 or 1,024 threads of a workgroup stands in dev_scan.hip alone: every count kernel and the record
+    stage call block_scan (the wave-level loops, d < 64, are other algorithms and stay where they are)"""
+    csrc = os.path.join(ROOT, "duckhts_amd", "csrc")
+    loop = re.compile(r"for \((?:uint32_t|int) d = 1; d < (?:256|1024|NT)")
+    assert [f for f in sorted(os.listdir(csrc)) if loop.search(source(f))] == ["dev_scan.hip"]
+    assert len(loop.findall(source("dev_scan.hip"))) == 1 and "block_scan(T v, T *sh)" in source("dev_scan.hip")
+    for f in sorted(os.listdir(csrc)):
+        assert not re.search(r"\b(dep_block_scan|depc_block_scan|bdg_block_scan_min|cov_block_scan|dep_carry_|cov_scan_|DEPC_)", source(f)), f

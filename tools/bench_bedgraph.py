@@ -1,4 +1,4 @@
-"""bam_bedgraph against bam_depth on the benchmark's synthetic BAM, resident in HBM (DESIGN.md §4n).
+"""bam_bedgraph against bam_depth on the benchmark's synthetic BAM, resident in HBM (DESIGN.md §4o).
 
 The file is bench.py's (its generator, seed 42; the 25-contig header, so the depth table has 12.4 GB).  One context, the compressed bytes
 uploaded once.  Legs over the same resident bytes, alternated pass by pass in one process after a warm-up pass of each:

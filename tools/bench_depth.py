@@ -11,8 +11,8 @@ one process after a warm-up pass of each:
   (c) fetch        the only route the parent offers: the region's scan with dhts_bam_batch_fetch of FLAG / POS / MAPQ / tid / CIGAR / QUAL
                    into pinned host memory + a numpy expansion (bench_coverage.py's) into a depth array of that contig.  It must equal
                    (b)'s third variant exactly, and the first variant's rows on that contig.
-  coverage         bam_coverage open + scan + result once per pass with the same min_baseq, so that bam_depth_add<false / true> and
-                   dep_tile_carry run on the same batches and the same tile sums as the new instantiations and the carry in two levels
+  coverage         bam_coverage open + scan + result once per pass with the same min_baseq, so that bam_depth_add<false / true> runs on the
+                   same batches as the nowords instantiations, and its result's carry in two levels over the same tile sums as bam_depth's
 One JSON line per leg: the host clock around whole passes (median, min, max), for (b) the parts, rows/s and bytes/s of emit + fetch against
 the rate of a plain device-to-host copy of the same bytes into the same buffer measured in the same run, and the device time of the add
 passes (HIP events of one extra pass).  Run under `rocprofv3 --kernel-trace --stats -- python tools/bench_depth.py --skip-fetch --passes 2`

@@ -1,4 +1,4 @@
-"""bam_depth_hist against bam_coverage's table pass and bam_bedgraph on the benchmark's synthetic BAM, resident in HBM (DESIGN.md §4o).
+"""bam_depth_hist against bam_coverage's table pass and bam_bedgraph on the benchmark's synthetic BAM, resident in HBM (DESIGN.md §4p).
 
 The file is bench.py's (its generator, seed 42; the 25-contig header, so the depth table has 12.4 GB).  One context, the compressed bytes
 uploaded once.  Legs over the same resident bytes, alternated pass by pass in one process after a warm-up pass of each:

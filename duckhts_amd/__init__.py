@@ -141,6 +141,14 @@ class BedgraphStats(C.Structure):
                 ("n_runs", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BedgraphExportParams(C.Structure):
+    _fields_ = [("level", C.c_int32), ("index", C.c_int32), ("min_shift", C.c_int32), ("overwrite", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class BedgraphExportStats(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("bytes_text", C.c_uint64), ("bytes_out", C.c_uint64), ("bytes_index", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DepthHistParams(C.Structure):
     _fields_ = [("min_read_len", C.c_int64), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32), ("require_flags", C.c_int32), ("exclude_flags", C.c_int32),
                 ("include_flags", C.c_int32), ("include_deletions", C.c_int32), ("depth_cap", C.c_int32), ("per", C.c_int32), ("reserved", C.c_int32 * 2)]
@@ -222,6 +230,8 @@ BEDGRAPH_COLUMNS = ["tid", "start", "end", "depth"]
 BEDGRAPH_DTYPES = (np.int32, np.int64, np.int64, np.int32)                   # start 0-based, end exclusive
 BEDGRAPH_COLMASK = DEPTH_COLMASK                                            # the columns of the scan bam_bedgraph accumulates (no string column)
 BEDGRAPH_MAX_BREAKS = 16
+BEDGRAPH_EXPORT_INDEX = {"none": 0, "tbi": 1, "csi": 2}                     # the C struct's index
+ROWS_TEXT_LDS_BYTES = 16384                                                 # csrc/rows_text.hip: RTX_LDS_BYTES, the longest span of 256 rows the write pass stages in LDS
 DEPTH_HIST_COLUMNS = ["tid", "start", "end", "depth", "n_positions", "n_at_least", "length"]
 DEPTH_HIST_DTYPES = (np.int32, np.int64, np.int64, np.int32, np.int64, np.int64, np.int64)   # start 0-based, end exclusive
 DEPTH_HIST_COLMASK = DEPTH_COLMASK                                          # the columns of the scan bam_depth_hist accumulates (no string column)
@@ -260,6 +270,7 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_bam_depth_open", "dhts_bam_depth_accumulate", "dhts_bam_depth_scan", "dhts_bam_depth_stats", "dhts_bam_depth_next", "dhts_bam_depth_batch_host_bytes", "dhts_bam_depth_batch_fetch",
            "dhts_bam_pileup_open", "dhts_bam_pileup_accumulate", "dhts_bam_pileup_scan", "dhts_bam_pileup_stats", "dhts_bam_pileup_next", "dhts_bam_pileup_batch_host_bytes", "dhts_bam_pileup_batch_fetch",
            "dhts_bam_bedgraph_open", "dhts_bam_bedgraph_accumulate", "dhts_bam_bedgraph_scan", "dhts_bam_bedgraph_stats", "dhts_bam_bedgraph_next", "dhts_bam_bedgraph_batch_host_bytes", "dhts_bam_bedgraph_batch_fetch",
+           "dhts_bedgraph_export",
            "dhts_bam_hist_open", "dhts_bam_hist_accumulate", "dhts_bam_hist_scan", "dhts_bam_hist_stats", "dhts_bam_hist_next", "dhts_bam_hist_batch_host_bytes", "dhts_bam_hist_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
@@ -375,6 +386,12 @@ def lib():
             f["batch_host_bytes"].restype = C.c_uint64
             f["batch_host_bytes"].argtypes = [C.POINTER(BedBatch)]
             f["batch_fetch"].argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_bedgraph_export.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(BedgraphExportParams), C.POINTER(BedgraphExportStats)]
+        L.dhts_debug_rows_text.restype = C.c_int64
+        L.dhts_debug_rows_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64]
+        L.dhts_debug_rows_text_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.dhts_debug_export_limits.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+        L.dhts_debug_rows_text_form.argtypes = [C.c_void_p, C.c_int]
         L.dhts_debug_pileup_add_form.argtypes = [C.c_void_p, C.c_int]
         L.dhts_debug_carry.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64]
         L.dhts_debug_hist_max_table_bytes.argtypes = [C.c_uint64]
@@ -1055,6 +1072,46 @@ class Context:
         b = BedBatch()
         self._chk(self.L.dhts_bam_bedgraph_next(self.h, max_rows, mask, C.byref(b)))
         return self._fixed_cols("bedgraph", b, mask, BEDGRAPH_COLUMNS, BEDGRAPH_DTYPES)
+
+    # ---- bam_bedgraph_export ----
+    def bam_bedgraph_export(self, out_path, index="tbi", level=-1, min_shift=0, overwrite=False):
+        """after bam_bedgraph_open and a scan: the result as a bgzipped bedGraph file at out_path, printed and compressed on the device, and its
+        tabix index (index: 'tbi', 'csi' or 'none'; out_path + '.tbi' / '.csi').  -> {"n_rows", "bytes_text", "bytes_out", "bytes_index",
+        "status", "output_path", "index_path" (None without an index)}.  The next bam_bedgraph_next returns page one."""
+        if index not in BEDGRAPH_EXPORT_INDEX:
+            raise DhtsError("bam_bedgraph_export: index must be one of: tbi, csi, none")
+        p = BedgraphExportParams(_clip(level, 31), BEDGRAPH_EXPORT_INDEX[index], _clip(min_shift, 31), int(bool(overwrite)))
+        st = BedgraphExportStats()
+        self._chk(self.L.dhts_bedgraph_export(self.h, os.fsencode(out_path), C.byref(p), C.byref(st)))
+        out = {k: int(getattr(st, k)) for k, _ in BedgraphExportStats._fields_ if k != "reserved"}
+        out["output_path"] = os.fspath(out_path)
+        out["index_path"] = None if index == "none" else os.fspath(out_path) + "." + index
+        return out
+
+    def debug_export_limits(self, page_rows=0, chunk_blocks=0):
+        """tests: the rows of a page and the blocks of a compressor launch of bam_bedgraph_export on this context (0: the defaults)"""
+        self._chk(self.L.dhts_debug_export_limits(self.h, page_rows, chunk_blocks))
+
+    def debug_rows_text_form(self, form):
+        """tests, tools/bench_bedgraph_export.py: the encoder's write pass, "staged" (the default) or "lane" (one lane per row, byte by byte)"""
+        self._chk(self.L.dhts_debug_rows_text_form(self.h, {"staged": 0, "lane": 1}.get(form, -1)))
+
+    def debug_rows_text(self, names, tid, start, end, depth):
+        """tests: the row-text encoder alone (dhts_debug_rows_text): names: a list of bytes; tid, start, end, depth: arrays of one length ->
+        (the text, {"staged", "fallback": the workgroups of the write pass that took either path})"""
+        arena = np.frombuffer(b"".join(names), np.uint8) if names else np.zeros(0, np.uint8)
+        offs = np.concatenate([[0], np.cumsum([len(x) for x in names])]).astype(np.uint32)
+        t, s, e, d = (np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64), np.ascontiguousarray(depth, np.int32))
+        if not len(t) == len(s) == len(e) == len(d):
+            raise ValueError("tid, start, end and depth have to be of one length")
+        args = (arena.ctypes.data, offs.ctypes.data, len(names), t.ctypes.data, s.ctypes.data, e.ctypes.data, d.ctypes.data, len(t))
+        need = self._chk(self.L.dhts_debug_rows_text(self.h, *args, None, 0))
+        out = np.zeros(max(need, 1), np.uint8)
+        got = self._chk(self.L.dhts_debug_rows_text(self.h, *args, out.ctypes.data, need))
+        assert got == need
+        w = (C.c_uint64 * 2)()
+        self._chk(self.L.dhts_debug_rows_text_paths(self.h, w))
+        return out[:need].tobytes(), {"staged": int(w[0]), "fallback": int(w[1])}
 
     # ---- bam_depth_hist (C ABI: dhts_bam_hist_*) ----
     def bam_depth_hist_open(self, bed_ctx=None, min_read_len=0, min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0, include_deletions=0, depth_cap=1000,
@@ -2306,6 +2363,36 @@ def bam_bedgraph(src, region=None, index=None, bed=None, max_blocks=0, max_rows=
         out["contigs"] = [n.encode() if isinstance(n, str) else bytes(n) for n in hdr["ref_names"]]
         out["stats"] = {k: v for k, v in ctx.bam_bedgraph_stats().items() if k != "status"}
         out["status"] = status
+        return out
+    finally:
+        if bctx is not None:
+            bctx.close()
+        ctx.close()
+
+
+def bam_bedgraph_export(src, out_path, index="tbi", level=-1, min_shift=0, overwrite=False, region=None, bam_index=None, bed=None, max_blocks=0, device=0, min_read_len=0,
+                        min_mapq=0, min_baseq=0, include_flags=0, require_flags=0, exclude_flags=0x704, include_deletions=0, zero_runs=0, breaks=None, limits=None):
+    """bam_bedgraph_export(path, out_path :=, index := 'tbi' | 'csi' | 'none', level :=, overwrite :=, and every parameter of bam_bedgraph): the
+    bedGraph of bam_bedgraph written as out_path (a .bed.gz) with its tabix index, printed, compressed and indexed on the device (the contract:
+    include/duckhts_amd.h).  -> the stats: {"n_rows", "bytes_text", "bytes_out", "bytes_index", "status", "output_path", "index_path", "stats":
+    bam_bedgraph's}.  index: the kind of the index written (bam_index: BAI / CSI bytes narrowing the scan of a region query); limits: tests, the
+    (page_rows, chunk_blocks) of debug_export_limits."""
+    if isinstance(breaks, (str, bytes)):
+        text = breaks.decode() if isinstance(breaks, bytes) else breaks
+        try:
+            breaks = [int(x) for x in text.split(",")]
+        except ValueError:
+            raise DhtsError("bam_bedgraph_export: breaks must be strictly increasing integers between 1 and 2147483647") from None
+    (ctx, hdr), bctx = _bam_ctx(src, device, region, bam_index), None
+    try:
+        if bed is not None:
+            bctx = _bed_ctx(device, bed)
+        ctx.bam_bedgraph_open(bctx, min_read_len, min_mapq, min_baseq, include_flags, require_flags, exclude_flags, include_deletions, zero_runs, breaks)
+        ctx.bam_bedgraph_scan(max_blocks)
+        if limits is not None:
+            ctx.debug_export_limits(*limits)
+        out = ctx.bam_bedgraph_export(out_path, index, level, min_shift, overwrite)
+        out["stats"] = {k: v for k, v in ctx.bam_bedgraph_stats().items() if k != "status"}
         return out
     finally:
         if bctx is not None:

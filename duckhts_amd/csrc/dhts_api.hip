@@ -23,6 +23,7 @@
 #include "bam_pileup.hip"
 #include "bam_bedgraph.hip"
 #include "bam_depth_hist.hip"
+#include "rows_text.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
 #include "bgzf_deflate.hip"
@@ -261,11 +262,14 @@ struct PileupState : AccumBase, DepLayout, DepPager {
     DevBuf row_tid, step, rlen, k0, k1, part, rowres, out_tid, out_pos, out_strand, out_nuc, out_count;
 };
 // bam_bedgraph (bam_bedgraph.hip, dhts_bam_bedgraph.inc): bam_depth's state with the classes in the parameters, and of a result the next
-// boundary of any class behind every tile (tnext) beside the depth (tsum) and the result index (toff) in front of it
+// boundary of any class behind every tile (tnext) beside the depth (tsum) and the result index (toff) in front of it.  bam_bedgraph_export
+// (rows_text.hip, dhts_bam_bedgraph_export.inc): the contigs' names on the device, the text offsets of a page's rows, the counters of the
+// encoder's two write paths, the test limits of dhts_debug_export_limits (0: the defaults) and the write pass's form (dhts_debug_rows_text_form)
 struct BedgraphState : AccumBase, DepLayout, DepPager {
     bool res_ready = false; dhts_bedgraph_params P;
     uint64_t n_bed_skipped = 0, n_runs = 0;
     DevBuf touched, row_tid, step, rlen, k0, k1, tsum, part, rowres, tnext, out_tid, out_start, out_end, out_depth;
+    DevBuf x_names, x_noff, x_off, x_which; int64_t x_page_rows = 0, x_chunk_blocks = 0; int x_form = 0;
 };
 // bam_depth_hist (bam_depth_hist.hip, dhts_bam_depth_hist.inc): the parameters, the layout, the group of every sorted row and the groups' contig,
 // start, end and length, the histogram table (hist: depth_cap + 1 64-bit words per group), of a result the depth in front of every tile (tsum)
@@ -637,6 +641,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_depth.inc"
 #include "dhts_bam_pileup.inc"
 #include "dhts_bam_bedgraph.inc"
+#include "dhts_bam_bedgraph_export.inc"
 #include "dhts_bam_depth_hist.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"

@@ -122,22 +122,17 @@ static int bedgraph_result(dhts_ctx *c) {
     return 0;
 }
 
-int dhts_bam_bedgraph_next(dhts_ctx *c, int64_t max_rows, uint32_t colmask, dhts_bedgraph_batch *out) {
-    if (!c || !out) return -1;
-    memset(out, 0, sizeof(*out));
+// the next <= max_rows rows of the result as a page of device columns (dst[i]: null for a column colmask leaves out), emitted and waited for;
+// *n_rows its rows, *last whether it ends the result.  dhts_bam_bedgraph_next hands the page out, dhts_bedgraph_export prints it
+static int bedgraph_page(dhts_ctx *c, int64_t max_rows, uint32_t colmask, void *dst[DHTS_BEDGRAPH_COL_COUNT], int64_t *n_rows, bool *last) {
     BedgraphState &S = c->bdg;
-    if (!S.open) return fail(c, "%s", BEDGRAPH_WHO.not_open);
-    HIPCHK(c, hipSetDevice(c->device));
     if (max_rows <= 0) max_rows = BEDGRAPH_DEFAULT_ROWS;
     if (bedgraph_result(c)) return -1;
     DepPage pg;
     dep_page_windows(S, S, max_rows, pg);
     const int64_t nrows = (int64_t)pg.rows;
     DevBuf *const bufs[DHTS_BEDGRAPH_COL_COUNT] = {&S.out_tid, &S.out_start, &S.out_end, &S.out_depth};
-    void *dst[DHTS_BEDGRAPH_COL_COUNT] = {nullptr, nullptr, nullptr, nullptr};
-    colmask &= (1u << DHTS_BEDGRAPH_COL_COUNT) - 1u;
-    cols_reset(S.out, DHTS_BEDGRAPH_COL_COUNT);
-    out->n_rows = nrows; out->n_cols = DHTS_BEDGRAPH_COL_COUNT; out->cols = S.out.data();
+    for (int i = 0; i < DHTS_BEDGRAPH_COL_COUNT; i++) dst[i] = nullptr;
     if (nrows > 0 && colmask) {
         for (int i = 0; i < DHTS_BEDGRAPH_COL_COUNT; i++)
             if ((colmask >> i) & 1u) { ENSURE(c, *bufs[i], (size_t)nrows * (size_t)bedgraph_col_kind(i) + 64); dst[i] = bufs[i]->p; }
@@ -159,10 +154,26 @@ int dhts_bam_bedgraph_next(dhts_ctx *c, int64_t max_rows, uint32_t colmask, dhts
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < DHTS_BEDGRAPH_COL_COUNT; i++) S.out[(size_t)i].fixed = dst[i];
     }
     S.o_next = pg.o; S.o_within = pg.within;
-    out->status = pg.o >= S.o_tid.size() ? 1 : 0;
+    *n_rows = nrows; *last = pg.o >= S.o_tid.size();
+    return 0;
+}
+
+int dhts_bam_bedgraph_next(dhts_ctx *c, int64_t max_rows, uint32_t colmask, dhts_bedgraph_batch *out) {
+    if (!c || !out) return -1;
+    memset(out, 0, sizeof(*out));
+    BedgraphState &S = c->bdg;
+    if (!S.open) return fail(c, "%s", BEDGRAPH_WHO.not_open);
+    HIPCHK(c, hipSetDevice(c->device));
+    void *dst[DHTS_BEDGRAPH_COL_COUNT]; int64_t nrows = 0; bool last = false;
+    colmask &= (1u << DHTS_BEDGRAPH_COL_COUNT) - 1u;
+    cols_reset(S.out, DHTS_BEDGRAPH_COL_COUNT);
+    out->n_cols = DHTS_BEDGRAPH_COL_COUNT; out->cols = S.out.data();
+    if (bedgraph_page(c, max_rows, colmask, dst, &nrows, &last)) return -1;
+    out->n_rows = nrows;
+    for (int i = 0; i < DHTS_BEDGRAPH_COL_COUNT; i++) S.out[(size_t)i].fixed = dst[i];
+    out->status = last ? 1 : 0;
     return 0;
 }
 

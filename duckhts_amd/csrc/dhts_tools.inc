@@ -2,14 +2,14 @@
 // bgzip / bgunzip / BGZF wrap.
 // ---- bgzip / bgunzip (src/bgzip.c: bgzf_write / bgzf_read loops, htslib bgzf.c) ----------------------------------------------------------
 static const uint8_t BGZF_EOF_BLOCK[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-// raw bytes already in z_in (n of them, padded) -> packed BGZF blocks in z_out; *out_len = their size
-static int bgzf_compress_device(dhts_ctx *c, uint64_t n, int level, uint64_t *out_len) {
+// raw bytes already in z_in (n of them, padded; `in`: where in z_in they start, null for its front) -> packed BGZF blocks in z_out; *out_len = their size
+static int bgzf_compress_device(dhts_ctx *c, uint64_t n, int level, uint64_t *out_len, const uint8_t *in = nullptr) {
     const int64_t nblk = (int64_t)((n + DFL_IN - 1) / DFL_IN);
     *out_len = 0;
     if (nblk == 0) return 0;
     ENSURE(c, c->z_slots, (size_t)nblk * DFL_SLOT + 64); ENSURE(c, c->z_sizes, (size_t)(nblk + 1) * 4 + 64); ENSURE(c, c->z_offs, (size_t)(nblk + 2) * 8 + 64);
     if (level != 0) ENSURE(c, c->z_tok, (size_t)nblk * DFL_IN * 4 + 64);                  // the parse of every block: one word per token
-    hipLaunchKernelGGL(bgzf_deflate_blocks, dim3((unsigned)nblk), dim3(64), DFL_LDS_BYTES, c->stream, (const uint8_t *)c->z_in.p, n, nblk, level, (uint8_t *)c->z_slots.p, (uint32_t *)c->z_sizes.p,
+    hipLaunchKernelGGL(bgzf_deflate_blocks, dim3((unsigned)nblk), dim3(64), DFL_LDS_BYTES, c->stream, in ? in : (const uint8_t *)c->z_in.p, n, nblk, level, (uint8_t *)c->z_slots.p, (uint32_t *)c->z_sizes.p,
                        (uint32_t *)c->z_tok.p);
     HIPCHK(c, hipGetLastError());
     const uint32_t *in1[1] = {(const uint32_t *)c->z_sizes.p}; uint64_t *o64[1] = {(uint64_t *)c->z_offs.p}; uint64_t total = 0;

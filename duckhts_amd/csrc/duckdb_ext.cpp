@@ -2,7 +2,7 @@
 //
 // The table functions live in the parts included below, one per reader family, over the shared helpers of duckdb_surface.h:
 //   duckdb_bam.inc read_bam, duckdb_bins.inc bam_bin_counts, duckdb_bedcov.inc bam_bedcov, duckdb_bcf.inc read_bcf, duckdb_seq.inc read_fastq / read_fasta, duckdb_interval.inc read_bed / fasta_nuc,
-//   duckdb_tabix.inc read_tabix / read_gtf / read_gff, duckdb_udf.inc the k-mer family, duckdb_bedgraph.inc bam_bedgraph, duckdb_depth_hist.inc bam_depth_hist; duckdb_tools.cpp (its own translation unit) the writers.
+//   duckdb_tabix.inc read_tabix / read_gtf / read_gff, duckdb_udf.inc the k-mer family, duckdb_bedgraph.inc bam_bedgraph, duckdb_depth_hist.inc bam_depth_hist, duckdb_bedgraph_export.inc bam_bedgraph_export; duckdb_tools.cpp (its own translation unit) the writers.
 // The htslib calls underneath are replaced by include/duckhts_amd.h (HIP kernels); DuckDB is reached only
 // through the function-pointer table returned by access->get_api(info, "v1.2.0").
 //
@@ -44,6 +44,7 @@ static double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); r
 #include "duckdb_pileup.inc"
 #include "duckdb_bedgraph.inc"
 #include "duckdb_depth_hist.inc"
+#include "duckdb_bedgraph_export.inc"
 #include "duckdb_tabix.inc"
 #include "duckdb_udf.inc"
 
@@ -86,6 +87,8 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     if (const char *e = getenv("DHTS_BEDGRAPH_FUNCTIONS")) if (atoi(e) == 1) register_bam_bedgraph_function(conn);
     // bam_depth_hist (the depth distribution per target row or contig) comes last, behind a variable of its own, DHTS_HIST_FUNCTIONS=1: no value of an existing variable changes its set
     if (const char *e = getenv("DHTS_HIST_FUNCTIONS")) if (atoi(e) == 1) register_bam_hist_function(conn);
+    // bam_bedgraph_export (the writer layer of PLAN.md 10.5.4 / 10.7.4 for bam_bedgraph) comes last, behind a variable of its own, DHTS_EXPORT_FUNCTIONS=1: no value of an existing variable changes its set
+    if (const char *e = getenv("DHTS_EXPORT_FUNCTIONS")) if (atoi(e) == 1) register_bedgraph_export_function(conn);
     API(void, duckdb_disconnect, duckdb_connection *)(&conn);
     return true;
 }

@@ -958,6 +958,48 @@ int dhts_bam_bedgraph_next(dhts_ctx *bam, int64_t max_rows, uint32_t colmask, dh
 uint64_t dhts_bam_bedgraph_batch_host_bytes(const dhts_bedgraph_batch *b);
 int dhts_bam_bedgraph_batch_fetch(dhts_ctx *bam, const dhts_bedgraph_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- bam_bedgraph_export ----------------------------------------------------------------------
+ * The result of bam_bedgraph written as a bgzipped bedGraph file (`chrom \t start \t end \t depth \n` per row, decimal, the contig by its name)
+ * with its tabix index -- mosdepth's per-base.bed.gz + .csi -- without a result row crossing PCIe: the pages of the result are printed on the
+ * device (csrc/rows_text.hip), compressed on the device (bgzip's encoder) and only the compressed bytes reach the host and the file.  It is the
+ * writer layer the reference plans (.github/PLAN.md, 10.5.4 / 10.7.4) for this one result; the reference has no code for it, so this is the
+ * specification.  (The entry is dhts_bedgraph_export: the dhts_bam_bedgraph_* names are the seven of the count function.)
+ *   Call it after dhts_bam_bedgraph_open and a scan (or any number of accumulates).  The rows are dhts_bam_bedgraph_next's, in its order.  On
+ *     return the paging state is as after an accumulate: the next dhts_bam_bedgraph_next returns page one.
+ *   The identity that defines correctness: the file's bytes equal what dhts_bgzip_file makes of the plain text of the same rows at the same
+ *     level, whatever the page size and the chunk size: blocks of 0xff00 bytes of the row stream, the last one short, then the EOF block.  This
+ *     holds because the encoder compresses every block on its own: a block's bytes depend on its 0xff00 input bytes and the level alone.
+ *   Parameters: level as dhts_bgzip_file (0 stores, every other value is the one compressing setting); index 0 none, 1 TBI (out_path + ".tbi"),
+ *     2 CSI (out_path + ".csi", min_shift <= 0: 14); overwrite 0 / 1.
+ *   Index: after the file is closed the existing tabix writer (dhts_tabix_build_index) reads it back through a scratch context on the same
+ *     device with the BED preset (0-based half-open, columns 1 / 2 / 3), and the index is wrapped by dhts_bgzf_wrap.  With an index and regions
+ *     the regions must keep each contig's rows together and ascending; without an index any region order is written as answered.
+ *   Empty result: the file is the 28-byte EOF block; the index is what dhts_tabix_build_index makes of that file: a valid index without a
+ *     sequence name, on which every region query finds no such sequence.
+ *   Returns 0, or: -1 a call in the wrong state, a parameter out of range or a device error; -3 an output cannot be opened; -5 write error;
+ *     -6 out_path exists and overwrite is 0 (the file is left alone); -7 the regions are not in file order; -8 the index could not be built.
+ *     Behind every failure but -6 neither output file is left.  dhts_error names the cause with the prefix "bam_bedgraph_export:".
+ *   With dhts_set_timing the count and emit kernels are timed as DHTS_K_SCAN, the encoder's lengths and carry as DHTS_K_BCF_MEASURE, its write
+ *     pass as DHTS_K_BCF_WRITE and the compressor as DHTS_K_HUFF.
+ *   Not in this contract: building the index from the row arrays without reading the file back; other results than bam_bedgraph's (the
+ *     encoder is generic over a name column and up to 8 integer columns; bam_bin_counts is to follow); .tsv.gz; several threads of file I/O. */
+typedef struct {
+    int32_t level;           /* as dhts_bgzip_file                                                            */
+    int32_t index;           /* 0 none, 1 TBI, 2 CSI                                                           */
+    int32_t min_shift;       /* CSI: <= 0 is 14                                                                */
+    int32_t overwrite;       /* 0 or 1                                                                         */
+    int32_t reserved[4];
+} dhts_bedgraph_export_params;
+typedef struct {
+    uint64_t n_rows;         /* rows written                                                                   */
+    uint64_t bytes_text;     /* bytes of their text                                                            */
+    uint64_t bytes_out;      /* bytes of the file, EOF block included                                          */
+    uint64_t bytes_index;    /* bytes of the index file, 0 without one                                         */
+    int32_t status;          /* the scan's, as in dhts_bedgraph_stats                                          */
+    int32_t reserved;
+} dhts_bedgraph_export_stats;
+int dhts_bedgraph_export(dhts_ctx *bam, const char *out_path, const dhts_bedgraph_export_params *p, dhts_bedgraph_export_stats *out);
+
 /* ---- bam_depth_hist ---------------------------------------------------------------------------
  * Per group of target rows and per depth: the number of positions on that depth -- mosdepth's *.dist.txt, the COV section of `samtools stats`,
  * "what fraction of the target is covered at >= 20x" -- binned on the device out of the depth table bam_depth's add pass fills in HBM.  The

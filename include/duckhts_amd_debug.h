@@ -58,6 +58,22 @@ int dhts_debug_deflate_codes(dhts_ctx *, const uint32_t *counts, uint32_t nsym, 
  * start at 0 (seed is unused) and return n + 1 elements, the total last.  host_v has room for n + 1 elements of every kind; element n is
  * uploaded as it is and must not change an answer. */
 int dhts_debug_carry(dhts_ctx *, int kind, void *host_v, uint64_t n, uint64_t seed);
+/* tests: the row-text encoder alone (csrc/rows_text.hip) on host arrays: a table of n_names names (names: the byte arena, name_offs:
+ * n_names + 1 offsets into it) and n_rows rows of tid (int32; outside the table: an empty name), start, end (int64) and depth (int32) -> the
+ * bytes `name \t start \t end \t depth \n` per row in out.  The text lies 5 bytes into the device buffer, so the write pass meets a span that
+ * is not 16-byte aligned.  Returns the bytes of the text (nothing is copied when cap is smaller), or -1 with dhts_error set. */
+int64_t dhts_debug_rows_text(dhts_ctx *, const uint8_t *names, const uint32_t *name_offs, int32_t n_names, const int32_t *tid, const int64_t *start, const int64_t *end,
+                             const int32_t *depth, int64_t n_rows, uint8_t *out, uint64_t cap);
+/* tests: the workgroups of the encoder's write pass that staged their rows in LDS (out2[0]) and that took the fallback for a span over the
+ * LDS budget (out2[1]) in the last dhts_debug_rows_text (an export does not count them) */
+int dhts_debug_rows_text_paths(dhts_ctx *, uint64_t out2[2]);
+/* tests, tools/bench_bedgraph_export.py: the form of the encoder's write pass on this context from the next call on: 0 the default (a workgroup
+ * stages its rows in LDS and stores aligned 16-byte pieces), 1 one lane per row storing byte by byte, the form the default is measured against
+ * (DESIGN.md 4r).  Any other value fails with a dhts_error. */
+int dhts_debug_rows_text_form(dhts_ctx *, int form);
+/* tests: the rows of a page and the blocks of a compressor launch dhts_bedgraph_export uses on this context (0: the defaults, 1,048,576
+ * rows and 4,096 blocks), so that a small file crosses pages and chunks */
+int dhts_debug_export_limits(dhts_ctx *, int64_t page_rows, int64_t chunk_blocks);
 /* tests: what the record stage's repair and retry paths did since the context was opened or rewound (host-side counters, read_bam and
  * read_bcf alike).  out[0] tiles changed by the repair rounds and by the sequential fallback, summed over rounds and batches;
  * out[1] repair rounds that changed a tile (the two rounds read_bam always queues count only when they repaired something, so a file that

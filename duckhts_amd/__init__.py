@@ -394,6 +394,7 @@ def lib():
         L.dhts_debug_rows_text_form.argtypes = [C.c_void_p, C.c_int]
         L.dhts_debug_pileup_add_form.argtypes = [C.c_void_p, C.c_int]
         L.dhts_debug_carry.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64]
+        L.dhts_debug_line_table.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int] + [C.c_void_p] * 5
         L.dhts_debug_hist_max_table_bytes.argtypes = [C.c_uint64]
         L.dhts_debug_hist_max_table_bytes.restype = None
         L.dhts_debug_hist_pass_ms.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -618,6 +619,22 @@ class Context:
         out[n] = 0 if kind == 2 else np.iinfo(a.dtype).max
         self._chk(self.L.dhts_debug_carry(self.h, kind, out.ctypes.data, n, seed))
         return out[:n] if kind == 2 else out
+
+    def debug_line_table(self, text, t0=0, open_last_ok=True, lim=None, tabs=False):
+        """the text readers' line table alone (dhts_debug_line_table) on `text`: a dict of the result's fields and the arrays line_off
+        (nlines + 1 starts) and, with tabs, tab_off, tab0 and has_nul; the arrays are empty when t0 lies at or behind the text's end"""
+        n = len(text)
+        src = np.frombuffer(bytes(text) + b"\0", np.uint8)
+        w = np.zeros(7, np.uint64)
+        a = [np.zeros(n + 2, np.uint32) for _ in range(4)]
+        self._chk(self.L.dhts_debug_line_table(self.h, src.ctypes.data, n, t0, int(bool(open_last_ok)), 0xffffffffffffffff if lim is None else lim, int(bool(tabs)),
+                                               w.ctypes.data, *[x.ctypes.data for x in a]))
+        out = dict(zip(("nl", "ntabs", "nlines", "last_start", "carry_start", "last_open", "finished"), (int(x) for x in w)))
+        nlines, made = out["nlines"], t0 < n
+        out["line_off"] = a[0][:nlines + 1 if made else 0]
+        if tabs:
+            out["tab_off"], out["tab0"], out["has_nul"] = a[1][:out["ntabs"]], a[2][:nlines + 1 if made else 0], a[3][:nlines]
+        return out
 
     def header(self):
         h = BamHeader()

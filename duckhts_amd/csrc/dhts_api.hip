@@ -180,12 +180,16 @@ struct FastaState {
     DevBuf text; uint64_t text_len = 0; bool text_ready = false;
     DevBuf o_noff, o_soff, o_name, o_seq, rg;
 };
+// the line table of a text (dhts_text_lines.inc): newlines per 4 KiB chunk, the chunks' bases, the lines' starts; with the tab part the same
+// for the tabs, the tabs in front of every line and the lines that hold a NUL
+struct LineBufs { DevBuf cnt, base, line_off; };
+struct TabBufs { DevBuf cnt, base, tab_off, tab0, has_nul; };
 // read_bed (bed_text.hip, dhts_bed_scan.inc): the projection, the region of a query, the delimiter table and the columns of the last batch
 struct BedState {
     bool open = false; std::vector<int32_t> proj; std::vector<dhts_col> out;
     int64_t lines_done = 0; int32_t status = 0;                   // lines in front of the next batch (the error's line number); the error the stream ended on
     bool rg_active = false, rg_all = false, rg_pending = false; std::string rg_tok, rg_name; int64_t rg_beg = 0, rg_end = 0; TbxConf conf = {0, 0, 0, 0, 0, 0}; DevBuf rg_name_dev, tbx;
-    DevBuf cnt_nl, cnt_tab, base_nl, base_tab, line_off, tab_off, tab0, has_nul, lend, ntab, is_row, rank, row_line, ctr;
+    LineBufs lines; TabBufs tabs; DevBuf lend, ntab, is_row, rank, row_line, ctr;
     DevBuf ival[BED_N_INT], ivalid[BED_N_INT], slen[BED_N_STR], soff[BED_N_STR], svalid[BED_N_STR], sbytes[BED_N_STR];
 };
 // read_tabix / read_gtf / read_gff (tabix_text.hip, dhts_tabix_scan.inc): the configuration and schema of bind, what is left of line_skip and
@@ -337,7 +341,8 @@ struct dhts_ctx {
     DevBuf f_len, f_flag, f_psum, f_rank, f_mark, f_next, f_plus, f_exit, f_entry, f_stop, f_isstart, f_recrank, f_recline;
     DevBuf v_pos_hi;                   // VCF text: the high words of the batch's 0-based positions (BcfStream::pos_hi)
     DevBuf v_keep, v_endsv; uint64_t proj_gen = 1, keep_gen = 0; int32_t keep_none = 0, fmt_none = 0; bool keep_all = true, fmt_keep_all = true; DevBuf v_fkeep;   // VCF text: the INFO keys the projection reads (VcfArgs::info_keep)
-    DevBuf v_cnt, v_base, v_line_off, v_rec_len, v_out, v_ctr, v_undef, v_patch, vd_ctg_off, vd_ctg_bytes, vd_ctg_id, vd_id_off, vd_id_bytes, vd_id_id, vd_id_typ, vd_id_ftyp, vd_ctg_hash, vd_id_hash, v_tok_off, v_tok_bytes, v_tok_bits;
+    LineBufs lines;                    // the line table of the batch (read_bcf on text, read_bam on SAM / FASTQ / FASTA text, fasta_index, the tabix index build)
+    DevBuf v_rec_len, v_out, v_ctr, v_undef, v_patch, vd_ctg_off, vd_ctg_bytes, vd_ctg_id, vd_id_off, vd_id_bytes, vd_id_id, vd_id_typ, vd_id_ftyp, vd_ctg_hash, vd_id_hash, v_tok_off, v_tok_bytes, v_tok_bits;
     uint32_t v_undef_cap = 65536, v_patch_cap = 1u << 20;      // entries the device may record per batch; grown (and the pass repeated) when a batch needs more
     uint32_t vd_ctg_hmask = 0, vd_id_hmask = 0;
     bool cache_hit = false; std::string pending_tag;       // the file's bytes came out of the pool (no read, no copy); tag to put on `comp` once staging has succeeded
@@ -468,8 +473,8 @@ static hipEvent_t ev_get(dhts_ctx *c) {
 }
 struct KTimer {
     dhts_ctx *c; int id; hipEvent_t a = nullptr, b = nullptr; hipStream_t s;
-    KTimer(dhts_ctx *c_, int id_, hipStream_t s_ = nullptr) : c(c_), id(id_), s(s_ ? s_ : c_->stream) { if (c->timing) { a = ev_get(c); b = ev_get(c); (void)hipEventRecord(a, s); } }
-    ~KTimer() { if (c->timing) { (void)hipEventRecord(b, s); c->pending.push_back({id, {a, b}}); } }
+    KTimer(dhts_ctx *c_, int id_, hipStream_t s_ = nullptr) : c(c_), id(id_), s(s_ ? s_ : c_->stream) { if (c->timing && id >= 0) { a = ev_get(c); b = ev_get(c); (void)hipEventRecord(a, s); } }   // (id < 0: times nothing)
+    ~KTimer() { if (c->timing && id >= 0) { (void)hipEventRecord(b, s); c->pending.push_back({id, {a, b}}); } }
 };
 static void timing_collect(dhts_ctx *c) {
     for (auto &p : c->pending) {
@@ -625,6 +630,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_tags.inc"
 #include "dhts_index_write.inc"
 #include "dhts_tools.inc"
+#include "dhts_text_lines.inc"
 #include "dhts_bam_join.inc"
 #include "dhts_bam_scan.inc"
 #include "dhts_sam_scan.inc"

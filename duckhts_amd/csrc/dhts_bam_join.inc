@@ -46,22 +46,16 @@ extern "C" int64_t dhts_bam_set_overlap_bed(dhts_ctx *c, const uint8_t *text, ui
     if (n && !text) return fail(c, "overlap bed: null text");
     if (n >= 0xfffffff0ull) return fail(c, "overlap bed: text of 4 GiB or more");
     if (n == 0) return 0;
-    DevBuf d_text, d_cnt, d_base, d_off, d_rows;
+    DevBuf d_text, d_rows; LineBufs lines;                                      // (buffers of its own: the context's belong to its scan)
     ENSURE(c, d_text, n + 64);
     HIPCHK(c, hipMemcpyAsync(d_text.p, text, n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync((uint8_t *)d_text.p + n, 0, 64, c->stream));
     const uint8_t *u = (const uint8_t *)d_text.p;
-    const int64_t nchunks = (int64_t)((n + VCF_CHUNK - 1) / VCF_CHUNK);
-    ENSURE(c, d_cnt, (size_t)nchunks * 4 + 64); ENSURE(c, d_base, (size_t)(nchunks + 1) * 4 + 64);
-    hipLaunchKernelGGL(vcf_line_count, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, (uint64_t)0, n, (uint32_t *)d_cnt.p, nchunks);
-    const uint32_t *kin[1] = {(const uint32_t *)d_cnt.p}; uint32_t *kout[1] = {(uint32_t *)d_base.p}; uint64_t nl = 0;
-    if (run_scan(c, 1, kin, kout, nullptr, nchunks, &nl)) return -1;
-    ENSURE(c, d_off, (size_t)(nl + 2) * 4 + 64);
-    hipLaunchKernelGGL(vcf_line_fill, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, (uint64_t)0, n, (const uint32_t *)d_base.p, (uint32_t *)d_off.p, nchunks);
-    int64_t nlines = (int64_t)nl; int last_open = 0;
-    if (text[n - 1] != '\n') { nlines++; last_open = 1; }
+    LineTab T;                                                                  // the text is whole: its last line counts when it has no newline
+    if (line_table(c, lines, nullptr, u, 0, n, text[n - 1] != '\n', ~0ull, -1, T)) return -1;
+    const int64_t nlines = T.nlines; const int last_open = T.last_open;      // (n > 0: at least one line)
     ENSURE(c, d_rows, (size_t)nlines * sizeof(TbxLine) + 64);
-    hipLaunchKernelGGL(bed_intervals, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, c->stream, u, (const uint32_t *)d_off.p, nlines, n, last_open, (TbxLine *)d_rows.p);
+    hipLaunchKernelGGL(bed_intervals, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, c->stream, u, (const uint32_t *)lines.line_off.p, nlines, n, last_open, (TbxLine *)d_rows.p);
     HIPCHK(c, hipGetLastError());
     std::vector<TbxLine> rows((size_t)nlines);
     HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows.p, (size_t)nlines * sizeof(TbxLine), hipMemcpyDeviceToHost, c->stream));

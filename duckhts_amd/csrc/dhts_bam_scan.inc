@@ -7,6 +7,8 @@ struct Batch {
     bool status_pending = false;      // the blocks' status words have not been looked at yet (batch_status_resolve)
 };
 static const uint32_t NONE32 = 0xffffffffu;
+// the end of the batch is the end of an undamaged file: what lies behind its last newline is the file's last line (set by batch_begin)
+static bool batch_clean_end(const dhts_ctx *c, const Batch &B) { return B.final_batch && !c->gz_error && !B.blk_err; }
 // where the batch lies: the carry in front, then blocks [B.b0, B.b0 + B.nb) as the block table places them NOW.  Sets B.carry / ulen / out_base / u
 // and grows the stream buffer (the carry bytes at its front are kept).  Called again when the table moved under a batch (a scratch retry).
 static int batch_place(dhts_ctx *c, Batch &B) {
@@ -200,25 +202,15 @@ extern "C" int64_t dhts_tabix_build_index(dhts_ctx *c, int preset, int sc, int b
         Batch B;
         if (batch_begin(c, 0, B)) return -1;
         const uint8_t *u = B.u; const uint64_t ulen = B.ulen, out_base = B.out_base;
-        uint64_t carry_start = ulen; int64_t nlines = 0; int last_open = 0;
-        if (ulen > 0) {
-            const int64_t nchunks = (int64_t)((ulen + VCF_CHUNK - 1) / VCF_CHUNK);
-            ENSURE(c, c->v_cnt, (size_t)nchunks * 4 + 64); ENSURE(c, c->v_base, (size_t)(nchunks + 1) * 4 + 64);
-            hipLaunchKernelGGL(vcf_line_count, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, (uint64_t)0, ulen, (uint32_t *)c->v_cnt.p, nchunks);
-            const uint32_t *kin[1] = {(const uint32_t *)c->v_cnt.p}; uint32_t *kout[1] = {(uint32_t *)c->v_base.p}; uint64_t nl = 0;
-            if (run_scan(c, 1, kin, kout, nullptr, nchunks, &nl)) return -1;
-            if (nl + 2 >= (1ull << 32)) return fail(c, "batch too large");
-            ENSURE(c, c->v_line_off, (size_t)(nl + 2) * 4 + 64);
-            hipLaunchKernelGGL(vcf_line_fill, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, (uint64_t)0, ulen, (const uint32_t *)c->v_base.p, (uint32_t *)c->v_line_off.p, nchunks);
-            lo.resize((size_t)nl + 2);
-            HIPCHK(c, hipMemcpyAsync(lo.data(), c->v_line_off.p, (size_t)(nl + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            nlines = (int64_t)nl; carry_start = lo[nl];
-            if (B.final_batch && lo[nl] < ulen) { nlines++; last_open = 1; carry_start = ulen; lo[nl + 1] = (uint32_t)ulen; }
-        }
+        // (its own rule for the open last line: B.final_batch alone.  It differs from batch_clean_end in B.blk_err only -- gz_error cannot be set
+        // on a BGZF file -- and a damaged block fails the build behind this batch either way; the cut line in front of it is parsed first)
+        LineTab T;
+        if (line_table(c, c->lines, nullptr, u, 0, ulen, B.final_batch, ~0ull, -1, T)) return -1;
+        const uint64_t carry_start = T.carry_start; const int64_t nlines = T.nlines; const int last_open = T.last_open;
+        if (nlines > 0 && line_starts_fetch(c, c->lines, T.nl + 1, lo)) return -1;
         if (nlines > 0) {
             ENSURE(c, c->v_undef, (size_t)nlines * sizeof(TbxLine) + 64);
-            hipLaunchKernelGGL(tabix_intervals, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, c->stream, u, (const uint32_t *)c->v_line_off.p, nlines, ulen, last_open, cf, (TbxLine *)c->v_undef.p);
+            hipLaunchKernelGGL(tabix_intervals, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, c->stream, u, (const uint32_t *)c->lines.line_off.p, nlines, ulen, last_open, cf, (TbxLine *)c->v_undef.p);
             rows.resize((size_t)nlines);
             HIPCHK(c, hipMemcpyAsync(rows.data(), c->v_undef.p, (size_t)nlines * sizeof(TbxLine), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -446,7 +438,6 @@ static int rows_queue(dhts_ctx *c, const BamStream &st, int64_t ntiles, const Ti
 
 static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask, dhts_bam_batch *out);
 static int sam_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, uint64_t &enc_len, int64_t &nrec, uint64_t &carry_start, bool &rejected, uint64_t &t0);
-static int sam_line_start(dhts_ctx *c, int64_t i, uint64_t &off);
 static int fastq_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, uint64_t &enc_len, int64_t &nrec, uint64_t &carry_start, bool &rejected, uint64_t &t0);
 static int fastq_record_start(dhts_ctx *c, int64_t i, uint64_t &off);
 int dhts_bam_next_batch(dhts_ctx *c, int64_t max_blocks, uint32_t colmask, dhts_bam_batch *out) {
@@ -456,13 +447,7 @@ int dhts_bam_next_batch(dhts_ctx *c, int64_t max_blocks, uint32_t colmask, dhts_
         if (bam_next_batch_one(c, max_blocks, colmask, out)) return -1;
         c->last_batch_rows = out->n_rows; c->last_batch_first = out->first_rec_uoff;
         // a region query with several index windows: the end of one window is the start of the next, not the end of the scan
-        if (out->status == 1 && c->win_cur + 1 < c->wins.size()) {
-            enter_window(c, c->win_cur + 1);
-            discard_prefetch(c);
-            c->next_block = c->shard_b0; c->carry_len = 0; c->stream_done = false; c->first_batch = true; c->ucur = 0;
-            out->status = 0;
-            if (out->n_rows == 0) continue;
-        }
+        if (next_window(c, out->status) && out->n_rows == 0) continue;
         return 0;
     }
 }
@@ -885,7 +870,7 @@ static int bam_next_batch_one(dhts_ctx *c, int64_t max_blocks, uint32_t colmask,
     if (bam_overlap_join(c, st, bc, nrows, out)) return -1;
     if (c->sam_text) {
         // back to text offsets: the carry starts at the first line that was not encoded, or at the line of a record bam_read1's checks refuse
-        if (rec_err || nrows < sam_nrec) { rec_err = true; if (c->fastq ? fastq_record_start(c, nrows, carry_start) : sam_line_start(c, nrows, carry_start)) return -1; }
+        if (rec_err || nrows < sam_nrec) { rec_err = true; if (c->fastq ? fastq_record_start(c, nrows, carry_start) : line_start(c, c->lines, nrows, carry_start)) return -1; }
         else { carry_start = sam_carry; rec_err = sam_rej; }
         have_first_rec = true; first_rec_rel = (uint32_t)sam_t0;
     }

@@ -235,8 +235,8 @@ static int vcf_text_records(dhts_ctx *c, const Batch &B, BcfStream &st, int64_t 
                             uint64_t lim, bool &finished) {
     const uint8_t *u = B.u; const uint64_t ulen = B.ulen, out_base = B.out_base;
     uint64_t t0 = 0;
-    if (c->first_batch && c->shard_rank == 0) { if (c->scan_first_uoff < out_base) return fail(c, "internal: header beyond first batch"); t0 = c->scan_first_uoff - out_base; }
-    else if (c->first_batch) {
+    if (!c->first_batch || c->shard_rank == 0) { if (!first_line_t0(c, out_base, t0)) return fail(c, "internal: header beyond first batch"); }
+    else {
         // a block-range shard that starts inside the file owns the lines that START at or behind its first block: lines synchronise on the
         // newline, so the start is the byte behind the first newline at or after (shard start - 1); the batch begins one block early for that byte
         const uint64_t U0 = c->h_uoff[c->shard_b0];
@@ -258,29 +258,12 @@ static int vcf_text_records(dhts_ctx *c, const Batch &B, BcfStream &st, int64_t 
         if (c->scan_end_uoff < end_abs) end_abs = c->scan_end_uoff;
         if (out_base + t0 >= end_abs) { finished = true; carry_start = t0 < ulen ? t0 : ulen; return 0; }
     }
-    if (t0 >= ulen) { carry_start = ulen; return 0; }
-    const int64_t nchunks = (int64_t)((ulen - (t0 & ~(uint64_t)15) + VCF_CHUNK - 1) / VCF_CHUNK);
-    ENSURE(c, c->v_cnt, (size_t)nchunks * 4 + 64); ENSURE(c, c->v_base, (size_t)(nchunks + 1) * 4 + 64);
-    hipLaunchKernelGGL(vcf_line_count, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, t0, ulen, (uint32_t *)c->v_cnt.p, nchunks);
-    const uint32_t *kin[1] = {(const uint32_t *)c->v_cnt.p}; uint32_t *kout[1] = {(uint32_t *)c->v_base.p}; uint64_t nl = 0;
-    if (run_scan(c, 1, kin, kout, nullptr, nchunks, &nl)) return -1;
-    if (nl + 2 >= (1ull << 32)) return fail(c, "batch too large");
-    ENSURE(c, c->v_line_off, (size_t)(nl + 2) * 4 + 64);
-    hipLaunchKernelGGL(vcf_line_fill, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, t0, ulen, (const uint32_t *)c->v_base.p, (uint32_t *)c->v_line_off.p, nchunks);
-    uint32_t last_start = 0;
-    HIPCHK(c, hipMemcpyAsync(&last_start, (const uint32_t *)c->v_line_off.p + nl, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int64_t nlines = (int64_t)nl; int last_open = 0;
-    carry_start = last_start;
-    if (B.final_batch && last_start < ulen && !c->gz_error) { nlines++; last_open = 1; carry_start = ulen; }     // the last line of the file need not end in a newline (behind a failed gzip stream it is a line the reader never saw whole)
-    if (lim < ulen) {
-        std::vector<uint32_t> lo_(nlines + 1);
-        HIPCHK(c, hipMemcpy(lo_.data(), c->v_line_off.p, (size_t)(nl + 1) * 4, hipMemcpyDeviceToHost));
-        int64_t lo = 0, hi = nlines;                                                            // first line that starts at or behind lim
-        while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (lo_[mid] < lim) lo = mid + 1; else hi = mid; }
-        if (lo < nlines) { finished = true; carry_start = lo_[lo]; nlines = lo; last_open = 0; }
-        else if (carry_start >= lim) finished = true;
-    }
+    // (differs from batch_clean_end: B.blk_err is not looked at, so the cut line in front of a damaged BGZF block counts as well -- only a
+    // failed gzip stream drops it, as a line the reader never saw whole; DESIGN.md 4s)
+    LineTab T;
+    if (line_table(c, c->lines, nullptr, u, t0, ulen, B.final_batch && !c->gz_error, lim, -1, T)) return -1;
+    int64_t nlines = T.nlines; const int last_open = T.last_open;
+    carry_start = T.carry_start; if (T.finished) finished = true;
     if (nlines == 0) return 0;
     ENSURE(c, c->v_rec_len, (size_t)(nlines + 1) * 4 + 64); ENSURE(c, c->b_rec_off, (size_t)(nlines + 1) * 4 + 64); ENSURE(c, c->v_ctr, 64);
     if (const char *e = getenv("DHTS_VCF_CAPS")) { const uint32_t v = (uint32_t)atoi(e); if (v > 0 && c->v_undef_cap == 65536 && c->v_patch_cap == (1u << 20)) c->v_undef_cap = c->v_patch_cap = v; }   // (tests: small caps make the growth path cheap to reach)
@@ -300,7 +283,7 @@ static int vcf_text_records(dhts_ctx *c, const Batch &B, BcfStream &st, int64_t 
         return 0;
     };
     VcfArgs a; memset(&a, 0, sizeof(a));
-    a.u = u; a.line_off = (const uint32_t *)c->v_line_off.p; a.nlines = nlines; a.text_end = ulen; a.last_open = last_open;
+    a.u = u; a.line_off = (const uint32_t *)c->lines.line_off.p; a.nlines = nlines; a.text_end = ulen; a.last_open = last_open;
     a.n_smp = (int32_t)c->bh.samples.size(); a.v44 = c->bh.version >= 4004000 ? 1 : 0;
     {
         // LDS a workgroup of the lane-per-line encoder stages its 64 lines in: what the batch's lines need (average line x 64, half as much again, in
@@ -491,7 +474,7 @@ static int vcf_text_records(dhts_ctx *c, const Batch &B, BcfStream &st, int64_t 
         hipLaunchKernelGGL(vcf_scatter_words, dim3((np + 255) / 256), dim3(256), 0, c->stream, (uint8_t *)c->v_out.p, (const VcfPatch *)c->v_patch.p, (const uint32_t *)c->v_tok_bits.p, np);
         HIPCHK(c, hipStreamSynchronize(c->stream));          // (`words` is pageable host memory: the copy must have left it before it goes out of scope)
     }
-    HIPCHK(c, hipMemcpyAsync(&rec0_text, c->v_line_off.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&rec0_text, c->lines.line_off.p, 4, hipMemcpyDeviceToHost, c->stream));
     st.u = (const uint8_t *)c->v_out.p; st.ulen = total; st.pos_hi = (const int32_t *)c->v_pos_hi.p;
     st.n_ctg = (int32_t)c->bh.ctg.size(); st.n_ids = (int32_t)c->bh.ids.size();
     st.ctg_ok = (const uint8_t *)c->d_ctg_ok.p; st.id_ok = (const uint8_t *)c->d_id_ok.p; st.info_slot = (const int16_t *)c->d_info_slot.p; st.fmt_slot = (const int16_t *)c->d_fmt_slot.p;
@@ -515,13 +498,7 @@ int dhts_bcf_next_batch(dhts_ctx *c, int64_t max_blocks, dhts_bcf_batch *out) {
     for (;;) {
         if (bcf_next_batch_one(c, max_blocks, out)) return -1;
         // a region query with several index windows: the end of one window is the start of the next, not the end of the scan
-        if (out->status == 1 && c->win_cur + 1 < c->wins.size()) {
-            enter_window(c, c->win_cur + 1);
-            discard_prefetch(c);
-            c->next_block = c->shard_b0; c->carry_len = 0; c->stream_done = false; c->first_batch = true; c->ucur = 0;
-            out->status = 0;
-            if (out->n_rows == 0) continue;
-        }
+        if (next_window(c, out->status) && out->n_rows == 0) continue;
         return 0;
     }
 }

@@ -134,60 +134,20 @@ int dhts_bed_region_segments(dhts_ctx *c, const char *region, const void *index_
     return text_region_segments(c, "read_bed", region, index_bytes, n, beg, end, cap, count);
 }
 
-// The delimiter table of a batch (bed_text.hip) in c->bed's buffers, for read_bed and read_tabix: the lines that belong to this batch's scan
-// range (a window of a region query ends inside a block), where the carry begins, whether the range ends here.
-struct LineTab { uint64_t carry_start = 0; int64_t nlines = 0; int last_open = 0; bool finished = false; };
+// The delimiter table of a batch (line_table with the tab part, dhts_text_lines.inc) in c->bed's buffers, for read_bed and read_tabix: the
+// lines that belong to this batch's scan range (a window of a region query ends inside a block), where the carry begins, whether the range
+// ends here.
 static int text_line_table(dhts_ctx *c, const Batch &B, LineTab &T) {
     BedState &S = c->bed;
-    const uint8_t *u = B.u; const uint64_t ulen = B.ulen, out_base = B.out_base;
+    const uint64_t ulen = B.ulen, out_base = B.out_base;
     uint64_t t0 = 0;
-    if (c->first_batch) { if (c->scan_first_uoff < out_base) return fail(c, "internal: window start in front of its first batch"); t0 = c->scan_first_uoff - out_base; }
+    if (!first_line_t0(c, out_base, t0)) return fail(c, "internal: window start in front of its first batch");
     // the scan range ends with its last block or, for an index window, exactly at the window's end (windows are disjoint)
     uint64_t end_abs = B.sharded_tail ? c->h_uoff[c->shard_b1] : ~0ull;
     if (c->scan_end_uoff < end_abs) end_abs = c->scan_end_uoff;
     const uint64_t lim = (end_abs != ~0ull && out_base + ulen > end_abs) ? end_abs - out_base : ~0ull;
-    bool finished = false; uint64_t carry_start = t0 < ulen ? t0 : ulen; int64_t nlines = 0; int last_open = 0;
-    if (c->first_batch && out_base + t0 >= end_abs) finished = true;
-    if (!finished && t0 < ulen) {
-        const uint64_t a0 = t0 & ~(uint64_t)15;
-        const int64_t nchunks = (int64_t)((ulen - a0 + VCF_CHUNK - 1) / VCF_CHUNK);
-        ENSURE(c, S.cnt_nl, (size_t)nchunks * 4 + 64); ENSURE(c, S.cnt_tab, (size_t)nchunks * 4 + 64); ENSURE(c, S.base_nl, (size_t)(nchunks + 1) * 4 + 64); ENSURE(c, S.base_tab, (size_t)(nchunks + 1) * 4 + 64);
-        uint64_t tot[2] = {0, 0};
-        {
-            KTimer tm(c, DHTS_K_TILES);
-            hipLaunchKernelGGL(bed_delim_count, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, t0, ulen, (uint32_t *)S.cnt_nl.p, (uint32_t *)S.cnt_tab.p);
-            const uint32_t *kin[2] = {(const uint32_t *)S.cnt_nl.p, (const uint32_t *)S.cnt_tab.p}; uint32_t *kout[2] = {(uint32_t *)S.base_nl.p, (uint32_t *)S.base_tab.p};
-            if (run_scan(c, 2, kin, kout, nullptr, nchunks, tot)) return -1;
-        }
-        const uint64_t nl = tot[0], ntabs = tot[1];
-        ENSURE(c, S.line_off, (size_t)(nl + 2) * 4 + 64); ENSURE(c, S.tab0, (size_t)(nl + 2) * 4 + 64); ENSURE(c, S.has_nul, (size_t)(nl + 2) * 4 + 64); ENSURE(c, S.tab_off, (size_t)(ntabs + 1) * 4 + 64);
-        HIPCHK(c, hipMemsetAsync(S.has_nul.p, 0, (size_t)(nl + 2) * 4, c->stream));
-        uint32_t last_start = 0;
-        {
-            KTimer tm(c, DHTS_K_TILES);
-            hipLaunchKernelGGL(bed_delim_fill, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, t0, ulen, (const uint32_t *)S.base_nl.p, (const uint32_t *)S.base_tab.p,
-                               (uint32_t *)S.line_off.p, (uint32_t *)S.tab_off.p, (uint32_t *)S.tab0.p, (uint32_t *)S.has_nul.p, (uint32_t)(nl + 2));
-        }
-        HIPCHK(c, hipMemcpyAsync(&last_start, (const uint32_t *)S.line_off.p + nl, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        nlines = (int64_t)nl; carry_start = last_start;
-        const bool clean_end = B.final_batch && !c->gz_error && !B.blk_err;     // the end of the batch is the end of an undamaged file
-        if (clean_end && last_start < ulen) {                                  // a last line without a newline is a line
-            const uint32_t nt32 = (uint32_t)ntabs;
-            HIPCHK(c, hipMemcpy((uint32_t *)S.tab0.p + nl + 1, &nt32, 4, hipMemcpyHostToDevice));
-            nlines++; last_open = 1; carry_start = ulen;
-        }
-        if (lim < ulen) {                                                      // lines that start at or behind the window's end are not this window's
-            std::vector<uint32_t> lo_((size_t)nl + 1);
-            HIPCHK(c, hipMemcpy(lo_.data(), S.line_off.p, (size_t)(nl + 1) * 4, hipMemcpyDeviceToHost));
-            int64_t lo = 0, hi = nlines;
-            while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (lo_[(size_t)mid] < lim) lo = mid + 1; else hi = mid; }
-            if (lo < nlines) { finished = true; carry_start = lo_[(size_t)lo]; nlines = lo; last_open = 0; }
-            else if (carry_start >= lim) finished = true;
-        }
-    }
-    T.carry_start = carry_start; T.nlines = nlines; T.last_open = last_open; T.finished = finished;
-    return 0;
+    if (c->first_batch && out_base + t0 >= end_abs) { T = LineTab(); T.carry_start = t0 < ulen ? t0 : ulen; T.finished = true; return 0; }
+    return line_table(c, S.lines, &S.tabs, B.u, t0, ulen, batch_clean_end(c, B), lim, DHTS_K_TILES, T);
 }
 
 static int bed_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *out) {
@@ -213,7 +173,7 @@ static int bed_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *o
         ENSURE(c, S.lend, ln); ENSURE(c, S.ntab, ln); ENSURE(c, S.is_row, ln); ENSURE(c, S.rank, ln); ENSURE(c, S.ctr, 64);
         const bool by_region = S.rg_active && !S.rg_all;
         BedLines a; memset(&a, 0, sizeof(a));
-        a.u = u; a.line_off = (const uint32_t *)S.line_off.p; a.tab_off = (const uint32_t *)S.tab_off.p; a.tab0 = (const uint32_t *)S.tab0.p; a.has_nul = (const uint32_t *)S.has_nul.p;
+        a.u = u; a.line_off = (const uint32_t *)S.lines.line_off.p; a.tab_off = (const uint32_t *)S.tabs.tab_off.p; a.tab0 = (const uint32_t *)S.tabs.tab0.p; a.has_nul = (const uint32_t *)S.tabs.has_nul.p;
         a.nlines = (uint32_t)nlines; a.text_end = (uint32_t)ulen; a.last_open = last_open; a.report_bad = by_region ? 0 : 1;
         a.lend = (uint32_t *)S.lend.p; a.ntab = (uint32_t *)S.ntab.p; a.is_row = (uint32_t *)S.is_row.p; a.first_bad = (unsigned long long *)S.ctr.p;
         const unsigned lgrid = (unsigned)((nlines + 255) / 256);
@@ -226,7 +186,7 @@ static int bed_next_batch_one(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *o
                 // hts_itr_next's test on the interval tbx_parse1 gives the line under the index's configuration; a line tabix passes over or
                 // cannot parse is no row of the query
                 ENSURE(c, S.tbx, (size_t)nlines * sizeof(TbxLine) + 64);
-                hipLaunchKernelGGL(tabix_intervals, dim3(lgrid), dim3(256), 0, c->stream, u, (const uint32_t *)S.line_off.p, nlines, ulen, (int32_t)last_open, S.conf, (TbxLine *)S.tbx.p);
+                hipLaunchKernelGGL(tabix_intervals, dim3(lgrid), dim3(256), 0, c->stream, u, (const uint32_t *)S.lines.line_off.p, nlines, ulen, (int32_t)last_open, S.conf, (TbxLine *)S.tbx.p);
                 hipLaunchKernelGGL(bed_region_keep, dim3(lgrid), dim3(256), 0, c->stream, u, (const TbxLine *)S.tbx.p, (uint32_t)nlines, (const uint8_t *)S.rg_name_dev.p, (uint32_t)S.rg_name.size(),
                                    (long long)S.rg_beg, (long long)S.rg_end, (uint32_t *)S.is_row.p, (unsigned long long *)S.ctr.p);
             }
@@ -301,13 +261,7 @@ int dhts_bed_next_batch(dhts_ctx *c, int64_t max_blocks, dhts_bed_batch *out) {
     for (;;) {
         if (bed_next_batch_one(c, max_blocks, out)) return -1;
         // several index windows: the end of one window is the start of the next, not the end of the scan
-        if (out->status == 1 && c->win_cur + 1 < c->wins.size()) {
-            enter_window(c, c->win_cur + 1);
-            discard_prefetch(c);
-            c->next_block = c->shard_b0; c->carry_len = 0; c->stream_done = false; c->first_batch = true; c->ucur = 0;
-            out->status = 0;
-            if (out->n_rows == 0) continue;
-        }
+        if (next_window(c, out->status) && out->n_rows == 0) continue;
         return 0;
     }
 }
@@ -333,28 +287,18 @@ int64_t dhts_debug_bed_walk(dhts_ctx *c, double *ms_line_table, double *ms_walk)
         Batch B;
         if (batch_begin(c, 0, B)) return -1;
         const uint8_t *u = B.u; const uint64_t ulen = B.ulen;
-        uint64_t carry_start = ulen; int64_t nlines = 0; int last_open = 0;
-        if (ulen > 0) {
-            const int64_t nchunks = (int64_t)((ulen + VCF_CHUNK - 1) / VCF_CHUNK);
-            ENSURE(c, c->v_cnt, (size_t)nchunks * 4 + 64); ENSURE(c, c->v_base, (size_t)(nchunks + 1) * 4 + 64);
-            HIPCHK(c, hipEventRecord(e[0], c->stream));
-            hipLaunchKernelGGL(vcf_line_count, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, (uint64_t)0, ulen, (uint32_t *)c->v_cnt.p, nchunks);
-            const uint32_t *kin[1] = {(const uint32_t *)c->v_cnt.p}; uint32_t *kout[1] = {(uint32_t *)c->v_base.p}; uint64_t nl = 0;
-            if (run_scan(c, 1, kin, kout, nullptr, nchunks, &nl)) return -1;
-            ENSURE(c, c->v_line_off, (size_t)(nl + 2) * 4 + 64);
-            hipLaunchKernelGGL(vcf_line_fill, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, (uint64_t)0, ulen, (const uint32_t *)c->v_base.p, (uint32_t *)c->v_line_off.p, nchunks);
-            HIPCHK(c, hipEventRecord(e[1], c->stream));
-            uint32_t last_start = 0;
-            HIPCHK(c, hipMemcpyAsync(&last_start, (const uint32_t *)c->v_line_off.p + nl, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            nlines = (int64_t)nl; carry_start = last_start;
-            if (B.final_batch && last_start < ulen) { nlines++; last_open = 1; carry_start = ulen; }
-            float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e[0], e[1])); t_tab += ms;
-        }
+        // (its own rule for the open last line: the end of the file alone, whatever the stream ended on -- it differs from batch_clean_end)
+        LineTab T;
+        HIPCHK(c, hipEventRecord(e[0], c->stream));
+        if (line_table(c, c->lines, nullptr, u, 0, ulen, B.final_batch, ~0ull, -1, T)) return -1;
+        HIPCHK(c, hipEventRecord(e[1], c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        { float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e[0], e[1])); t_tab += ms; }
+        const uint64_t carry_start = T.carry_start; const int64_t nlines = T.nlines; const int last_open = T.last_open;
         if (nlines > 0) {
             ENSURE(c, c->bed.tbx, (size_t)nlines * sizeof(TbxLine) + 64);
             HIPCHK(c, hipEventRecord(e[1], c->stream));
-            hipLaunchKernelGGL(bed_intervals, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, c->stream, u, (const uint32_t *)c->v_line_off.p, nlines, ulen, (int32_t)last_open, (TbxLine *)c->bed.tbx.p);
+            hipLaunchKernelGGL(bed_intervals, dim3((unsigned)((nlines + 255) / 256)), dim3(256), 0, c->stream, u, (const uint32_t *)c->lines.line_off.p, nlines, ulen, (int32_t)last_open, (TbxLine *)c->bed.tbx.p);
             HIPCHK(c, hipEventRecord(e[2], c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e[1], e[2])); t_walk += ms;

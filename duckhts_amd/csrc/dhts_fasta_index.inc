@@ -65,37 +65,28 @@ extern "C" int64_t dhts_fasta_build_index(dhts_ctx *c) {
         const uint8_t *u = B.u; const uint64_t ulen = B.ulen, out_base = B.out_base;
         uint64_t lines_end = ulen;
         if (ulen > 0) {
-            const int64_t nchunks = (int64_t)((ulen + FA_CHUNK - 1) / FA_CHUNK);
-            ENSURE(c, c->v_cnt, (size_t)nchunks * 4 + 64); ENSURE(c, c->v_base, (size_t)(nchunks + 1) * 4 + 64);
-            hipLaunchKernelGGL(vcf_line_count, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, (uint64_t)0, ulen, (uint32_t *)c->v_cnt.p, nchunks);
-            const uint32_t *kin[1] = {(const uint32_t *)c->v_cnt.p}; uint32_t *kout[1] = {(uint32_t *)c->v_base.p}; uint64_t nl = 0;
-            if (run_scan(c, 1, kin, kout, nullptr, nchunks, &nl)) return -1;
-            ENSURE(c, c->v_line_off, (size_t)(nl + 2) * 4 + 64);
-            hipLaunchKernelGGL(vcf_line_fill, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, (uint64_t)0, ulen, (const uint32_t *)c->v_base.p, (uint32_t *)c->v_line_off.p, nchunks);
-            uint32_t last_start = 0;
-            HIPCHK(c, hipMemcpyAsync(&last_start, (const uint32_t *)c->v_line_off.p + nl, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            int64_t nlines = (int64_t)nl; lines_end = last_start; bool open_last = false;
-            if (B.final_batch && last_start < ulen) {                           // the last line of the file need not end in a newline; it counts one byte more all the same (faidx.c:260)
-                const uint32_t end1 = (uint32_t)ulen + 1;
-                HIPCHK(c, hipMemcpy((uint32_t *)c->v_line_off.p + nl + 1, &end1, 4, hipMemcpyHostToDevice));
-                nlines++; lines_end = ulen; open_last = true;
-            }
+            const int64_t nchunks = (int64_t)((ulen + FA_CHUNK - 1) / FA_CHUNK);      // (the line table's chunks from 0: FA_CHUNK is VCF_CHUNK by definition, fasta_index.hip)
+            // the last line of the file need not end in a newline; it counts one byte more all the same (faidx.c:260).  batch_clean_end is
+            // B.final_batch here: a damaged block has returned above, and plain gzip, which alone sets gz_error, was refused before the scan
+            LineTab T;
+            if (line_table(c, c->lines, nullptr, u, 0, ulen, batch_clean_end(c, B), ~0ull, -1, T)) return -1;
+            const uint64_t nl = T.nl; const int64_t nlines = T.nlines; const bool open_last = T.last_open != 0;
+            lines_end = T.carry_start;
             if (nlines > 0) {
                 const size_t ln = (size_t)(nlines + 2) * 4 + 64; const unsigned lgrid = (unsigned)((nlines + 255) / 256);
                 ENSURE(c, F.gtmp, ln); ENSURE(c, F.cls, (size_t)nlines + 2 + 64); ENSURE(c, F.gchunk, (size_t)nchunks * 4 + 64); ENSURE(c, F.gbase, (size_t)(nchunks + 1) * 4 + 64);
                 ENSURE(c, F.cl, ln); ENSURE(c, F.flag, ln); ENSURE(c, F.csum, ln); ENSURE(c, F.hrank, ln); ENSURE(c, F.err, 64);
-                hipLaunchKernelGGL(fa_chunk_props, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, ulen, (const uint32_t *)c->v_base.p, (uint32_t *)F.gtmp.p, (uint32_t *)F.gchunk.p, (uint8_t *)F.cls.p);
+                hipLaunchKernelGGL(fa_chunk_props, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, ulen, (const uint32_t *)c->lines.base.p, (uint32_t *)F.gtmp.p, (uint32_t *)F.gchunk.p, (uint8_t *)F.cls.p);
                 const uint32_t *gin[1] = {(const uint32_t *)F.gchunk.p}; uint32_t *gout[1] = {(uint32_t *)F.gbase.p}; uint64_t gtotal = 0;
                 if (run_scan(c, 1, gin, gout, nullptr, nchunks, &gtotal)) return -1;
-                hipLaunchKernelGGL(fa_line_cl, dim3(lgrid), dim3(256), 0, c->stream, (const uint32_t *)c->v_line_off.p, (const uint32_t *)F.gtmp.p, (const uint32_t *)F.gbase.p, (const uint8_t *)F.cls.p,
+                hipLaunchKernelGGL(fa_line_cl, dim3(lgrid), dim3(256), 0, c->stream, (const uint32_t *)c->lines.line_off.p, (const uint32_t *)F.gtmp.p, (const uint32_t *)F.gbase.p, (const uint8_t *)F.cls.p,
                                    (uint32_t)nlines, (uint32_t)nl, (uint32_t)gtotal, (uint32_t *)F.cl.p, (uint32_t *)F.flag.p);
                 const uint32_t *in2[2] = {(const uint32_t *)F.cl.p, (const uint32_t *)F.flag.p}; uint32_t *out2[2] = {(uint32_t *)F.csum.p, (uint32_t *)F.hrank.p}; uint64_t tot2[2] = {0, 0};
                 if (run_scan(c, 2, in2, out2, nullptr, nlines, tot2)) return -1;
                 const uint32_t nhdr = (uint32_t)tot2[1];
                 ENSURE(c, F.hdr, (size_t)(nhdr + 1) * 4 + 64); ENSURE(c, F.fshort, (size_t)(nhdr + 1) * 4 + 64); ENSURE(c, F.rec, (size_t)(nhdr + 1) * sizeof(FaRec) + 64);
                 FaArgs a; memset(&a, 0, sizeof(a));
-                a.u = u; a.ulen = ulen; a.line_off = (const uint32_t *)c->v_line_off.p; a.cls = (const uint8_t *)F.cls.p; a.nlines = (uint32_t)nlines;
+                a.u = u; a.ulen = ulen; a.line_off = (const uint32_t *)c->lines.line_off.p; a.cls = (const uint8_t *)F.cls.p; a.nlines = (uint32_t)nlines;
                 a.cl = (const uint32_t *)F.cl.p; a.csum = (const uint32_t *)F.csum.p; a.hrank = (const uint32_t *)F.hrank.p; a.hdr_line = (const uint32_t *)F.hdr.p; a.nhdr = nhdr;
                 a.c_phase = (cur.active && cur.phase == 0) ? 0u : 1u; a.c_line_len = cur.line_len;
                 a.first_short = (uint32_t *)F.fshort.p; a.err = (unsigned long long *)F.err.p; a.rec = (FaRec *)F.rec.p;
@@ -129,8 +120,9 @@ extern "C" int64_t dhts_fasta_build_index(dhts_ctx *c) {
                     if (kind == FA_ERR_DIFFLEN) return fail(c, "Different line length in sequence '%s' at line %lld", nm.c_str(), ln1);
                     if (kind == FA_ERR_AT) return fail(c, "Found '@' in a FASTA file, error at line %lld", ln1);
                     if (kind == FA_ERR_CR) return fail(c, "Format error, carriage return not followed by new line at line %lld", ln1);
-                    uint32_t lo = 0; uint8_t ch = 0;
-                    HIPCHK(c, hipMemcpy(&lo, (const uint32_t *)c->v_line_off.p + e, 4, hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy(&ch, u + lo, 1, hipMemcpyDeviceToHost));
+                    uint64_t lo = 0; uint8_t ch = 0;
+                    if (line_start(c, c->lines, e, lo)) return -1;
+                    HIPCHK(c, hipMemcpy(&ch, u + lo, 1, hipMemcpyDeviceToHost));
                     if (ch >= 0x20 && ch <= 0x7e) return fail(c, "Format error, unexpected \"%c\" at line %lld", (char)ch, ln1);
                     return fail(c, "Format error, unexpected character at line %lld", ln1);
                 }
@@ -144,7 +136,7 @@ extern "C" int64_t dhts_fasta_build_index(dhts_ctx *c) {
                     const FaRec &R = recs[r];
                     if (open_last && R.hdr_line + 1 == (uint32_t)nlines) {       // the file ends inside this header line
                         eof_hdr_line = lineno + R.hdr_line + 1;
-                        uint32_t lo = 0; HIPCHK(c, hipMemcpy(&lo, (const uint32_t *)c->v_line_off.p + R.hdr_line, 4, hipMemcpyDeviceToHost));
+                        uint64_t lo = 0; if (line_start(c, c->lines, R.hdr_line, lo)) return -1;
                         eof_hdr.assign((size_t)(ulen - lo), '\0');
                         HIPCHK(c, hipMemcpy(&eof_hdr[0], u + lo, (size_t)(ulen - lo), hipMemcpyDeviceToHost));
                         if (eof_hdr.size() == 1) break;                          // a bare '>' as the last byte: IN_NAME is never entered, the record in front of it is still open

@@ -278,7 +278,7 @@ static int nuc_next_bed_one(dhts_ctx *c, dhts_ctx *b, int64_t max_blocks, dhts_n
         if (S.lend.ensure(ln) || S.ntab.ensure(ln) || S.is_row.ensure(ln) || S.ctr.ensure(64)) return fail(c, "hipMalloc failed");
         const bool by_region = S.rg_active && !S.rg_all;
         BedLines a; memset(&a, 0, sizeof(a));
-        a.u = u; a.line_off = (const uint32_t *)S.line_off.p; a.tab_off = (const uint32_t *)S.tab_off.p; a.tab0 = (const uint32_t *)S.tab0.p; a.has_nul = (const uint32_t *)S.has_nul.p;
+        a.u = u; a.line_off = (const uint32_t *)S.lines.line_off.p; a.tab_off = (const uint32_t *)S.tabs.tab_off.p; a.tab0 = (const uint32_t *)S.tabs.tab0.p; a.has_nul = (const uint32_t *)S.tabs.has_nul.p;
         a.nlines = (uint32_t)nlines; a.text_end = (uint32_t)ulen; a.last_open = T.last_open; a.report_bad = 0;
         a.lend = (uint32_t *)S.lend.p; a.ntab = (uint32_t *)S.ntab.p; a.is_row = (uint32_t *)S.is_row.p; a.first_bad = (unsigned long long *)S.ctr.p;
         const unsigned lgrid = (unsigned)((nlines + 255) / 256);
@@ -286,7 +286,7 @@ static int nuc_next_bed_one(dhts_ctx *c, dhts_ctx *b, int64_t max_blocks, dhts_n
         hipLaunchKernelGGL(bed_classify, dim3(lgrid), dim3(256), 0, b->stream, a);
         if (by_region) {                                                       // tbx_itr_next's test, as read_bed's region query makes it
             if (S.tbx.ensure((size_t)nlines * sizeof(TbxLine) + 64)) return fail(c, "hipMalloc failed");
-            hipLaunchKernelGGL(tabix_intervals, dim3(lgrid), dim3(256), 0, b->stream, u, (const uint32_t *)S.line_off.p, nlines, ulen, (int32_t)T.last_open, S.conf, (TbxLine *)S.tbx.p);
+            hipLaunchKernelGGL(tabix_intervals, dim3(lgrid), dim3(256), 0, b->stream, u, (const uint32_t *)S.lines.line_off.p, nlines, ulen, (int32_t)T.last_open, S.conf, (TbxLine *)S.tbx.p);
             hipLaunchKernelGGL(bed_region_keep, dim3(lgrid), dim3(256), 0, b->stream, u, (const TbxLine *)S.tbx.p, (uint32_t)nlines, (const uint8_t *)S.rg_name_dev.p, (uint32_t)S.rg_name.size(),
                                (long long)S.rg_beg, (long long)S.rg_end, (uint32_t *)S.is_row.p, (unsigned long long *)S.ctr.p);
         }
@@ -316,13 +316,7 @@ int dhts_nuc_next_bed(dhts_ctx *c, dhts_ctx *b, int64_t max_blocks, dhts_nuc_bat
     HIPCHK(c, hipSetDevice(c->device));
     for (;;) {
         if (nuc_next_bed_one(c, b, max_blocks, out)) return -1;
-        if (out->status == 1 && b->win_cur + 1 < b->wins.size()) {            // several index windows, as in dhts_bed_next_batch
-            enter_window(b, b->win_cur + 1);
-            discard_prefetch(b);
-            b->next_block = b->shard_b0; b->carry_len = 0; b->stream_done = false; b->first_batch = true; b->ucur = 0;
-            out->status = 0;
-            if (out->n_rows == 0) continue;
-        }
+        if (next_window(b, out->status) && out->n_rows == 0) continue;      // several index windows, as in dhts_bed_next_batch
         return 0;
     }
 }

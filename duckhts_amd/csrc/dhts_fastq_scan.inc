@@ -9,30 +9,16 @@
 #define FASTQ_MAX_RECORD_TEXT (2ull << 30)
 static int fastq_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, uint64_t &enc_len, int64_t &nrec, uint64_t &carry_start, bool &rejected, uint64_t &t0) {
     const uint8_t *u = B.u; const uint64_t ulen = B.ulen, out_base = B.out_base;
-    t0 = 0;
-    if (c->first_batch) { if (c->scan_first_uoff < out_base) return fail(c, "internal: header beyond first batch"); t0 = c->scan_first_uoff - out_base; }
-    nrec = 0; enc = nullptr; enc_len = 0; rejected = false; carry_start = t0 < ulen ? t0 : ulen;
+    if (!first_line_t0(c, out_base, t0)) return fail(c, "internal: header beyond first batch");
+    nrec = 0; enc = nullptr; enc_len = 0; rejected = false;
     c->s_last_nrec = 0; c->s_last_len = 0;
-    if (t0 >= ulen) return 0;
-    const int64_t nchunks = (int64_t)((ulen - (t0 & ~(uint64_t)15) + VCF_CHUNK - 1) / VCF_CHUNK);
-    ENSURE(c, c->v_cnt, (size_t)nchunks * 4 + 64); ENSURE(c, c->v_base, (size_t)(nchunks + 1) * 4 + 64);
-    hipLaunchKernelGGL(vcf_line_count, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, t0, ulen, (uint32_t *)c->v_cnt.p, nchunks);
-    const uint32_t *kin[1] = {(const uint32_t *)c->v_cnt.p}; uint32_t *kout[1] = {(uint32_t *)c->v_base.p}; uint64_t nl = 0;
-    if (run_scan(c, 1, kin, kout, nullptr, nchunks, &nl)) return -1;
-    if (nl + 2 >= (uint64_t)FQ_IDX) return fail(c, "batch too large");
-    ENSURE(c, c->v_line_off, (size_t)(nl + 2) * 4 + 64);
-    hipLaunchKernelGGL(vcf_line_fill, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, t0, ulen, (const uint32_t *)c->v_base.p, (uint32_t *)c->v_line_off.p, nchunks);
-    uint32_t last_start = 0;
-    HIPCHK(c, hipMemcpyAsync(&last_start, (const uint32_t *)c->v_line_off.p + nl, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int64_t nlines = (int64_t)nl;
-    uint64_t lines_end = last_start;                                           // text offset behind the batch's complete lines
-    const bool clean_end = B.final_batch && !c->gz_error && !B.blk_err;        // the end of the batch is the end of an undamaged file
-    if (clean_end && last_start < ulen) {                                      // the last line of the file need not end in a newline
-        const uint32_t end1 = (uint32_t)ulen + 1;
-        HIPCHK(c, hipMemcpy((uint32_t *)c->v_line_off.p + nl + 1, &end1, 4, hipMemcpyHostToDevice));
-        nlines++; lines_end = ulen;
-    }
+    const bool clean_end = batch_clean_end(c, B);
+    LineTab T;
+    if (line_table(c, c->lines, nullptr, u, t0, ulen, clean_end, ~0ull, -1, T)) return -1;
+    if (T.nl + 2 >= (uint64_t)FQ_IDX) return fail(c, "batch too large");         // (line numbers share their word with the chain's flags)
+    const int64_t nlines = T.nlines;
+    const uint64_t lines_end = T.carry_start;                                  // text offset behind the batch's complete lines
+    if (t0 >= ulen) { carry_start = ulen; return 0; }
     carry_start = t0;
     if (nlines == 0) return 0;
     const size_t ln = (size_t)(nlines + 2) * 4 + 64; const int64_t ntiles = (nlines + FQ_TILE - 1) / FQ_TILE;
@@ -40,7 +26,7 @@ static int fastq_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, 
     ENSURE(c, c->f_plus, ln); ENSURE(c, c->f_exit, ln); ENSURE(c, c->f_isstart, ln); ENSURE(c, c->f_recrank, ln); ENSURE(c, c->f_recline, ln);
     ENSURE(c, c->f_entry, (size_t)ntiles * 4 + 64); ENSURE(c, c->f_stop, 64); ENSURE(c, c->s_ctr, 64);
     FqArgs a; memset(&a, 0, sizeof(a));
-    a.u = u; a.line_off = (const uint32_t *)c->v_line_off.p; a.nlines = (uint32_t)nlines; a.fasta = c->fastq == 2 ? 1 : 0; a.final_batch = clean_end ? 1 : 0;
+    a.u = u; a.line_off = (const uint32_t *)c->lines.line_off.p; a.nlines = (uint32_t)nlines; a.fasta = c->fastq == 2 ? 1 : 0; a.final_batch = clean_end ? 1 : 0;
     a.len = (uint32_t *)c->f_len.p; a.flag = (uint32_t *)c->f_flag.p; a.psum = (const uint32_t *)c->f_psum.p; a.rank = (const uint32_t *)c->f_rank.p; a.mark_idx = (uint32_t *)c->f_mark.p;
     a.next = (uint32_t *)c->f_next.p; a.plus = (uint32_t *)c->f_plus.p; a.exit_ = (uint32_t *)c->f_exit.p; a.entry = (uint32_t *)c->f_entry.p; a.stop = (uint32_t *)c->f_stop.p;
     a.is_start = (uint32_t *)c->f_isstart.p; a.rec_rank = (const uint32_t *)c->f_recrank.p; a.rec_line = (uint32_t *)c->f_recline.p;
@@ -64,9 +50,8 @@ static int fastq_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, 
         if (run_scan(c, 1, in1, out1, nullptr, nlines, &nstart)) return -1;        // (waits for the stream: `stop` has arrived)
     }
     // where the chain ended: behind the lines (the partial line is the carry), at a refused line, or at a record the batch cuts short
-    auto line_start = [&](uint32_t i, uint64_t &off) -> int { uint32_t w = 0; HIPCHK(c, hipMemcpy(&w, (const uint32_t *)c->v_line_off.p + i, 4, hipMemcpyDeviceToHost)); off = w; return 0; };
     if (stop[1] == 0) carry_start = lines_end;
-    else { if (line_start(stop[0], carry_start)) return -1; rejected = stop[1] == 1 || B.final_batch; }
+    else { if (line_start(c, c->lines, stop[0], carry_start)) return -1; rejected = stop[1] == 1 || B.final_batch; }
     if (!rejected && !B.final_batch && nstart == 0 && ulen - carry_start >= FASTQ_MAX_RECORD_TEXT)
         return fail(c, "read_bam: a FASTQ/FASTA record of more than 2 GiB of text does not fit into one batch");
     if (nstart == 0) return 0;
@@ -107,10 +92,9 @@ static int fastq_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, 
 }
 // text offset of record `i` of the last FASTQ / FASTA batch
 static int fastq_record_start(dhts_ctx *c, int64_t i, uint64_t &off) {
-    uint32_t l = 0, w = 0;
+    uint32_t l = 0;
     HIPCHK(c, hipMemcpy(&l, (const uint32_t *)c->f_recline.p + i, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&w, (const uint32_t *)c->v_line_off.p + l, 4, hipMemcpyDeviceToHost));
-    off = w; return 0;
+    return line_start(c, c->lines, l, off);
 }
 // debugging aid (include/duckhts_amd_debug.h): the BAM records the encoder made of the last FASTQ / FASTA batch
 extern "C" int64_t dhts_debug_fastq_records(dhts_ctx *c, uint8_t *dst, uint64_t cap, int64_t *nrec) {

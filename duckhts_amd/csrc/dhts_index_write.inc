@@ -203,7 +203,7 @@ int64_t dhts_bcf_build_index(dhts_ctx *c, int min_shift) {
             // rid / pos / rlen sit in the 32-byte head of every record: offsets from the batch, the heads gathered by one strided copy
             lap(t2_scan);
             ro.resize(n); core.resize((size_t)n * 16);
-            HIPCHK(c, hipMemcpyAsync(ro.data(), text ? c->v_line_off.p : c->b_rec_off.p, n * 4, hipMemcpyDeviceToHost, c->stream));   // (text: a line ends where the next one starts)
+            HIPCHK(c, hipMemcpyAsync(ro.data(), text ? c->lines.line_off.p : c->b_rec_off.p, n * 4, hipMemcpyDeviceToHost, c->stream));   // (text: a line ends where the next one starts)
             HIPCHK(c, hipStreamSynchronize(c->stream));
             ENSURE(c, c->ix_end, (size_t)n * 16 + 64);
             hipLaunchKernelGGL(bcf_index_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->last_bcf_u, (const uint32_t *)c->b_rec_off.p, n, text ? (const int32_t *)c->v_pos_hi.p : (const int32_t *)nullptr, (uint32_t *)c->ix_end.p);

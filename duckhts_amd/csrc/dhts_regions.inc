@@ -462,6 +462,16 @@ static void enter_window(dhts_ctx *c, size_t k) {
     c->win_cur = k; c->shard_b0 = w.b0; c->shard_b1 = w.b1; c->shard_rank = 0; c->shard_world = (w.b1 < c->n_blocks) ? 2 : 1;
     c->scan_first_uoff = w.first_uoff; c->scan_end_uoff = w.end_uoff;
 }
+// a batch ended its index window (status 1) and another window follows: the scan moves on to it and goes on (status 0).  The caller asks
+// for the next batch at once when this one had no rows.
+static bool next_window(dhts_ctx *c, int32_t &status) {
+    if (status != 1 || c->win_cur + 1 >= c->wins.size()) return false;
+    enter_window(c, c->win_cur + 1);
+    discard_prefetch(c);
+    c->next_block = c->shard_b0; c->carry_len = 0; c->stream_done = false; c->first_batch = true; c->ucur = 0;
+    status = 0;
+    return true;
+}
 int dhts_bam_rewind(dhts_ctx *c) {
     if (!c) return -1;
     discard_prefetch(c);

@@ -8,36 +8,20 @@
 // the batch's first line).
 static int sam_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, uint64_t &enc_len, int64_t &nrec, uint64_t &carry_start, bool &rejected, uint64_t &t0) {
     const uint8_t *u = B.u; const uint64_t ulen = B.ulen, out_base = B.out_base;
-    t0 = 0;
-    if (c->first_batch) { if (c->scan_first_uoff < out_base) return fail(c, "internal: header beyond first batch"); t0 = c->scan_first_uoff - out_base; }
-    nrec = 0; enc = nullptr; enc_len = 0; rejected = false; carry_start = t0 < ulen ? t0 : ulen;
+    if (!first_line_t0(c, out_base, t0)) return fail(c, "internal: header beyond first batch");
+    nrec = 0; enc = nullptr; enc_len = 0; rejected = false;
     c->s_last_nrec = 0; c->s_last_len = 0;                                    // (a batch without a complete line encodes nothing)
-    if (t0 >= ulen) return 0;
-    const int64_t nchunks = (int64_t)((ulen - (t0 & ~(uint64_t)15) + VCF_CHUNK - 1) / VCF_CHUNK);
-    ENSURE(c, c->v_cnt, (size_t)nchunks * 4 + 64); ENSURE(c, c->v_base, (size_t)(nchunks + 1) * 4 + 64);
-    hipLaunchKernelGGL(vcf_line_count, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, t0, ulen, (uint32_t *)c->v_cnt.p, nchunks);
-    const uint32_t *kin[1] = {(const uint32_t *)c->v_cnt.p}; uint32_t *kout[1] = {(uint32_t *)c->v_base.p}; uint64_t nl = 0;
-    if (run_scan(c, 1, kin, kout, nullptr, nchunks, &nl)) return -1;
-    if (nl + 2 >= (1ull << 32)) return fail(c, "batch too large");
-    ENSURE(c, c->v_line_off, (size_t)(nl + 2) * 4 + 64);
-    hipLaunchKernelGGL(vcf_line_fill, dim3((unsigned)nchunks), dim3(256), 0, c->stream, u, t0, ulen, (const uint32_t *)c->v_base.p, (uint32_t *)c->v_line_off.p, nchunks);
-    uint32_t last_start = 0;
-    HIPCHK(c, hipMemcpyAsync(&last_start, (const uint32_t *)c->v_line_off.p + nl, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int64_t nlines = (int64_t)nl;
-    carry_start = last_start;
-    if (B.final_batch && last_start < ulen && !c->gz_error && !B.blk_err) {                  // the last line of the file need not end in a newline
-        const uint32_t end1 = (uint32_t)ulen + 1;                               // (line i ends at line_off[i + 1] - 1)
-        HIPCHK(c, hipMemcpy((uint32_t *)c->v_line_off.p + nl + 1, &end1, 4, hipMemcpyHostToDevice));
-        nlines++; carry_start = ulen;
-    }
+    LineTab T;
+    if (line_table(c, c->lines, nullptr, u, t0, ulen, batch_clean_end(c, B), ~0ull, -1, T)) return -1;      // (the encoder reads the open last line's end from the sentinel)
+    const int64_t nlines = T.nlines;
+    carry_start = T.carry_start;
     if (nlines == 0) return 0;
     ENSURE(c, c->v_rec_len, (size_t)(nlines + 1) * 4 + 64); ENSURE(c, c->b_rec_off, (size_t)(nlines + 1) * 4 + 64); ENSURE(c, c->s_ctr, 64);
     // room for the values the host converts: grown (and the measure pass repeated) when a batch needs more.  DHTS_SAM_PATCH_CAP: the
     // starting room (tests: a small one makes the growth path cheap to reach)
     if (c->s_patch_cap == 0) { const char *e = getenv("DHTS_SAM_PATCH_CAP"); const long v = e ? atol(e) : 0; c->s_patch_cap = v > 0 ? (uint32_t)v : (1u << 20); }
     SamArgs a; memset(&a, 0, sizeof(a));
-    a.u = u; a.line_off = (const uint32_t *)c->v_line_off.p; a.nlines = nlines;
+    a.u = u; a.line_off = (const uint32_t *)c->lines.line_off.p; a.nlines = nlines;
     a.names.off = (const uint32_t *)c->s_name_off.p; a.names.bytes = (const uint8_t *)c->s_name_bytes.p; a.names.id = (const int32_t *)c->s_name_id.p;
     a.names.n = c->s_n_names; a.names.hash = (const uint32_t *)c->s_name_hash.p; a.names.hmask = c->s_name_hmask; a.n_targets = (int32_t)c->ref_name.size();
     a.rec_len = (uint32_t *)c->v_rec_len.p; a.rec_off = (const uint32_t *)c->b_rec_off.p;
@@ -118,20 +102,15 @@ static int sam_text_records(dhts_ctx *c, const Batch &B, const uint8_t *&enc, ui
     rejected = nrec < nlines;
     enc_len = total;
     if (rejected) {
-        uint32_t w[2] = {0, 0};
-        HIPCHK(c, hipMemcpy(&w[0], (const uint32_t *)c->b_rec_off.p + nrec, 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(&w[1], (const uint32_t *)c->v_line_off.p + nrec, 4, hipMemcpyDeviceToHost));
-        enc_len = w[0]; carry_start = w[1];
+        uint32_t w = 0;
+        HIPCHK(c, hipMemcpy(&w, (const uint32_t *)c->b_rec_off.p + nrec, 4, hipMemcpyDeviceToHost));
+        enc_len = w;
+        if (line_start(c, c->lines, nrec, carry_start)) return -1;
     }
     enc = (const uint8_t *)c->s_out.p;
     c->s_last_nrec = nrec; c->s_last_len = enc_len;
     return 0;
 }
-// text offset of line `i` of the last SAM batch (a record that bam_read1's checks refuse ends the scan in front of its line)
-static int sam_line_start(dhts_ctx *c, int64_t i, uint64_t &off) {
-    uint32_t w = 0; HIPCHK(c, hipMemcpy(&w, (const uint32_t *)c->v_line_off.p + i, 4, hipMemcpyDeviceToHost)); off = w; return 0;
-}
-
 extern "C" int dhts_bam_is_text(const dhts_ctx *c) { return (!c || !c->bam_open || !c->sam_text) ? 0 : (c->plain_text ? 2 : 1) + 2 * c->fastq; }
 // debugging aid (include/duckhts_amd_debug.h): the BAM records the encoder made of the last SAM text batch
 extern "C" int64_t dhts_debug_sam_records(dhts_ctx *c, uint8_t *dst, uint64_t cap, int64_t *nrec) {

@@ -82,7 +82,7 @@ int dhts_tabix_region_segments(dhts_ctx *c, const char *region, const void *inde
 static int tabix_fetch_line(dhts_ctx *c, const uint8_t *u, uint32_t li, std::string &text, uint32_t *ntab) {
     BedState &S = c->bed;
     uint32_t l0 = 0, l1 = 0;
-    HIPCHK(c, hipMemcpy(&l0, (const uint32_t *)S.line_off.p + li, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&l0, (const uint32_t *)S.lines.line_off.p + li, 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(&l1, (const uint32_t *)S.lend.p + li, 4, hipMemcpyDeviceToHost));
     if (ntab) HIPCHK(c, hipMemcpy(ntab, (const uint32_t *)S.ntab.p + li, 4, hipMemcpyDeviceToHost));
     text.assign((size_t)(l1 - l0), '\0');
@@ -106,7 +106,7 @@ static int tabix_rows(dhts_ctx *c, int64_t max_blocks, bool need_lines, TabixRow
     const bool skipping = seq && Q.skip_left > 0;
     if (skipping) ENSURE(c, Q.ne, ln);
     BedLines a; memset(&a, 0, sizeof(a));
-    a.u = u; a.line_off = (const uint32_t *)S.line_off.p; a.tab_off = (const uint32_t *)S.tab_off.p; a.tab0 = (const uint32_t *)S.tab0.p; a.has_nul = (const uint32_t *)S.has_nul.p;
+    a.u = u; a.line_off = (const uint32_t *)S.lines.line_off.p; a.tab_off = (const uint32_t *)S.tabs.tab_off.p; a.tab0 = (const uint32_t *)S.tabs.tab0.p; a.has_nul = (const uint32_t *)S.tabs.has_nul.p;
     a.nlines = (uint32_t)nlines; a.text_end = (uint32_t)X.B.ulen; a.last_open = X.T.last_open; a.report_bad = 0;
     a.lend = (uint32_t *)S.lend.p; a.ntab = (uint32_t *)S.ntab.p; a.is_row = (uint32_t *)S.is_row.p; a.first_bad = (unsigned long long *)S.ctr.p;
     const unsigned lgrid = (unsigned)((nlines + 255) / 256);
@@ -118,7 +118,7 @@ static int tabix_rows(dhts_ctx *c, int64_t max_blocks, bool need_lines, TabixRow
             // hts_itr_next's test on the interval tbx_parse1 gives the line under the index's configuration, as read_bed applies it
             ENSURE(c, S.tbx, (size_t)nlines * sizeof(TbxLine) + 64);
             HIPCHK(c, hipMemsetAsync(S.ctr.p, 0xff, 8, c->stream));
-            hipLaunchKernelGGL(tabix_intervals, dim3(lgrid), dim3(256), 0, c->stream, u, (const uint32_t *)S.line_off.p, nlines, X.B.ulen, (int32_t)X.T.last_open, S.conf, (TbxLine *)S.tbx.p);
+            hipLaunchKernelGGL(tabix_intervals, dim3(lgrid), dim3(256), 0, c->stream, u, (const uint32_t *)S.lines.line_off.p, nlines, X.B.ulen, (int32_t)X.T.last_open, S.conf, (TbxLine *)S.tbx.p);
             hipLaunchKernelGGL(bed_region_keep, dim3(lgrid), dim3(256), 0, c->stream, u, (const TbxLine *)S.tbx.p, (uint32_t)nlines, (const uint8_t *)S.rg_name_dev.p, (uint32_t)S.rg_name.size(),
                                (long long)S.rg_beg, (long long)S.rg_end, is_row, (unsigned long long *)S.ctr.p);
         }
@@ -432,13 +432,7 @@ int dhts_tabix_next_batch(dhts_ctx *c, int64_t max_blocks, dhts_tabix_batch *out
     for (;;) {
         if (tabix_next_batch_one(c, max_blocks, out)) return -1;
         // several index windows: the end of one window is the start of the next, not the end of the scan
-        if (out->status == 1 && c->win_cur + 1 < c->wins.size()) {
-            enter_window(c, c->win_cur + 1);
-            discard_prefetch(c);
-            c->next_block = c->shard_b0; c->carry_len = 0; c->stream_done = false; c->first_batch = true; c->ucur = 0;
-            out->status = 0;
-            if (out->n_rows == 0) continue;
-        }
+        if (next_window(c, out->status) && out->n_rows == 0) continue;
         return 0;
     }
 }

@@ -58,6 +58,14 @@ int dhts_debug_deflate_codes(dhts_ctx *, const uint32_t *counts, uint32_t nsym, 
  * start at 0 (seed is unused) and return n + 1 elements, the total last.  host_v has room for n + 1 elements of every kind; element n is
  * uploaded as it is and must not change an answer. */
 int dhts_debug_carry(dhts_ctx *, int kind, void *host_v, uint64_t n, uint64_t seed);
+/* tests: the line table the text readers share, alone (csrc/dhts_text_lines.inc: line_table), on a host text of n bytes that is staged with
+ * the 64 zero bytes a batch has behind it.  t0: where the first line starts; open_last_ok: a last line without a newline counts; lim: lines
+ * that start at or behind it are cut (~0: no cut); with_tabs: the tab part (bed_delim_count / bed_delim_fill instead of vcf_line_count /
+ * vcf_line_fill).  out takes the function's result: nl, ntabs, nlines, last_start, carry_start, last_open, finished.  When t0 < n, line_off takes the nlines + 1 starts line_off[0 .. nlines] (behind an open last
+ * line that is n + 1) and, with the tab part, tab0 as many words, has_nul nlines words and tab_off ntabs words; the arrays have room for n + 2
+ * words each.  When t0 >= n no table is made and no array is written. */
+int dhts_debug_line_table(dhts_ctx *, const uint8_t *text, uint64_t n, uint64_t t0, int open_last_ok, uint64_t lim, int with_tabs, uint64_t out[7],
+                          uint32_t *line_off, uint32_t *tab_off, uint32_t *tab0, uint32_t *has_nul);
 /* tests: the row-text encoder alone (csrc/rows_text.hip) on host arrays: a table of n_names names (names: the byte arena, name_offs:
  * n_names + 1 offsets into it) and n_rows rows of tid (int32; outside the table: an empty name), start, end (int64) and depth (int32) -> the
  * bytes `name \t start \t end \t depth \n` per row in out.  The text lies 5 bytes into the device buffer, so the write pass meets a span that

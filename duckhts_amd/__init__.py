@@ -160,6 +160,11 @@ class DepthHistStats(C.Structure):
                 ("table_bytes", C.c_uint64), ("hist_bytes", C.c_uint64), ("n_result_rows", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class IvlStats(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_skipped", C.c_uint64), ("n_chroms", C.c_uint64), ("n_name_runs", C.c_uint64), ("n_runs", C.c_uint64), ("n_pairs", C.c_uint64),
+                ("sort_passes", C.c_int32), ("status", C.c_int32)]
+
+
 class TabixMap(C.Structure):
     _fields_ = [("pair_off", C.c_void_p), ("valid", C.c_void_p), ("n_pairs", C.c_uint64), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p), ("key_nbytes", C.c_uint64),
                 ("val_off", C.c_void_p), ("val_bytes", C.c_void_p), ("val_nbytes", C.c_uint64)]
@@ -232,6 +237,13 @@ BEDGRAPH_COLMASK = DEPTH_COLMASK                                            # th
 BEDGRAPH_MAX_BREAKS = 16
 BEDGRAPH_EXPORT_INDEX = {"none": 0, "tbi": 1, "csi": 2}                     # the C struct's index
 ROWS_TEXT_LDS_BYTES = 16384                                                 # csrc/rows_text.hip: RTX_LDS_BYTES, the longest span of 256 rows the write pass stages in LDS
+INTERVAL_MERGE_COLUMNS = ["chrom", "start", "end", "n_merged"]
+INTERVAL_OVERLAP_COLUMNS = ["chrom", "start", "end", "left_row", "right_start", "right_end", "right_row", "overlap"]
+INTERVAL_DTYPES = (np.int32,) + (np.int64,) * 7                              # chrom: the context's name id; every other column an int64
+INTERVAL_MODES = {"any": 0, "contain": 1, "within": 2}                      # the C ABI's mode
+INTERVAL_MAX_GAP = 1 << 40
+IVL_SORT_TILE = 4096                                                        # csrc/interval_sort.hip: IVL_SORT_TILE, the pairs one workgroup of the sort ranks
+IVL_SORT_MAX_PASSES = 12                                                    # ... IVL_SORT_MAX_PASSES: 8 bytes of the start, 4 of the chrom's rank
 DEPTH_HIST_COLUMNS = ["tid", "start", "end", "depth", "n_positions", "n_at_least", "length"]
 DEPTH_HIST_DTYPES = (np.int32, np.int64, np.int64, np.int32, np.int64, np.int64, np.int64)   # start 0-based, end exclusive
 DEPTH_HIST_COLMASK = DEPTH_COLMASK                                          # the columns of the scan bam_depth_hist accumulates (no string column)
@@ -272,6 +284,8 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_bam_bedgraph_open", "dhts_bam_bedgraph_accumulate", "dhts_bam_bedgraph_scan", "dhts_bam_bedgraph_stats", "dhts_bam_bedgraph_next", "dhts_bam_bedgraph_batch_host_bytes", "dhts_bam_bedgraph_batch_fetch",
            "dhts_bedgraph_export",
            "dhts_bam_hist_open", "dhts_bam_hist_accumulate", "dhts_bam_hist_scan", "dhts_bam_hist_stats", "dhts_bam_hist_next", "dhts_bam_hist_batch_host_bytes", "dhts_bam_hist_batch_fetch",
+           "dhts_ivl_load", "dhts_ivl_stats_get", "dhts_ivl_chrom_name", "dhts_ivl_merge_open", "dhts_ivl_merge_next", "dhts_ivl_overlap_open", "dhts_ivl_overlap_next",
+           "dhts_ivl_batch_host_bytes", "dhts_ivl_batch_fetch",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
            "dhts_udf_upload", "dhts_udf_apply", "dhts_udf_result_host_bytes", "dhts_udf_fetch", "dhts_udf_seq_kmers", "dhts_udf_kmers_host_bytes", "dhts_udf_kmers_fetch"]
@@ -387,6 +401,20 @@ def lib():
             f["batch_host_bytes"].argtypes = [C.POINTER(BedBatch)]
             f["batch_fetch"].argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
         L.dhts_bedgraph_export.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(BedgraphExportParams), C.POINTER(BedgraphExportStats)]
+        L.dhts_ivl_load.argtypes = [C.c_void_p, C.c_int64]
+        L.dhts_ivl_stats_get.argtypes = [C.c_void_p, C.POINTER(IvlStats)]
+        L.dhts_ivl_chrom_name.restype = C.c_void_p
+        L.dhts_ivl_chrom_name.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
+        L.dhts_ivl_merge_open.argtypes = [C.c_void_p, C.c_int64]
+        L.dhts_ivl_merge_next.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(BedBatch)]
+        L.dhts_ivl_overlap_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.dhts_ivl_overlap_next.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(BedBatch)]
+        L.dhts_ivl_batch_host_bytes.restype = C.c_uint64
+        L.dhts_ivl_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
+        L.dhts_ivl_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_debug_ivl_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int32)]
+        L.dhts_debug_ivl_ms.restype = C.c_double
+        L.dhts_debug_ivl_ms.argtypes = [C.c_void_p, C.c_int]
         L.dhts_debug_rows_text.restype = C.c_int64
         L.dhts_debug_rows_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64]
         L.dhts_debug_rows_text_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
@@ -1089,6 +1117,84 @@ class Context:
         b = BedBatch()
         self._chk(self.L.dhts_bam_bedgraph_next(self.h, max_rows, mask, C.byref(b)))
         return self._fixed_cols("bedgraph", b, mask, BEDGRAPH_COLUMNS, BEDGRAPH_DTYPES)
+
+    # ---- interval_merge / interval_overlap ----
+    def ivl_load(self, max_blocks=0):
+        """after open, bgzf_index and dhts_bed_open: the BED read to its end, its valid rows sorted and indexed on the device"""
+        self._chk(self.L.dhts_ivl_load(self.h, max_blocks))
+
+    def ivl_stats(self):
+        st = IvlStats()
+        self._chk(self.L.dhts_ivl_stats_get(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in IvlStats._fields_}
+
+    def ivl_chrom_names(self):
+        """the chrom names by name id (order of first appearance), as bytes"""
+        out, n = [], C.c_uint64(0)
+        while True:
+            p = self.L.dhts_ivl_chrom_name(self.h, len(out), C.byref(n))
+            if not p:
+                return out
+            out.append(C.string_at(p, n.value))
+
+    def _ivl_fetch(self, b, mask, names):
+        need = int(self.L.dhts_ivl_batch_host_bytes(C.byref(b)))
+        arena = np.zeros(max(need, 8), np.uint8)
+        host = (BcfCol * max(b.n_cols, 1))()
+        self._chk(self.L.dhts_ivl_batch_fetch(self.h, C.byref(b), arena.ctypes.data, need, host))
+        n, out = int(b.n_rows), {"n_rows": int(b.n_rows)}
+        for i in range(b.n_cols):
+            col, dt = names[host[i].col], INTERVAL_DTYPES[host[i].col]
+            if not (mask >> host[i].col) & 1:
+                out[col] = None
+            elif n == 0:
+                out[col] = np.zeros(0, dt)
+            else:
+                off = host[i].fixed - arena.ctypes.data
+                out[col] = arena[off:off + n * np.dtype(dt).itemsize].view(dt).copy()
+        return out, int(b.status)
+
+    def ivl_merge_open(self, max_gap=0):
+        """after ivl_load: the runs of interval_merge flagged and numbered"""
+        if not 0 <= int(max_gap) <= INTERVAL_MAX_GAP:
+            raise DhtsError("interval_merge: max_gap must be between 0 and 1099511627776")
+        self._chk(self.L.dhts_ivl_merge_open(self.h, int(max_gap)))
+
+    def ivl_merge_next(self, max_rows=0, columns=None):
+        """the next rows of the result: ({"n_rows", "chrom": int32 name ids, "start", "end", "n_merged": int64 arrays; None for a column
+        `columns` leaves out}, status)"""
+        mask = sum(1 << INTERVAL_MERGE_COLUMNS.index(k) for k in (INTERVAL_MERGE_COLUMNS if columns is None else columns))
+        b = BedBatch()
+        self._chk(self.L.dhts_ivl_merge_next(self.h, max_rows, mask, C.byref(b)))
+        return self._ivl_fetch(b, mask, INTERVAL_MERGE_COLUMNS)
+
+    def ivl_overlap_open(self, right, mode="any"):
+        """after ivl_load on both contexts (one device): every left row's pairs counted against right's index"""
+        if mode not in INTERVAL_MODES:
+            raise DhtsError("interval_overlap: mode must be 'any', 'contain' or 'within'")
+        self._chk(self.L.dhts_ivl_overlap_open(self.h, right.h if right is not None else None, INTERVAL_MODES[mode]))
+
+    def ivl_overlap_next(self, max_rows=0, columns=None):
+        """the next page of whole left rows: ({"n_rows", "chrom": the left context's int32 name ids, the other columns int64 arrays; None for
+        a column `columns` leaves out}, status)"""
+        mask = sum(1 << INTERVAL_OVERLAP_COLUMNS.index(k) for k in (INTERVAL_OVERLAP_COLUMNS if columns is None else columns))
+        b = BedBatch()
+        self._chk(self.L.dhts_ivl_overlap_next(self.h, max_rows, mask, C.byref(b)))
+        return self._ivl_fetch(b, mask, INTERVAL_OVERLAP_COLUMNS)
+
+    def debug_ivl_sort(self, keys, rank):
+        """tests, tools/bench_intervals.py: the sort alone.  keys: uint64, compared unsigned; rank: uint32 per row, the more significant part.
+        (the row numbers in sorted order as uint32, the radix passes that were run)"""
+        k, r = np.ascontiguousarray(keys, np.uint64), np.ascontiguousarray(rank, np.uint32)
+        if len(k) != len(r):
+            raise ValueError("keys and rank have to be of one length")
+        out, passes = np.zeros(max(len(k), 1), np.uint32), C.c_int32(0)
+        self._chk(self.L.dhts_debug_ivl_sort(self.h, k.ctypes.data, r.ctypes.data, len(k), out.ctypes.data, C.byref(passes)))
+        return out[:len(k)], int(passes.value)
+
+    def debug_ivl_ms(self, what):
+        """tools/bench_intervals.py: device milliseconds of a part (0 load, 1 sort, 2 index, 3 merge, 4 overlap count, 5 overlap write, 16 + p sort pass p)"""
+        return float(self.L.dhts_debug_ivl_ms(self.h, what))
 
     # ---- bam_bedgraph_export ----
     def bam_bedgraph_export(self, out_path, index="tbi", level=-1, min_shift=0, overwrite=False):
@@ -2385,6 +2491,65 @@ def bam_bedgraph(src, region=None, index=None, bed=None, max_blocks=0, max_rows=
         if bctx is not None:
             bctx.close()
         ctx.close()
+
+
+def _interval_result(ctx, parts, names_cols, status):
+    out = {k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts]) for k in names_cols}
+    names = ctx.ivl_chrom_names()
+    out["chrom"] = None if out["chrom"] is None else [names[i] for i in out["chrom"]]
+    out["n_rows"] = sum(p["n_rows"] for p in parts)
+    out["pages"] = [p["n_rows"] for p in parts]
+    out["status"] = status
+    return out
+
+
+def interval_merge(bed, max_gap=0, columns=None, device=0, max_rows=0, max_blocks=0, stats=None):
+    """interval_merge(path, max_gap := 0): the valid rows of a BED (a path, plain or bgzipped, or the file's bytes) sorted by (chrom, start) and
+    merged into runs on the device (the contract: include/duckhts_amd.h).  {"n_rows", "chrom": list of bytes, "start", "end", "n_merged": int64
+    arrays -- None for a column `columns` leaves out --, "pages": the rows of every page, "status": how the BED's stream ended}.  stats (a
+    dict) receives n_rows, n_skipped, n_chroms, n_name_runs, sort_passes and n_runs; max_rows: rows per page; max_blocks: BGZF blocks per batch of
+    the read."""
+    if not 0 <= int(max_gap) <= INTERVAL_MAX_GAP:
+        raise DhtsError("interval_merge: max_gap must be between 0 and 1099511627776")
+    ctx = _bed_ctx(device, bed)
+    try:
+        ctx.ivl_load(max_blocks)
+        ctx.ivl_merge_open(max_gap)
+        parts = _drain(lambda: ctx.ivl_merge_next(max_rows, columns))
+        st = ctx.ivl_stats()
+        if stats is not None:
+            stats.update({k: v for k, v in st.items() if k not in ("status", "n_pairs")})
+        return _interval_result(ctx, parts, INTERVAL_MERGE_COLUMNS, st["status"])
+    finally:
+        ctx.close()
+
+
+def interval_overlap(left, right, mode="any", columns=None, device=0, max_rows=0, max_blocks=0, stats=None):
+    """interval_overlap(path, right_path :=, mode := 'any' | 'contain' | 'within'): one row per pair of valid rows of the two BED files (paths or
+    bytes) on one chrom that satisfies the mode's predicate, joined on the device (the contract: include/duckhts_amd.h).  {"n_rows", "chrom":
+    list of bytes, "start", "end", "left_row", "right_start", "right_end", "right_row", "overlap": int64 arrays -- None for a column `columns`
+    leaves out --, "pages", "status"}.  stats (a dict) receives the left file's n_rows, n_skipped, n_chroms, n_name_runs, sort_passes and
+    n_pairs, and the right file's under "right"."""
+    if mode not in INTERVAL_MODES:
+        raise DhtsError("interval_overlap: mode must be 'any', 'contain' or 'within'")
+    if right is None:
+        raise DhtsError("interval_overlap requires right_path")
+    lctx, rctx = _bed_ctx(device, left), None
+    try:
+        rctx = _bed_ctx(device, right)
+        lctx.ivl_load(max_blocks)
+        rctx.ivl_load(max_blocks)
+        lctx.ivl_overlap_open(rctx, mode)
+        parts = _drain(lambda: lctx.ivl_overlap_next(max_rows, columns))
+        st = lctx.ivl_stats()
+        if stats is not None:
+            stats.update({k: v for k, v in st.items() if k not in ("status", "n_runs")})
+            stats["right"] = {k: v for k, v in rctx.ivl_stats().items() if k not in ("status", "n_runs", "n_pairs")}
+        return _interval_result(lctx, parts, INTERVAL_OVERLAP_COLUMNS, st["status"])
+    finally:
+        if rctx is not None:
+            rctx.close()
+        lctx.close()
 
 
 def bam_bedgraph_export(src, out_path, index="tbi", level=-1, min_shift=0, overwrite=False, region=None, bam_index=None, bed=None, max_blocks=0, device=0, min_read_len=0,

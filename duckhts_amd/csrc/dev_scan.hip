@@ -2,7 +2,9 @@
 // exclusive scan of an array in place in two levels (the carry).  DESIGN.md 4q says who instantiates what.
 //
 //   operator     Op::identity<T>() and Op::combine(a, b): ScanSum (uint32_t, uint64, and any T with operator+, such as bam_bedcov's CovVec)
-//                and ScanMin (uint64).  Both are commutative; the carry relies on it where it reduces a chunk.
+//                ScanMin (uint64) and ScanMax (any T with operator< and a static T::lowest(), such as the interval index's (rank, end) pair,
+//                whose maximum in lexicographic order is the running maximum end per chrom).  All are commutative; the carry relies on it
+//                where it reduces a chunk.
 //   block_scan   the inclusive scan over the NT threads of the workgroup, Hillis-Steele through LDS: log2 NT rounds of read / barrier /
 //                combine / barrier.  It ends in a barrier and leaves sh[t] = the inclusive value of thread t, so a caller may read its
 //                neighbour's value or the workgroup's total (sh[NT - 1]) behind it, and needs a barrier of its own before sh is written again.
@@ -23,6 +25,11 @@ struct ScanSum {
 struct ScanMin {
     template <typename T> static __device__ __forceinline__ T identity() { return ~(T)0; }
     template <typename T> static __device__ __forceinline__ T combine(const T &a, const T &b) { return a < b ? a : b; }
+};
+
+struct ScanMax {
+    template <typename T> static __device__ __forceinline__ T identity() { return T::lowest(); }
+    template <typename T> static __device__ __forceinline__ T combine(const T &a, const T &b) { return a < b ? b : a; }
 };
 
 template <typename T, typename Op, uint32_t NT = 256u> __device__ __forceinline__ T block_scan(T v, T *sh) {

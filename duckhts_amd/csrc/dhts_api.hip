@@ -23,6 +23,8 @@
 #include "bam_pileup.hip"
 #include "bam_bedgraph.hip"
 #include "bam_depth_hist.hip"
+#include "interval_sort.hip"
+#include "interval_algebra.hip"
 #include "rows_text.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
@@ -285,6 +287,24 @@ struct HistState : AccumBase, DepLayout {
     DevBuf touched, row_group, step, rlen, k0, k1, tsum, part, hist, gcnt, g_tid, g_beg, g_end, g_len, scratch;
     DevBuf out_tid, out_start, out_end, out_depth, out_n, out_at_least, out_len;
 };
+// interval_merge / interval_overlap (interval_sort.hip, interval_algebra.hip, dhts_interval.inc): the chrom names in order of first appearance
+// with their ranks in byte order, per-batch scratch of the load, the table in file order (name id, start, end; vpos: the validity flags, then
+// the valid rows in front of every row), the sort's two sets of (key, row) pairs with its counts, the index by sorted row (OverlapDev's
+// layout with the rank), the runs of a merge, the offsets of an overlap's pairs with the right context, the columns of the last page, and the
+// device times of the parts (dhts_debug_ivl_ms)
+struct IvlState {
+    bool loaded = false, too_many = false, merge_open = false, ov_open = false; int32_t status = 0, mode = 0, sort_passes = 0;
+    uint64_t n_rows = 0, n_valid = 0, n_skipped = 0, n_name_runs = 0, n_runs = 0, n_pairs = 0, cursor = 0;
+    std::vector<std::string> names; std::map<std::string, int32_t> id_of; std::vector<uint32_t> rank_of;
+    dhts_ctx *right = nullptr;
+    DevBuf is_row, head, rpos, hpos, hoff, hlen, hdst, hnames, head_id, ctr;
+    DevBuf name_id, start, end, vpos;
+    DevBuf rank_of_id, rank_row, key[2], row[2], counts, part, bits;
+    DevBuf s_beg, s_end, s_id, s_rank, rank_first, pair, pmax, bmax;
+    DevBuf hidx, run_head, rank_of_left, cnt, cut;
+    DevBuf out[8]; std::vector<dhts_col> cols;
+    double ms[32] = {0};
+};
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
 struct UdfState {
@@ -335,6 +355,7 @@ struct dhts_ctx {
     PileupState pil;
     BedgraphState bdg;
     HistState dhi;
+    IvlState ivl;
     UdfState udf;
     TabixState tbx;
     bool text_any = false;            // dhts_bed_open: a file that is not BGZF is text whatever it holds (BED has no signature)
@@ -584,6 +605,7 @@ static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
     c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->bins.open = false; c->cov.open = false; c->dep.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->range_cut = false; c->last_batch_rows = -1; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
+    c->ivl.loaded = c->ivl.too_many = c->ivl.merge_open = c->ivl.ov_open = false;      // (an interval table is its file's)
     memset(c->tile_stats, 0, sizeof(c->tile_stats));
     c->last_stream = BamStream{};                             // (dhts_debug_tile_scan and the passes that read the latest batch refuse until a batch of the new file has been read)
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
@@ -649,6 +671,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_bedgraph.inc"
 #include "dhts_bam_bedgraph_export.inc"
 #include "dhts_bam_depth_hist.inc"
+#include "dhts_interval.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

@@ -1,7 +1,7 @@
 // duckdb_ext.cpp -- DuckDB C-API extension surface (outer drop-in boundary) over the MI355X scan path.
 //
 // The table functions live in the parts included below, one per reader family, over the shared helpers of duckdb_surface.h:
-//   duckdb_bam.inc read_bam, duckdb_bins.inc bam_bin_counts, duckdb_bedcov.inc bam_bedcov, duckdb_bcf.inc read_bcf, duckdb_seq.inc read_fastq / read_fasta, duckdb_interval.inc read_bed / fasta_nuc,
+//   duckdb_bam.inc read_bam, duckdb_bins.inc bam_bin_counts, duckdb_bedcov.inc bam_bedcov, duckdb_bcf.inc read_bcf, duckdb_seq.inc read_fastq / read_fasta, duckdb_interval.inc read_bed / fasta_nuc, duckdb_interval_algebra.inc interval_merge / interval_overlap,
 //   duckdb_tabix.inc read_tabix / read_gtf / read_gff, duckdb_udf.inc the k-mer family, duckdb_bedgraph.inc bam_bedgraph, duckdb_depth_hist.inc bam_depth_hist, duckdb_bedgraph_export.inc bam_bedgraph_export; duckdb_tools.cpp (its own translation unit) the writers.
 // The htslib calls underneath are replaced by include/duckhts_amd.h (HIP kernels); DuckDB is reached only
 // through the function-pointer table returned by access->get_api(info, "v1.2.0").
@@ -38,6 +38,7 @@ static double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); r
 #include "duckdb_bcf.inc"
 #include "duckdb_seq.inc"
 #include "duckdb_interval.inc"
+#include "duckdb_interval_algebra.inc"
 #include "duckdb_bedcov.inc"
 #include "duckdb_coverage.inc"
 #include "duckdb_depth.inc"
@@ -70,6 +71,7 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     if (const char *e = getenv("DHTS_INTERVAL_FUNCTIONS")) if (atoi(e) == 1) register_read_bed_function(conn);
     // fasta_nuc follows read_bed (src/duckhts.c:59-60), behind a variable of its own: DHTS_NUC_FUNCTIONS=1
     if (const char *e = getenv("DHTS_NUC_FUNCTIONS")) if (atoi(e) == 1) register_fasta_nuc_function(conn);
+    if (const char *e = getenv("DHTS_ALGEBRA_FUNCTIONS")) if (atoi(e) == 1) { register_interval_merge_function(conn); register_interval_overlap_function(conn); }   // interval_merge, interval_overlap: their place in src/interval_udf.c (PLAN.md 10.5.2), behind a variable of their own
     // the k-mer family follows tabix_index and precedes read_tabix (src/duckhts.c:66), behind a variable of its own: DHTS_KMER_FUNCTIONS=1
     if (const char *e = getenv("DHTS_KMER_FUNCTIONS")) if (atoi(e) == 1) register_kmer_udf_functions(conn);
     // read_tabix, read_gtf, read_gff close the list (src/duckhts.c:67-69), opt-in: DHTS_TABIX_FUNCTIONS=1

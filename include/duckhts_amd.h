@@ -1238,6 +1238,84 @@ double dhts_kernel_time_ms(const dhts_ctx *, int kernel_id, int64_t *launches);
 void dhts_kernel_time_reset(dhts_ctx *);
 void dhts_set_timing(dhts_ctx *, int enabled);
 
+/* ---- interval algebra: interval_merge, interval_overlap ------------------------------------------
+ * BED interval algebra on the device: the rows of a BED file are sorted by (chrom, start) with a radix sort on the device, indexed, and
+ * merged into runs (interval_merge) or joined with the rows of a second file (interval_overlap).  The reference has only a plan for these
+ * (.github/PLAN.md 10.5.2 / 10.7.1; INTEGRATION.md "Interval overlap join" names cgranges as the model of the join), so this is the
+ * specification.
+ *   Rows: those read_bed returns -- meta lines (empty, '#', "track", "browser") do not count; a line with fewer than 3 fields raises
+ *     read_bed's error with its line number.  A row's number is its 0-based index among read_bed's rows.  A row is invalid if its start or
+ *     end is NULL, if end < start, or if start or end lies outside [-2^62, 2^62) (so no sum or difference below can overflow).  Invalid rows
+ *     keep their number, take no part in any result and are counted in n_skipped.  Empty rows (start == end) are valid and follow the
+ *     predicates literally.
+ *   Chrom names are compared byte for byte; chrom order is byte order of the name (memcmp, the shorter name first on a common prefix --
+ *     DuckDB's default ORDER BY on VARCHAR).
+ *   interval_merge(path, max_gap := 0): chrom, start, end, n_merged.  The valid rows sorted by (chrom order, start); within a chrom a row
+ *     joins the current run iff start <= run_end + max_gap, where run_end is the largest end seen in the run -- rows that touch merge at
+ *     max_gap = 0 (bedtools merge -d, and the rule of the count functions' BED merge).  One output row per run: its first start, its run_end,
+ *     the number of rows in it.  Order: (chrom order, start).  max_gap 0 .. 2^40, else "interval_merge: max_gap must be between 0 and
+ *     1099511627776".  No column is ever NULL.
+ *   interval_overlap(path, right_path :=, mode := 'any' | 'contain' | 'within'): chrom, start, end, left_row, right_start, right_end,
+ *     right_row, overlap.  One row per pair (l, r) of valid rows with the same chrom name that satisfies the mode's predicate; with
+ *     l = [s, e) and r = [rs, re):  any: rs < e && s < re (cgranges' cr_overlap);  contain: s <= rs && re <= e && rs < e (cr_contain with l
+ *     as the query);  within: rs <= s && e <= re && s < re (the same with the roles swapped).  overlap = max(0, min(e, re) - max(s, rs)).
+ *     Order: by left_row; within a left row by (right_start, right_row).  A left chrom the right file lacks gives no rows.  No column is
+ *     ever NULL.
+ *   Paging: the concatenation of the pages is the result, whatever max_rows is (0 = 1,048,576).  A page of interval_overlap is the longest
+ *     run of whole left rows, from where the last page ended, whose pairs fit max_rows; it holds at least one left row, so a single left row
+ *     with more pairs than max_rows makes a larger page.
+ *   Limits: fewer than 2^32 - 16 rows per file ("<fn>: more than 4294967279 rows"), fewer than 2^63 pairs.
+ *   Not in this contract: interval_nearest; strand-aware merge; a region parameter; unmatched left rows (a left join) and counts-only output;
+ *     BED columns beyond the first three in the results (rows are identified by left_row / right_row, as the BAM join identifies intervals
+ *     by read_bed's row number); table-valued (subquery) arguments; dhts_bam_set_overlap_intervals and the count functions' BED merge stay
+ *     on their host sort; two files on different devices.
+ *   Method: the batches of the BED context go through the line table and bed_intervals, a compaction appends (name id, start, end, valid)
+ *     per row to arrays in HBM and the host sees chrom names only at the heads of name runs; a stable LSD radix sort of (key, row) pairs,
+ *     8 bits a pass, passes whose digit is equal in all keys skipped (csrc/interval_sort.hip); one gather for beg / end / id, the running
+ *     maximum of (rank, end) through the carry for pmax, bmax per 64 rows; merge: head flags, their scan, a window of runs per page;
+ *     overlap: a count pass with one lane per left row (binary search, walk back by pmax and bmax), a 64-bit carry, a write pass per page
+ *     (csrc/interval_algebra.hip).
+ * Every error is prefixed with the function's name ("interval_merge:", "interval_overlap:"; read_bed's own errors keep "read_bed:").  Every
+ * call on a context in the wrong state fails with a dhts_error that names what is missing. */
+enum { DHTS_IVL_MERGE_CHROM = 0, DHTS_IVL_MERGE_START, DHTS_IVL_MERGE_END, DHTS_IVL_MERGE_N, DHTS_IVL_MERGE_COL_COUNT };
+enum { DHTS_IVL_OV_CHROM = 0, DHTS_IVL_OV_START, DHTS_IVL_OV_END, DHTS_IVL_OV_LEFT_ROW, DHTS_IVL_OV_RIGHT_START, DHTS_IVL_OV_RIGHT_END, DHTS_IVL_OV_RIGHT_ROW,
+       DHTS_IVL_OV_OVERLAP, DHTS_IVL_OV_COL_COUNT };
+enum { DHTS_IVL_ANY = 0, DHTS_IVL_CONTAIN = 1, DHTS_IVL_WITHIN = 2 };      /* mode */
+#define DHTS_IVL_MAX_GAP (1ll << 40)
+typedef struct {
+    uint64_t n_rows;         /* read_bed's rows                                                                */
+    uint64_t n_skipped;      /* invalid rows                                                                   */
+    uint64_t n_chroms;       /* distinct chrom names (of all rows)                                             */
+    uint64_t n_name_runs;    /* heads of name runs the host looked at: chrom changes, and one per batch       */
+    uint64_t n_runs;         /* interval_merge: rows of the result, valid after dhts_ivl_merge_open           */
+    uint64_t n_pairs;        /* interval_overlap: rows of the result, valid after dhts_ivl_overlap_open       */
+    int32_t sort_passes;     /* radix passes that were run (of 12)                                             */
+    int32_t status;          /* 1, or the negative status of a stream that ended on an error; -2: too many rows */
+} dhts_ivl_stats;
+typedef struct {
+    int64_t n_rows;
+    int32_t status;          /* 0 = more rows follow, 1 = the last page                                                                    */
+    int32_t n_cols;          /* DHTS_IVL_MERGE_COL_COUNT or DHTS_IVL_OV_COL_COUNT, in that order                                           */
+    const dhts_col *cols;    /* host array of descriptors, DEVICE pointers inside: fixed = int32 (chrom: the context's name id; for overlap the
+                                left context's) or int64 (every other column) per row, a null pointer for a column colmask left out; no row is
+                                NULL and valid stays a null pointer                                                                         */
+} dhts_ivl_batch;
+/* bed: a context prepared as for read_bed (dhts_open_path, dhts_bgzf_index, dhts_bed_open).  Reads it to its end, max_blocks BGZF blocks a
+ * batch (0 = the default), and leaves the interval table -- the rows, the sort and the index -- on the context. */
+int dhts_ivl_load(dhts_ctx *bed, int64_t max_blocks);
+int dhts_ivl_stats_get(dhts_ctx *bed, dhts_ivl_stats *out);
+/* the chrom name of a name id (ids are given in order of first appearance); NULL for an id out of range */
+const char *dhts_ivl_chrom_name(dhts_ctx *bed, int32_t id, uint64_t *len);
+int dhts_ivl_merge_open(dhts_ctx *bed, int64_t max_gap);
+int dhts_ivl_merge_next(dhts_ctx *bed, int64_t max_rows, uint32_t colmask, dhts_ivl_batch *out);
+/* left and right: two loaded contexts on one device (refused otherwise); right has to stay as it is while the result is paged out.  The
+ * pairs are counted here. */
+int dhts_ivl_overlap_open(dhts_ctx *left, dhts_ctx *right, int32_t mode);
+int dhts_ivl_overlap_next(dhts_ctx *left, int64_t max_rows, uint32_t colmask, dhts_ivl_batch *out);
+/* read-back as for dhts_bedgraph_batch */
+uint64_t dhts_ivl_batch_host_bytes(const dhts_ivl_batch *b);
+int dhts_ivl_batch_fetch(dhts_ctx *bed, const dhts_ivl_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
+
 #ifdef __cplusplus
 }
 #endif

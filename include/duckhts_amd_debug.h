@@ -101,6 +101,14 @@ int64_t dhts_debug_tile_scan(dhts_ctx *, int kernel, uint64_t *first, uint64_t *
 int dhts_debug_diag(dhts_ctx *, unsigned long long *out8);
 int dhts_debug_hw_diag(dhts_ctx *, unsigned long long *out16, int reset);
 int dhts_debug_tr_diag(dhts_ctx *, unsigned long long *out16, int reset);
+/* tests, tools/bench_intervals.py: the interval functions' sort alone (csrc/interval_sort.hip) on host arrays.  keys_u64[n] are compared
+ * unsigned, rank_u32[n] is row i's rank (the more significant part of the order); rows_out_u32[n] receives the row numbers 0 .. n - 1 in
+ * the order of (rank, key), rows of equal (rank, key) in input order.  *passes: the radix passes that were run (a pass whose digit is equal
+ * in all pairs is skipped). */
+int dhts_debug_ivl_sort(dhts_ctx *, const uint64_t *keys_u64, const uint32_t *rank_u32, uint64_t n, uint32_t *rows_out_u32, int32_t *passes);
+/* tools/bench_intervals.py: device time in milliseconds of the parts of the last dhts_ivl_load (0 load, 1 sort, 2 index), dhts_ivl_merge_open
+ * (3), dhts_ivl_overlap_open (4: the count pass and its carry) and of the write passes of the pages taken since (5), and of sort pass p (16 + p) */
+double dhts_debug_ivl_ms(dhts_ctx *, int what);
 
 #ifdef __cplusplus
 }

@@ -605,6 +605,7 @@ static_assert(BR_R >= BR_FLUSH + BR_SPAN + 265u, "far sources must always be flu
 // knock-out experiments (tools/dbg/time_lz.py; the output is wrong on purpose): -DB_EXP_NOCRC, -DB_EXP_NOLIT, -DB_EXP_NOFAR, -DB_EXP_NOROUNDS,
 // -DB_EXP_NOREPLAY, -DB_EXP_NOSTORE, -DB_EXP_NOEPI (the per-block CRC epilogue: the tail's table loop and the combine of the 64 states)
 // leave out one part of the kernel each, so that its cost can be read off the launch time
+// -DB_EXP_ROUND4W (the output stays right): all four windows of an 8..32-byte match made by every such lane, as before round 10
 // (NOROUNDS leaves out the windowed far copies too: round 1 makes them; NOFAR turns far matches into near ones and so removes their loads)
 #ifdef B_EXP_NOSTORE
 #define B_EXP_STORE(p_, v_) do { asm volatile("" :: "v"((v_).x), "v"((v_).y), "v"((v_).z), "v"((v_).w)); } while (0)
@@ -922,8 +923,8 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
             // matches are pending (or a round found nothing it could copy) the rest is replayed one match at a time in stream order
             // -- always ready by construction, no readiness test -- by the whole wave (one byte per lane).
             // One copy body serves the three kinds of ready lane, which differ only in where a window's value comes from: the ring
-            // (near), the replicated source byte (dist 1), or fv* (far).  All loads of a lane come before its stores, so overlapping
-            // sources (1 < dist < len), like matches that wrap in the ring and long ones, stay pending for the sequential replay.
+            // (near), the replicated source byte (dist 1), or fv* (far).  The body never copies from a lane's own destination, so
+            // overlapping sources (1 < dist < len), like matches that wrap in the ring and long ones, stay pending for the sequential replay.
             const uint8_t *sp = win + (farm ? 0u : rs); uint8_t *dp = win + rd;      // (a far lane's loads are discarded: any address)
             const bool d1 = mdist == 1u;
             bool more = P != 0ull;
@@ -936,13 +937,26 @@ __device__ __forceinline__ void lz_block(uint8_t *win, uint32_t *crct, uint8_t *
                 const bool easy = pending && ((smask & owed) == 0ull) && wcopy;
                 if (easy) {
                     if (mlen >= 8u) {
-                        uint64_t v0 = lds_ld64(sp), v1 = lds_ld64(sp + wk1), v2 = lds_ld64(sp + wk2), v3 = lds_ld64(sp + wk3);
+                        // Two windows reach 16 bytes, and most matches are no longer (the bench's average 9.5 bytes): windows 3 and 4 are
+                        // loaded and stored by the longer matches alone, behind the first two.  With all four in one body every lane made
+                        // eight LDS accesses and every store waited for four loads; the instructions issued are what they were, the wave's
+                        // wait for LDS is what fell.  A ready lane's source overlaps neither its own destination nor the
+                        // destination of any lane that stores in this round (earlier pending ones are owed, later ones lie behind it), so
+                        // loads behind the first stores read what they would have read in front of them.
+                        uint64_t v0 = lds_ld64(sp), v1 = lds_ld64(sp + wk1);
                         const uint32_t r4 = __builtin_amdgcn_perm((uint32_t)v0, (uint32_t)v0, 0u);
                         const uint64_t rep = ((uint64_t)r4 << 32) | r4;
                         v0 = farm ? fv0 : d1 ? rep : v0; v1 = farm ? fv1 : d1 ? rep : v1;
-                        v2 = farm ? fv2 : d1 ? rep : v2; v3 = farm ? fv3 : d1 ? rep : v3;
                         __builtin_memcpy(dp, &v0, 8); __builtin_memcpy(dp + wk1, &v1, 8);
-                        __builtin_memcpy(dp + wk2, &v2, 8); __builtin_memcpy(dp + wk3, &v3, 8);
+#ifdef B_EXP_ROUND4W
+                        {
+#else
+                        if (mlen > 16u) {
+#endif
+                            uint64_t v2 = lds_ld64(sp + wk2), v3 = lds_ld64(sp + wk3);
+                            v2 = farm ? fv2 : d1 ? rep : v2; v3 = farm ? fv3 : d1 ? rep : v3;
+                            __builtin_memcpy(dp + wk2, &v2, 8); __builtin_memcpy(dp + wk3, &v3, 8);
+                        }
                     } else if (mlen >= 4u) {
                         const uint32_t k = mlen - 4u;
                         uint32_t a, b; __builtin_memcpy(&a, sp, 4); __builtin_memcpy(&b, sp + k, 4);

@@ -93,7 +93,88 @@ def simulate(toks, W, policy):
         outpos = pos
     return steps, rounds, nm
 
+RING, SPAN, SEQ_T = 4096, 1536, 6          # B_RING_LOG2, BR_SPAN, B_SEQ_T of bgzf_inflate.hip
+
+def kernel_model(toks, ncell, sh0, seq_t=SEQ_T):
+    """lz_block's lane-parallel batches as the kernel runs them: far-big matches placed first, rounds of windowed copies behind the cell
+    test (ncell cells of at least 2^sh0 bytes), the rest replayed as soon as seq_t or fewer are pending or a round copied nothing.
+    Returns a Counter: batches, oversized, matches, rounds, ready[r] (copied by round r), replayed, replay_wait (replayed matches that a
+    windowed copy could have taken: they only waited), and the literal pass's classes per batch."""
+    c = collections.Counter(); outpos = 0
+    for t0 in range(0, len(toks), 64):
+        batch = toks[t0:t0 + 64]
+        tot = sum(lr + ml for lr, ml, _ in batch); lit = sum(lr for lr, _, _ in batch)
+        if tot > SPAN or lit > 1024:
+            c['oversized'] += 1; outpos += tot; continue
+        c['batches'] += 1
+        bend = outpos + tot; rlo = max(bend - RING, 0); pos = outpos; lanes = []
+        n8 = nwin = nexact = nexact4 = 0
+        for lr, ml, di in batch:
+            md = pos + lr
+            # the literal pass: runs of 8..32 bytes (four windows), a short run in front of a match (one 8-byte window when run + match
+            # reach 8 bytes, else one 4-byte window: both end inside the lane's own match), the exact 4 / 2 / 1 classes for the rest
+            if 8 <= lr <= 32: n8 += 1
+            elif 1 <= lr < 8 and ml > 0 and lr + ml >= 8: nwin += 1
+            elif 1 <= lr < 8:
+                nexact += 1; nexact4 += ml > 0
+            if ml > 0:
+                ms = md - di; far = ms < rlo; rs, rd = ms % RING, md % RING
+                wcopy = ml <= 32 and rd + ml <= RING and (far or (rs + ml <= RING and (di >= ml or di == 1)))
+                if not (far and not wcopy): lanes.append((md, ml, ms, min(ml, di), far, wcopy))
+                c['matches'] += 1; c['farbig'] += far and not wcopy
+            pos = md + ml
+        c['lit_has_8plus'] += n8 > 0; c['lit_has_exact'] += nexact > 0; c['lit_has_exact_without_4window'] += nexact > nexact4
+        c['runs_8plus'] += n8; c['runs_window8'] += nwin; c['runs_exact'] += nexact; c['runs_exact_match_behind'] += nexact4
+        sh = sh0
+        while (tot >> sh) > ncell - 1: sh += 1
+        pend = lanes; r = 0
+        while pend:
+            if r and len(pend) <= seq_t: break
+            r += 1; c['rounds'] += 1; owed = 0; keep = []; nready = 0
+            for md, ml, ms, sp, far, wcopy in pend:
+                lo, hi = (md - outpos) >> sh, (md - outpos + ml - 1) >> sh
+                smask = 0
+                if not far and ms + sp > outpos:
+                    slo, shi = (max(ms, outpos) - outpos) >> sh, (ms + sp - 1 - outpos) >> sh
+                    smask = ((1 << (shi + 1)) - 1) & ~((1 << slo) - 1)
+                if wcopy and smask & owed == 0: nready += 1
+                else: keep.append((md, ml, ms, sp, far, wcopy))
+                owed |= ((1 << (hi + 1)) - 1) & ~((1 << lo) - 1)
+            c['ready%d' % min(r, 4)] += nready; pend = keep
+            if nready == 0: break
+        c['replayed'] += len(pend); c['replay_wait'] += sum(1 for x in pend if x[5])
+        outpos = bend
+    return c
+
+def load_synth(nrec):
+    """bench-shaped blocks (duckhts_amd.synth.bam_segment from the middle of the bench's file, host code only)"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+    from duckhts_amd import synth
+    body, _ = synth.bam_segment(nrec, seed=42, total_n=4_000_000, rec0=2_000_000, with_header=False, with_eof=False)
+    data = body.tobytes(); p = 0; out = []
+    while p + 18 <= len(data):
+        bl = struct.unpack_from('<H', data, p + 16)[0] + 1
+        if bl > 28: out.append(tokens_of(data[p + 18:p + bl - 8]))
+        p += bl
+    return out
+
+def report_kernel(blocks):
+    for name, ncell, sh0 in (('64 cells of >= 16 bytes (the kernel)', 64, 4), ('128 cells of >= 8 bytes', 128, 3)):
+        c = collections.Counter()
+        for toks, tail in blocks: c += kernel_model(toks, ncell, sh0)
+        B, M = c['batches'], c['matches'] - c['farbig']
+        print(f"{name}: blocks {len(blocks)} batches {B} oversized {c['oversized']} pending matches/batch {M / B:.1f} far-big {c['farbig'] / B:.2f}")
+        print(f"  rounds/batch {c['rounds'] / B:.3f}  ready in round 1 / 2 / 3 / 4+: " + ' / '.join(f"{100 * c['ready%d' % r] / M:.1f} %" for r in (1, 2, 3, 4))
+              + f"  replayed {100 * c['replayed'] / M:.1f} % = {c['replayed'] / B:.2f} per batch ({c['replay_wait'] / B:.2f} of them only waited)")
+    print(f"literal pass, per batch: runs of 8..32 bytes {c['runs_8plus'] / B:.2f} (in {100 * c['lit_has_8plus'] / B:.1f} % of the batches), "
+          f"1..7 bytes with run + match >= 8 {c['runs_window8'] / B:.2f}, other runs of 1..7 bytes {c['runs_exact'] / B:.2f} "
+          f"({c['runs_exact_match_behind'] / B:.2f} with a match behind); batches with such a run {100 * c['lit_has_exact'] / B:.1f} %, "
+          f"with one that has no match behind {100 * c['lit_has_exact_without_4window'] / B:.1f} %")
+
 if __name__ == '__main__':
+    if sys.argv[1] == '--synth':             # lz_rounds_model.py --synth [records]: the kernel's policy on bench-shaped data
+        report_kernel(load_synth(int(sys.argv[2]) if len(sys.argv) > 2 else 60_000))
+        sys.exit(0)
     blocks = load(sys.argv[1], int(sys.argv[2]), 3)
     for W in (64, 128):
         for pol in ('cell', 'first', 'exact'):

@@ -101,12 +101,12 @@ __device__ __forceinline__ int w_msb64(uint64_t v) { return 63 - __clzll((long l
 #define HW_OFF_TAB (HW_OFF_SD + 128u)                    /* u32 [2][3][16]: per alphabet limit15 / first / offs by code length */
 #define HW_OFF_LRING (HW_OFF_TAB + 384u)                 /* literal ring; while the header is read: u8 [1024 + 8] staged header bytes */
 #define HW_OFF_TRING (HW_OFF_LRING + HW_LRING_BYTES)     /* token ring;   while the tables are built: u8 [320] code lengths */
-#define HW_OFF_IRING (HW_OFF_TRING + HW_TRING_BYTES)      /* input ring: 64 bytes per lane; between two decoding passes: */
+#define HW_OFF_IRING (HW_OFF_TRING + HW_TRING_BYTES)      /* input ring: 64 + 8 bytes per lane; between two decoding passes: */
 #define HW_OFF_X HW_OFF_IRING                            /*   u32 [6][64] lane exchange arrays (never touched while a lane decodes) */
 #define HW_OFF_HX (HW_OFF_TRING + 512u)                  /* u32 [64] exchange array of the header reader (the input ring's space holds its position table) */
 #define HW_OFF_STAGE HW_OFF_LRING
 #define HW_OFF_LENS HW_OFF_TRING
-#define HW_LDS_BYTES (HW_OFF_IRING + 4096u)
+#define HW_LDS_BYTES (HW_OFF_IRING + 4096u + 512u)
 // exchange arrays
 #define HX_START 0
 #define HX_END 1
@@ -204,8 +204,33 @@ W_DEV uint4 hw_tring_chunk(const uint8_t *smem, int lane, uint32_t k) {     // t
     return make_uint4(p[0], p[64], p[128], p[192]);
 }
 
-// input ring: 64 bytes per lane, [16 words][64 lanes]
-#define HW_IRING_AT(smem, lane, k) ((uint32_t *)((smem) + HW_OFF_IRING) + ((k) & 15u) * 64u + (uint32_t)(lane))
+// input ring: 64 bytes per lane, [16 words][64 lanes], plus two MIRROR ROWS [16], [17] that repeat rows 0 and 1: the three words
+// [k, k + 3) of a lane's stream are rows r, r + 1, r + 2 with r = k & 15, without a wrap (HW_IRING_PUT keeps the mirror)
+#define HW_IRING_ROW(smem, lane, r) ((uint32_t *)((smem) + HW_OFF_IRING) + (r) * 64u + (uint32_t)(lane))
+// the 16-byte chunk g_ of the stream (words [4 g_, 4 g_ + 4)) enters the ring; its first two words are written a second time: to the
+// mirror rows when the chunk lies in rows 0..3, else once more to where they already are (no branch)
+#define HW_IRING_PUT(smem, lane, g_, c_) do {                                                                                                        \
+        const uint32_t s_ = ((g_) & 3u) * 4u; uint32_t *p_ = HW_IRING_ROW(smem, lane, s_), *m_ = HW_IRING_ROW(smem, lane, s_ ? s_ : 16u);                 \
+        p_[0] = (c_).x; p_[64] = (c_).y; p_[128] = (c_).z; p_[192] = (c_).w; m_[0] = (c_).x; m_[64] = (c_).y;                                             \
+        HW_SHADOW_PUT(lane, s_, 4u * (g_)); HW_SHADOW_PUT(lane, s_ ? s_ : 16u, 4u * (g_));                                                                \
+    } while (0)
+#ifdef HOSTSIM_W
+// host simulation only: which stream word every ring row of every lane holds (0xffffffff: none).  Every window read asserts that its
+// three rows hold the words w, w + 1, w + 2: the check of the commit invariant, of the mirror rows and of the wrap.
+static uint32_t g_hw_shadow[18][64];
+static unsigned long long g_hw_windows;
+#define HW_SHADOW_RESET(lane) do { for (int r_ = 0; r_ < 18; r_++) g_hw_shadow[r_][lane] = 0xffffffffu; } while (0)
+#define HW_SHADOW_PUT(lane, row_, word_) do { for (uint32_t k_ = 0; k_ < ((row_) < 16u ? 4u : 2u); k_++) g_hw_shadow[(row_) + k_][lane] = (word_) + k_; } while (0)
+#define HW_SHADOW_CHECK(lane, w_, n_) do { g_hw_windows++;                                                                                            \
+        for (uint32_t k_ = 0; k_ < (n_); k_++) { const uint32_t r_ = k_ < 3u ? ((w_) & 15u) + k_ : ((w_) + k_) & 15u; if (g_hw_shadow[r_][lane] != (w_) + k_) { \
+            fprintf(stderr, "input ring: lane %d reads word %u from row %u, which holds word %u\n", lane, (w_) + k_, r_, g_hw_shadow[r_][lane]);          \
+            abort(); } }                                                                                                                                  \
+    } while (0)
+#else
+#define HW_SHADOW_RESET(lane) do { } while (0)
+#define HW_SHADOW_PUT(lane, row_, word_) do { } while (0)
+#define HW_SHADOW_CHECK(lane, w_, n_) do { } while (0)
+#endif
 // The next 16 input bytes of a lane travel global memory -> four VGPRs -> LDS ring WITHOUT the compiler's knowledge (a load the compiler
 // sees is waited for where its result is copied, i.e. right behind the load: every iteration of the loop then costs a memory latency):
 // HW_LOAD16 issues the load, HW_LOAD16_WAIT is the wait; both sit in ONE straight-line loop body (no back edge between them, so the four
@@ -226,33 +251,48 @@ typedef uint32_t hw_u32x4 __attribute__((ext_vector_type(4)));
 
 // One lane decodes the units that START in [start, stop) with the tables in LDS: ONE UNIT per step -- a literal, or a length with
 // its distance (the distance half runs under the execution mask of the lanes that decoded a length) -- so a range boundary always lies
-// between units and no lane carries an alphabet state.  Straight-line arithmetic (masks instead of selects); the branches are the refill
-// of the bit buffer (from the lane's input ring in LDS), the rare code above the table's root, the end-of-block symbol, a literal run
-// of 511 or more in front of a match.  The loop body is four units between two "stage points": the top one requests the lane's next
-// 16 input bytes, the bottom one parks them in the input ring and moves full 16-byte pieces of the output rings to the lane's slice.
+// between units and no lane carries an alphabet state.  Straight-line arithmetic (masks instead of selects); the branches are the rare
+// code above the table's root, the end-of-block symbol, a literal run of 511 or more in front of a match.  The loop body is four units
+// between two "stage points": the top one requests the lane's next 16 input bytes, the bottom one parks them in the input ring and moves
+// full 16-byte pieces of the output rings to the lane's slice.
 // PASS 0: nothing is counted or emitted (proposal of the neighbour's start);  PASS 1: counts and emits into the lane's slice.
 template <int PASS>
 W_DEV void hw_span(uint8_t *smem, const uint32_t *in32, uint32_t start, uint32_t stop, uint32_t limit_bits, uint32_t mask_ll, uint32_t mask_d, uint32_t rll, uint32_t rd, uint32_t subbits,
                    int lane, HwLane &r, uint8_t *lit_out, uint32_t *tok_out, uint32_t lit_cap, uint32_t tok_cap, uint32_t run_in) {
     const uint16_t *lut_ll = (const uint16_t *)(smem + HW_OFF_LL);
     const uint32_t *lut_d = (const uint32_t *)(smem + HW_OFF_D);
-    // input: words [.., wcommit) of the lane's stream are in the ring (word k at ring position k & 15); widx = the next word to enter the
-    // bit buffer, nw = that word (read one refill ahead, so the LDS latency overlaps the decoding of 32 bits)
-    uint32_t lo, hi = 0, cnt, widx, nw, gnext, wcommit;
+    // BIT INPUT: the reader's state is the bit position `pos` alone.  A unit is at most 48 bits (literal/length code <= 15 + 5 extra bits,
+    // distance code <= 15 + 13): once per unit HW_WINDOW reads the three ring words that hold the bits [pos, pos + 64) -- rows r, r + 1,
+    // r + 2 of the lane's column, r = (pos >> 5) & 15, the mirror rows stand in for the wrap -- and aligns them to (hi:lo).  The
+    // literal/length half reads `lo`; HW_ADV(n) shifts the window down by the n <= 22 bits it took, so the distance half reads `lo` again
+    // (64 - 22 >= 32 bits are left, it needs 28).
+    // INVARIANT: chunks [.., gnext) are committed, wcommit = 4 gnext, and the ring still holds the chunks [gnext - 4, gnext).  With
+    // w = pos >> 5 at the top of the loop body, its four units start at most 3 x 48 = 144 bits further on, i.e. in a word <= w + 5
+    // ((31 + 144) >> 5), and a window reaches two words beyond the word of its position: the body reads words up to w + 7, so it needs
+    // wcommit - w >= 8.  Below that the top stage point fetches a chunk and waits for it.  That overwrites chunk gnext - 4, which no
+    // window reaches any more when 4 (gnext - 4) + 3 < w, and wcommit - w <= 7 gives w >= 4 gnext - 7.  One fetch is always enough: the
+    // prologue leaves wcommit - w >= 13, a body moves w by at most 6 words, and it commits a chunk at its bottom unless
+    // gnext - (w >> 2) >= 4, i.e. wcommit - w >= 13: wcommit - w >= 6 at every top, >= 10 behind the fetch.  The chunk requested at the
+    // top replaces chunk gnext - 4 < w >> 2 at the bottom: consumed, because pos only moves forward.
+    // (With HW_LL2 a body is three steps of at most 63 bits and one window each: they start at most 126 bits further on, read words up to
+    // w + 6 and move w by at most 6 words: the same bounds hold.)
+    uint32_t lo, hi, gnext, wcommit;
     {
-        const uint32_t w = start >> 5, o = start & 31u, g0 = w >> 2;
+        const uint32_t g0 = start >> 7;
+        HW_SHADOW_RESET(lane);
         for (uint32_t g = g0; g < g0 + 4u; g++) {
             uint4 c; __builtin_memcpy(&c, in32 + 4u * g, 16);
-            *HW_IRING_AT(smem, lane, 4u * g) = c.x; *HW_IRING_AT(smem, lane, 4u * g + 1u) = c.y; *HW_IRING_AT(smem, lane, 4u * g + 2u) = c.z; *HW_IRING_AT(smem, lane, 4u * g + 3u) = c.w;
+            HW_IRING_PUT(smem, lane, g, c);
         }
         gnext = g0 + 4u; wcommit = 4u * gnext;
-        lo = *HW_IRING_AT(smem, lane, w) >> o; cnt = 32u - o; widx = w + 1u; nw = *HW_IRING_AT(smem, lane, widx);
     }
-    // (the bit buffer holds fewer than 32 bits here, all of them in lo: hi is zero)
-#define HW_REFILL() do {                                                                                                                              \
-        if (cnt < 32u) { lo |= nw << cnt; hi = (nw >> 1) >> (31u - cnt); cnt += 32u; widx++; nw = *HW_IRING_AT(smem, lane, widx); }                       \
+#define HW_WINDOW() do {                                                                                                                              \
+        const uint32_t w_ = pos >> 5; const uint32_t *p_ = HW_IRING_ROW(smem, lane, w_ & 15u);                                                            \
+        HW_SHADOW_CHECK(lane, w_, 3u);                                                                                                                    \
+        const uint32_t w0_ = p_[0], w1_ = p_[64], w2_ = p_[128];                                                                                          \
+        lo = hw_shr64lo(w1_, w0_, pos & 31u); hi = hw_shr64lo(w2_, w1_, pos & 31u);                                                                       \
     } while (0)
-#define HW_TAKE(n_) do { const uint32_t u_ = (n_); lo = hw_shr64lo(hi, lo, u_); hi >>= u_; cnt -= u_; pos += u_; } while (0)
+#define HW_ADV(n_) do { const uint32_t u_ = (n_); lo = hw_shr64lo(hi, lo, u_); hi >>= u_; pos += u_; } while (0)
 #define HW_PUSH_TOK(v_) do { *HW_TRING_AT(smem, lane, ntok) = (v_); ntok++; } while (0)
 #ifdef HW_EXP_NOEMIT            /* knock-out experiment: what the 16-byte stores into the lane's slice cost; the output is invalid */
 #define HW_EXP_CAP(c_) 0u
@@ -275,7 +315,6 @@ W_DEV void hw_span(uint8_t *smem, const uint32_t *in32, uint32_t start, uint32_t
     uint32_t stopv = stop < limit_bits + 64u ? stop : limit_bits + 64u;
     // one literal / length symbol: entry, fields, the literal ring (pass 1), the bits taken, the end of the block
 #define HW_LL() do {                                                                                                                                  \
-            HW_REFILL();                                                                                                                                  \
             e = lut_ll[lo & mask_ll];                                                                                                                     \
             if (HW_ANY((e & 15u) == 0u)) {                                                                                                                \
                 if ((e & 15u) == 0u) {                                                                                                                    \
@@ -293,26 +332,28 @@ W_DEV void hw_span(uint8_t *smem, const uint32_t *in32, uint32_t start, uint32_t
                 *HW_LRING_AT(smem, lane, nlit) = (uint8_t)(e >> 8);                                                                                       \
                 nlit += 1u + islen_m; run += 1u + islen_m;                                                                                                \
             }                                                                                                                                             \
-            HW_TAKE(L + x);                                                                                                                               \
+            HW_ADV(L + x);                                                                                                                                \
             iseob = (e & 0xf0u) == 0xf0u;                                                                                                                 \
             if (HW_ANY(iseob)) { if (iseob) { flags |= HWF_EOB; stopv = 0; pos -= 7u; } }                                                                 \
     } while (0)
-    // ONE step: a literal / length symbol, then the distance of the lanes that hold a length.  -DHW_LL2=1 (round 4, measured and not used:
-    // 9.10 against 9.01 ms per 65,536 blocks, profiles/r04/huff_two_symbols_per_step.txt) gives the lanes whose first symbol was a literal a
-    // SECOND literal / length symbol before the distance half (two thirds of the symbols are literals, and a lane that has decoded one idles
-    // through the distance half): 40 % fewer steps, no less time -- the wave waits on its dependent LDS look-ups, not on its instruction count.
+    // ONE step: a literal / length symbol, then the distance of the lanes that hold a length.  HW_LL2 (the default since round 11) gives
+    // the lanes whose first symbol was a literal a SECOND literal / length symbol before the distance half (two thirds of the symbols are
+    // literals, and a lane that has decoded one idles through the distance half); the three symbols take at most 15 + 20 + 28 = 63 bits,
+    // which the step's one window holds.  Round 4, when the second symbol brought its own refill, measured it slower (9.10 against 9.01 ms
+    // per 65,536 blocks, profiles/r04/huff_two_symbols_per_step.txt); on the window it costs a look-up and a field extraction and is 3 %
+    // faster than one symbol per step in every run.  -DHW_LL2=0 gives one literal / length symbol per step.
     // Every piece ends on a unit boundary, so a range boundary lies between units either way.
 #ifndef HW_LL2
-#define HW_LL2 0
+#define HW_LL2 1
 #endif
 #define HW_UNIT() do {                                                                                                                                \
         if (pos < stopv) {                                                                                                                                \
             uint32_t e, ext, islen_m; bool iseob;                                                                                                         \
+            HW_WINDOW();                                                                                                                                  \
             HW_LL();                                                                                                                                      \
             if (HW_LL2 && islen_m == 0u && pos < stopv) HW_LL();                                                                                          \
             if (islen_m != 0u && !iseob) {                                                                                                                \
                 const uint32_t want3 = (e >> 8) + ext;          /* length - 3 */                                                                          \
-                HW_REFILL();                                                                                                                              \
                 uint32_t d = lut_d[lo & mask_d];                                                                                                          \
                 if (HW_ANY((d & 15u) == 0u)) {                                                                                                            \
                     if ((d & 15u) == 0u) {                                                                                                                \
@@ -322,7 +363,7 @@ W_DEV void hw_span(uint8_t *smem, const uint32_t *in32, uint32_t start, uint32_t
                 }                                                                                                                                         \
                 const uint32_t L2 = d & 15u, x2 = (d >> 4) & 15u;                                                                                         \
                 const uint32_t dist1 = (d >> 16) + hw_bfe(lo, L2, x2);      /* distance - 1 */                                                            \
-                HW_TAKE(L2 + x2);                                                                                                                         \
+                pos += L2 + x2;                                                                                                                           \
                 if (PASS == 1) {                                                                                                                          \
                     if (HW_ANY(run >= DHTS_TOK_PURE)) {                                                                                                   \
                         while (run >= DHTS_TOK_PURE) {             /* 511 literals or more in front of this match: "511 literals, no match" tokens */     \
@@ -339,120 +380,40 @@ W_DEV void hw_span(uint8_t *smem, const uint32_t *in32, uint32_t start, uint32_t
 #if defined(HOSTSIM_W) && defined(HW_STATS)
     g_hw_it[lane] = 0;
 #endif
-#ifdef HW_PER_SYMBOL           /* (not the default: measured slower, see below) */
-    // ONE SYMBOL per step, the same instructions for both alphabets (round 4).  A lane is either in front of a literal / length code or -- `ind`
-    // -- in front of the distance code of the length it has just read; the two cases differ in the table they index, in two field widths
-    // and in what the value means, all of which are selects, not branches.  A unit-per-step loop made every lane walk through the distance
-    // half in every step because SOME lane of 64 always holds a length (a third of the units are matches), although two thirds of the
-    // lanes had nothing to do there.  A range still ends between units: a lane that has read a length goes on to its distance whatever
-    // `stopv` says.  MEASURED AND NOT USED (profiles/r04/pmc_sq_per_unit_vs_per_symbol.txt, huff_per_unit_vs_per_symbol.txt): the
-    // symbol step costs ~93 wave-instructions as compiled, a unit step ~110, and a unit is 1.33 symbols: 80.0 k instead of 70.8 k
-    // wave-instructions per BGZF block, 10.1 instead of 9.0 ms per 65,536 blocks.  It would need < 83 per step to pay.  Kept because it is
-    // exact (host simulation, word for word the lane kernel's output) and is the shape a hand-scheduled version would start from.
-    // (`ind` is kept as 0 / 1 in a vector register and the bookkeeping is arithmetic on it: a bool makes the compiler juggle lane masks on the
-    //  scalar unit, and scalar instructions take the same issue slots)
-    uint32_t ind = 0, want3p = 0;                             // want3p = (length - 3) + 3 of the pending match
-#define HW_SYM() do {                                                                                                                                 \
-        if (pos < stopv || ind != 0u) {                                                                                                                   \
-            HW_REFILL();                                                                                                                                  \
-            const uint32_t a_ll = (lo & mask_ll) << 1, a_d = HW_OFF_D + ((lo & mask_d) << 2);                                                              \
-            uint32_t e; __builtin_memcpy(&e, smem + (ind ? a_d : a_ll), 4);   /* (a literal/length entry is the low half: the fields below never look higher) */ \
-            if (HW_ANY((e & 15u) == 0u)) {                                                                                                                \
-                if ((e & 15u) == 0u) {                                                                                                                    \
-                    if (ind) e = !(e & HW_LONG) ? 0u : hw_long_code(smem, lo, 1u, rd);                                                                    \
-                    else if (e & 0x20u) e = ((const uint16_t *)(smem + HW_OFF_SUB))[(((e & 0xffffu) >> 6) << subbits) + hw_bfe(lo, rll, subbits)];          \
-                    else e = (e & HW_LONG) ? hw_long_code(smem, lo, 0u, rll) : 0u;                                                                        \
-                    if ((e & 15u) == 0u) { flags |= HWF_BAD; stopv = 0; e = 0x0001u; ind = 0u; }                                                          \
-                }                                                                                                                                         \
-            }                                                                                                                                             \
-            const uint32_t L = e & 15u, x = hw_bfe(e, 4u, 3u + ind);                                                                                      \
-            const uint32_t k8 = 8u << ind, val = hw_bfe(e, k8, k8) + hw_bfe(lo, L, x);   /* literal byte | length - 3 | distance - 1 (an end-of-block entry asks for 7 bits: given back below) */ \
-            const uint32_t lenb = hw_bfe(e, 7u, 1u) & ~ind;            /* 1: a length code (or the end of the block) */                                     \
-            const uint32_t litv = (lenb | ind) ^ 1u;                   /* 1: a literal */                                                                  \
-            HW_TAKE(L + x);                                                                                                                               \
-            if (PASS == 1) {                                                                                                                              \
-                /* both rings are written every time; a cursor moves only when the symbol was what the ring holds */                                      \
-                *HW_LRING_AT(smem, lane, nlit) = (uint8_t)val;                                                                                            \
-                nlit += litv; run += litv;                                                                                                                \
-                *HW_TRING_AT(smem, lane, ntok) = (run << 23) | ((want3p - 3u) << 15) | val;                                                               \
-                mbytes += ind * want3p;                                                                                                                   \
-            }                                                                                                                                             \
-            /* the rare cases in one test: the end of the block, and (pass 1) a match behind 511 literals or more, whose token was not right */           \
-            if (HW_ANY((lenb != 0u && (e & 0x70u) == 0x70u) || (PASS == 1 && ind != 0u && run >= DHTS_TOK_PURE))) {                                        \
-                if (lenb != 0u && (e & 0x70u) == 0x70u) { flags |= HWF_EOB; stopv = 0; pos -= 7u; }                                                       \
-                else if (PASS == 1 && ind != 0u && run >= DHTS_TOK_PURE) {                                                                                \
-                    while (run >= DHTS_TOK_PURE) {                 /* "511 literals, no match" tokens in front of the match's own */                      \
-                        HW_PUSH_TOK(DHTS_TOK_PURE << 23); run -= DHTS_TOK_PURE;                                                                           \
-                        if (ntok - tfl >= 4u) HW_FLUSH_TOK();                                                                                             \
-                    }                                                                                                                                     \
-                    *HW_TRING_AT(smem, lane, ntok) = (run << 23) | ((want3p - 3u) << 15) | val;                                                           \
-                }                                                                                                                                         \
-            }                                                                                                                                             \
-            if (PASS == 1) { ntok += ind; run &= ind - 1u; }                                                                                              \
-            want3p = lenb ? val + 3u : want3p;                                                                                                            \
-            ind = lenb & (flags ^ HWF_EOB);                            /* (bit 0 of flags is HWF_EOB: a lane that has just seen it has no distance to read) */ \
-        }                                                                                                                                                 \
-    } while (0)
-    hw_u32x4 inq; inq.x = 0; inq.y = 0; inq.z = 0; inq.w = 0;
-    while (pos < stopv || ind != 0u) {
-#if defined(HOSTSIM_W) && defined(HW_STATS)
-        g_hw_it[lane]++;
-#endif
-        // stage points as in the per-unit loop below: six symbols take at most 21 bytes
-        if (wcommit - widx < 8u) {
-            const uint32_t *gp = in32 + 4u * gnext; hw_u32x4 now; HW_LOAD16(now, gp); HW_LOAD16_WAIT(now);
-            *HW_IRING_AT(smem, lane, 4u * gnext) = now.x; *HW_IRING_AT(smem, lane, 4u * gnext + 1u) = now.y; *HW_IRING_AT(smem, lane, 4u * gnext + 2u) = now.z; *HW_IRING_AT(smem, lane, 4u * gnext + 3u) = now.w;
-            gnext++; wcommit += 4u;
-        }
-        const bool req = gnext - (widx >> 2) < 4u;
-        if (req) { const uint32_t *gp = in32 + 4u * gnext; HW_LOAD16(inq, gp); }
-        HW_SYM(); HW_SYM(); HW_SYM(); HW_SYM(); HW_SYM(); HW_SYM();
-        HW_LOAD16_WAIT(inq);
-        if (req) {
-            *HW_IRING_AT(smem, lane, 4u * gnext) = inq.x; *HW_IRING_AT(smem, lane, 4u * gnext + 1u) = inq.y; *HW_IRING_AT(smem, lane, 4u * gnext + 2u) = inq.z; *HW_IRING_AT(smem, lane, 4u * gnext + 3u) = inq.w;
-            gnext++; wcommit += 4u;
-        }
-        if (PASS == 1) {
-            // at most three new tokens and six new literals since the last stage point (a match with a very long literal run flushes for itself)
-            if (ntok - tfl >= 4u) HW_FLUSH_TOK();
-            if (nlit - lfl >= 16u) HW_FLUSH_LIT();
-        }
-    }
-#undef HW_SYM
-#else
     hw_u32x4 inq; inq.x = 0; inq.y = 0; inq.z = 0; inq.w = 0;
     while (pos < stopv) {
 #if defined(HOSTSIM_W) && defined(HW_STATS)
         g_hw_it[lane]++;
 #endif
-        // stage point: four units take at most 24 bytes (6 words) and the refill reads one word ahead: with fewer than 8 words in the ring
-        // beyond widx the lane fetches its next 16 bytes and waits for them (a rare burst of long matches); otherwise it requests
-        // them when the ring has a free slot (the chunks [widx / 4, gnext) are in it or on their way) and collects them four units later
-        if (wcommit - widx < 8u) {
+        // stage point (see INVARIANT above): the four units read words up to (pos >> 5) + 7.  With fewer than 8 committed words from
+        // the word of pos on, the lane fetches its next 16 bytes and waits for them (a rare burst of long matches); otherwise it requests
+        // them when the ring has a free slot (the chunks [pos / 128, gnext) are in it or on their way) and collects them four units later
+        const uint32_t wtop = pos >> 5;
+        if (wcommit - wtop < 8u) {
             const uint32_t *gp = in32 + 4u * gnext; hw_u32x4 now; HW_LOAD16(now, gp); HW_LOAD16_WAIT(now);
-            *HW_IRING_AT(smem, lane, 4u * gnext) = now.x; *HW_IRING_AT(smem, lane, 4u * gnext + 1u) = now.y; *HW_IRING_AT(smem, lane, 4u * gnext + 2u) = now.z; *HW_IRING_AT(smem, lane, 4u * gnext + 3u) = now.w;
+            HW_IRING_PUT(smem, lane, gnext, now);
             gnext++; wcommit += 4u;
         }
-        const bool req = gnext - (widx >> 2) < 4u;
+        const bool req = gnext - (wtop >> 2) < 4u;
         if (req) { const uint32_t *gp = in32 + 4u * gnext; HW_LOAD16(inq, gp); }
 #if HW_LL2
-        HW_UNIT(); HW_UNIT(); HW_UNIT();                     // (three steps of at most 20 + 20 + 28 bits: 26 bytes, within the 28 the ring holds ahead)
+        HW_UNIT(); HW_UNIT(); HW_UNIT();                     // (three steps of at most 15 + 20 + 28 = 63 bits, one window each: words up to (pos >> 5) + 6)
 #else
         HW_UNIT(); HW_UNIT(); HW_UNIT(); HW_UNIT();
 #endif
         // stage point: the requested bytes have arrived (the load is four units old; so are the stores of the previous stage point)
         HW_LOAD16_WAIT(inq);
         if (req) {
-            *HW_IRING_AT(smem, lane, 4u * gnext) = inq.x; *HW_IRING_AT(smem, lane, 4u * gnext + 1u) = inq.y; *HW_IRING_AT(smem, lane, 4u * gnext + 2u) = inq.z; *HW_IRING_AT(smem, lane, 4u * gnext + 3u) = inq.w;
+            HW_IRING_PUT(smem, lane, gnext, inq);
             gnext++; wcommit += 4u;
         }
         if (PASS == 1) {
-            // at most four new entries per ring since the last stage point (a match with a very long literal run flushes for itself)
+            // at most three new tokens and six new literals since the last stage point, four and four with HW_LL2 off (a match with a very
+            // long literal run flushes for itself)
             if (ntok - tfl >= 4u) HW_FLUSH_TOK();
             if (nlit - lfl >= 16u) HW_FLUSH_LIT();
         }
     }
-#endif
     if (!(flags & HWF_EOB) && pos > limit_bits) flags |= HWF_BAD;            // ran off the payload (a true stream ends with its end-of-block symbol)
     if (PASS == 1) {
         // what is still in the rings: whole pieces first, then single entries (nothing is ever stored beyond the lane's counts)
@@ -464,8 +425,9 @@ W_DEV void hw_span(uint8_t *smem, const uint32_t *in32, uint32_t start, uint32_t
     }
     r.end = pos; r.flags = flags;
 #undef HW_UNIT
-#undef HW_REFILL
-#undef HW_TAKE
+#undef HW_WINDOW
+#undef HW_ADV
+#undef HW_LL
 #undef HW_PUSH_TOK
 #undef HW_FLUSH_TOK
 #undef HW_FLUSH_LIT

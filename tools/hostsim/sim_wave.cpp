@@ -128,6 +128,7 @@ int main(int argc, char **argv) {
         printf("%s: blocks %lld failed %d mismatching %d differing-from-lane-kernel %d (LDS=%d)\n", argv[a], (long long)nb, bad, mism, differ, (int)HW_LDS_BYTES);
         if (mism || differ || (bad && !damaged)) rc = 1;
     }
+    printf("input-ring windows read, each checked against the shadow of the ring: %llu\n", g_hw_windows);
 #ifdef HW_STATS
     printf("segments %llu; pass-1 rounds executed (by round index):", g_hw_stat_seg);
     for (int i = 0; i < 8; i++) printf(" %llu", g_hw_stat_p1[i]);

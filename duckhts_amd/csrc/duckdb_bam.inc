@@ -34,45 +34,29 @@ struct BamBind {
 //                  exactly like the reference's own parallel mode (contig-parallel, src/bam_reader.c:577-585, 689-716).
 //   DHTS_DEVICES = 0,1,...: one producer per listed GPU, each staging and scanning its own BGZF block range of the file.
 struct HostTag { std::vector<uint8_t> valid, bytes; std::vector<int64_t> fixed; std::vector<uint32_t> off; std::vector<int64_t> child; };
-struct HostBatch {
-    void *arena = nullptr; uint64_t cap = 0;
+struct HostBatch : PipeSlot {
     dhts_bam_batch b;                 // HOST pointers for the core columns
-    int64_t n = 0; int status = 0;
     std::vector<HostTag> tags;
-    std::vector<uint8_t> aux_valid; std::vector<uint32_t> aux_off; std::vector<std::string> aux_key, aux_val;
+    std::vector<uint8_t> aux_valid; std::vector<uint32_t> aux_off, aux_koff, aux_voff; std::string aux_keys, aux_vals;    // the auxiliary map, laid out as a dhts_tabix_map
     std::vector<uint32_t> qual_lut;   // QUAL as 2- / 4-bit codes (dhts_bam_batch.qual_bits): code byte -> its 4 / 2 characters, built when the batch's bytes have landed
-    // parallel mode
-    int64_t next = 0; int readers = 0; bool retired = false;
 };
-struct Producer {
-    int device = 0, rank = 0, world = 1;
-    std::thread th;
-    std::deque<HostBatch *> ready; std::vector<HostBatch *> free_slots; std::vector<HostBatch *> all;
-    bool done = false;
-    // where this rank's rows begin and end in the file, as BGZF virtual offsets: adjacent ranks must meet exactly (SURVEY 8(e) hand-off)
-    bool has_rows = false, clean_end = false; uint64_t first_v = 0, end_v = 0;
-};
+typedef Pipeline<HostBatch> BamPipe;
+// one producer's share of the file; where its rows begin and end, as BGZF virtual offsets: adjacent ranks must meet exactly (SURVEY 8(e) hand-off)
+struct Shard { int device = 0, rank = 0, world = 1; bool has_rows = false; uint64_t first_v = 0, end_v = 0; };
 struct BamScan {
     BamBind *bind = nullptr;
     std::vector<idx_t> column_ids; uint32_t colmask = 0;
     std::vector<int32_t> tag_ids; std::vector<int> tag_slot; bool want_aux = false;
-    int n_workers = 1;
-    std::mutex mu; std::condition_variable cv_ready, cv_free;
-    std::vector<Producer *> prod; size_t cur_prod = 0;
-    std::string error; bool cancel = false, handoff_checked = false;
+    std::vector<Shard> shard;                                            // one per source of `pipe`
     std::vector<uint8_t> index_bytes;
     std::vector<uint64_t> seg_beg, seg_end; int64_t seg_count = -1;      // region query: the file byte ranges to stage (-1: the whole file)
-    ~BamScan() {
-        { std::lock_guard<std::mutex> lk(mu); cancel = true; }
-        cv_free.notify_all(); cv_ready.notify_all();
-        for (auto p : prod) { if (p->th.joinable()) p->th.join(); for (auto hb : p->all) { dhts_host_free(hb->arena); delete hb; } delete p; }
-    }
+    BamPipe pipe;
+    ~BamScan() { pipe.teardown(); }                                      // (joins the producers, which read the fields above)
 };
 struct BamLocal {
     std::vector<char> seq_tmp;         // packed SEQ expands here before it is assigned
     std::vector<char> qual_tmp;        // packed QUAL: a row that starts inside a code byte is expanded here first
-    bool done = false;
-    HostBatch *cur = nullptr; Producer *cur_owner = nullptr; int64_t pos = 0, end = 0;     // rows [pos, end) of `cur` are this worker's
+    BamPipe::Cursor at;
 };
 
 static void destroy_bind(void *p) { BamBind *b = (BamBind *)p; if (!b) return; if (b->ctx) dhts_destroy(b->ctx); delete b; }
@@ -197,11 +181,11 @@ static int fetch_optional(dhts_ctx *c, BamScan *g, const dhts_bam_batch &b, Host
         if (ne && (dhts_memcpy_d2h(c, key.data(), am.key, ne * 2) || dhts_memcpy_d2h(c, kind.data(), am.kind, ne) || dhts_memcpy_d2h(c, sub.data(), am.sub, ne))) return -1;
         if (dhts_memcpy_d2h(c, po.data(), am.pay_off, (ne + 1) * 4)) return -1;
         if (am.payload_bytes && dhts_memcpy_d2h(c, pay.data(), am.payload, am.payload_bytes)) return -1;
-        hb->aux_key.assign(ne, std::string()); hb->aux_val.assign(ne, std::string());
+        hb->aux_keys.clear(); hb->aux_vals.clear(); hb->aux_koff.assign(1, 0); hb->aux_voff.assign(1, 0);
         char tmp[64];
         for (size_t i = 0; i < ne; i++) {
             char kb[3] = {(char)(key[i] & 0xff), (char)(key[i] >> 8), 0};
-            hb->aux_key[i] = kb;
+            hb->aux_keys += kb; hb->aux_koff.push_back((uint32_t)hb->aux_keys.size());
             const uint8_t *p = pay.data() + po[i]; const size_t pl = po[i + 1] - po[i];
             std::string v;
             int64_t iv; double dv;
@@ -213,7 +197,7 @@ static int fetch_optional(dhts_ctx *c, BamScan *g, const dhts_bam_batch &b, Host
             case 5: v.push_back((char)sub[i]); for (size_t q = 0; q < pl / 8; q++) { memcpy(&dv, p + 8 * q, 8); snprintf(tmp, sizeof tmp, ",%g", dv); v += tmp; } break;
             default: break;
             }
-            hb->aux_val[i] = v.c_str();                              // C-string semantics: cut at the first NUL
+            hb->aux_vals += v.c_str(); hb->aux_voff.push_back((uint32_t)hb->aux_vals.size());     // C-string semantics: cut at the first NUL
         }
     }
     hb->tags.resize(b.n_tag_cols);
@@ -251,29 +235,26 @@ static inline void expand_qual(const uint8_t *stream, int bits, const uint32_t *
     else for (uint32_t k = 0; k < nb; k++) { const uint16_t v = (uint16_t)lut[stream[first + k]]; memcpy(w + 2 * k, &v, 2); }
     if (skip) memcpy(out, w + skip, n);
 }
-static void producer_main(BamScan *g, Producer *p) {
-    BamBind *bind = g->bind;
+static void producer_main(BamScan *g, size_t k) {
+    BamBind *bind = g->bind; BamPipe &pipe = g->pipe; BamPipe::Source &src = *pipe.src[k]; Shard *p = &g->shard[k];
     static const bool trace = getenv("DHTS_TRACE") != nullptr;       // stage timings of every producer on stderr
-    const double t_start = now_s(); double t_open = 0, t_gpu = 0, t_fetch = 0, t_slot = 0, t_wait = 0, t_index = 0; int64_t n_batches = 0, n_rows = 0, n_index = 0;
-    auto fail_with = [&](const std::string &msg) {
-        std::lock_guard<std::mutex> lk(g->mu);
-        if (g->error.empty()) g->error = msg;
-        p->done = true; g->cv_ready.notify_all();
-    };
+    const double t_start = now_s(); double t_open = 0, t_gpu = 0, t_fetch = 0, t_slot = 0, t_ext[2] = {0, 0}; int64_t n_batches = 0, n_rows = 0, n_index = 0;
     // the producer, the staging readers it starts and the pinned arenas it allocates live on the NUMA node of its GPU
     const int numa_rc = dhts_bind_thread_near_device(p->device);
     if (trace) fprintf(stderr, "[dhts] producer %d: device %d on NUMA node %d (%s)\n", p->rank, p->device, dhts_device_numa_node(p->device), numa_rc == 0 ? "bound" : numa_rc == 1 ? "not bound" : "bind failed");
     dhts_ctx *c = dhts_create(p->device);
+    // the context dies before the producer reports done: its HBM goes back to the pool for the next query
+    auto fail_with = [&](std::string msg) { if (c) dhts_destroy(c); pipe.finish(src, msg); };
+    auto fail = [&] { fail_with(dhts_error(c)); };
     if (!c) { fail_with(no_device_message("read_bam")); return; }
     dhts_set_super_blocks(c, 196608);                    // a scratch the device pool keeps from query to query (29 GB instead of 67 GB for a 10 GB file)
-    { static const bool env_qraw = getenv("DHTS_QUAL_PACKED") && atoi(getenv("DHTS_QUAL_PACKED")) == 0; dhts_bam_set_qual_packed(c, env_qraw ? 0 : 1); }         // QUAL crosses PCIe as 2- / 4-bit codes when the batch holds at most 4 / 16 different characters
-    { static const bool env_unpacked = getenv("DHTS_SEQ_PACKED") && atoi(getenv("DHTS_SEQ_PACKED")) == 0; dhts_bam_set_seq_packed(c, env_unpacked ? 0 : 1); }   // SEQ crosses PCIe as 4-bit codes, the fill threads expand it
+    dhts_bam_set_qual_packed(c, env_is_zero("DHTS_QUAL_PACKED") ? 0 : 1);     // QUAL crosses PCIe as 2- / 4-bit codes when the batch holds at most 4 / 16 different characters
+    dhts_bam_set_seq_packed(c, env_is_zero("DHTS_SEQ_PACKED") ? 0 : 1);       // SEQ crosses PCIe as 4-bit codes, the fill threads expand it
     const double t_created = now_s() - t_start; double t_staged = 0;
     int rc;
     // a plain whole-file scan on one device starts decoding while the file is still being staged: the block table is built over the
     // resident prefix and extended as more bytes arrive (DHTS_STREAM=0 stages the whole file first)
-    static const bool env_nostream = getenv("DHTS_STREAM") && atoi(getenv("DHTS_STREAM")) == 0;
-    const bool streaming = p->world == 1 && bind->region.empty() && !env_nostream && (dhts_bam_is_text(bind->ctx) == 0 || dhts_bam_is_text(bind->ctx) % 2 != 0);   // (uncompressed text -- 2, 4, 6 -- is staged first)
+    const bool streaming = p->world == 1 && bind->region.empty() && env_stream() && (dhts_bam_is_text(bind->ctx) == 0 || dhts_bam_is_text(bind->ctx) % 2 != 0);   // (uncompressed text -- 2, 4, 6 -- is staged first)
     int staged_all = 1;
     if (g->seg_count >= 0) rc = dhts_open_path_segments(c, bind->path.c_str(), bind->header_bytes, g->seg_beg.data(), g->seg_end.data(), g->seg_count);
     else if (p->world > 1) rc = dhts_open_path_shard(c, bind->path.c_str(), p->rank, p->world, bind->header_bytes);
@@ -289,18 +270,8 @@ static void producer_main(BamScan *g, Producer *p) {
         if (rc == 0 && dhts_bam_open(c) != 0) rc = -1;
         t_hdr = now_s() - q1;
     }
-    if (rc == 0 && streaming) {
-        // the header needs the first blocks only: start with what the bind saw, four times more whenever that is not enough
-        uint64_t want = bind->header_bytes + (32u << 20);
-        for (;;) {
-            const int64_t f = dhts_stage_wait(c, want, &staged_all);
-            if (f < 0) { rc = -1; break; }
-            if (dhts_bgzf_index_staged(c) > 0 && dhts_bam_open(c) == 0) break;
-            if (staged_all) { rc = -1; break; }
-            want *= 4;
-        }
-    }
-    if (rc != 0) { std::string m = std::string("Failed to open SAM/BAM/CRAM file: ") + bind->path; dhts_destroy(c); fail_with(m); return; }
+    if (rc == 0 && streaming) rc = stream_open(c, bind->header_bytes + (32u << 20), &staged_all, dhts_bam_open);     // start with what the bind saw
+    if (rc != 0) { fail_with(std::string("Failed to open SAM/BAM/CRAM file: ") + bind->path); return; }
     t_open = now_s() - t_start;
     dhts_bam_set_tag_columns(c, g->tag_ids.data(), (int32_t)g->tag_ids.size());
     dhts_bam_set_aux_map(c, g->want_aux ? 1 : 0, bind->standard_tags);
@@ -310,73 +281,45 @@ static void producer_main(BamScan *g, Producer *p) {
     } else rc = dhts_bam_set_regions(c, nullptr);
     if (rc == 0 && p->world > 1) rc = dhts_bam_set_file_shard(c, p->rank, p->world);
     else if (rc == 0 && bind->region.empty()) rc = dhts_bam_rewind(c);
-    if (rc != 0) { std::string m = dhts_error(c); dhts_destroy(c); fail_with(m); return; }
-    static const int64_t env_mb = getenv("DHTS_BATCH_BLOCKS") ? atoll(getenv("DHTS_BATCH_BLOCKS")) : 0;
-    const int64_t max_blocks = env_mb > 0 ? env_mb : 4096;       // ~270 MB of inflated stream per batch: the engine gets its first chunk early and the stages overlap
-    HostBatch *pending = nullptr; int pending_slot = 0, slot_no = 0;
+    if (rc != 0) { fail(); return; }
+    const int64_t max_blocks = env_batch_blocks(4096);           // ~270 MB of inflated stream per batch: the engine gets its first chunk early and the stages overlap
     int64_t n_qual[3] = {0, 0, 0};                               // batches whose QUAL crossed PCIe as 2-bit codes / 4-bit codes / characters
-    auto publish = [&](HostBatch *hb, int sl) -> bool {
-        if (dhts_bam_batch_fetch_wait(c, sl) != 0) return false;
-        build_qual_lut(hb);
-        { std::lock_guard<std::mutex> lk(g->mu); p->ready.push_back(hb); }
-        g->cv_ready.notify_all();
-        return true;
-    };
+    dhts_bam_batch b;
+    // the read-back of a batch runs on a copy stream while the next batch is scanned: the batch is handed to the fill threads one turn
+    // later, when its bytes have had a whole scan's time to cross PCIe (DHTS_OVERLAP_READBACK=0: copy, wait, hand over)
+    auto rb = make_readback(pipe, src, !env_overlap_readback(),
+                            [&](HostBatch *hb) { return dhts_bam_batch_fetch(c, &b, g->colmask, hb->arena, hb->cap, &hb->b) == 0; },
+                            [&](HostBatch *hb, int sl) { return dhts_bam_batch_fetch_begin(c, &b, g->colmask, hb->arena, hb->cap, &hb->b, sl) == 0; },
+                            [&](int sl) { return dhts_bam_batch_fetch_wait(c, sl) == 0; }, build_qual_lut);
     for (;;) {
-        dhts_bam_batch b;
-        if (streaming && !staged_all && dhts_blocks_ahead(c) < max_blocks) {
-            // not enough known blocks for a full batch: wait for (at least) another 128 MiB of the file, then extend the block table
-            const double tw0 = now_s();
-            int64_t f = dhts_stage_wait(c, 0, &staged_all);
-            if (f >= 0 && !staged_all) f = dhts_stage_wait(c, (uint64_t)f + (128u << 20), &staged_all);
-            const double tw1 = now_s(); t_wait += tw1 - tw0;
-            if (f < 0 || dhts_bgzf_index_staged(c) < 0) { std::string m = dhts_error(c); dhts_destroy(c); fail_with(m); return; }
-            t_index += now_s() - tw1; n_index++;
-        }
+        if (streaming) { const int e = stream_extend(c, max_blocks, &staged_all, t_ext); if (e < 0) { fail(); return; } n_index += e; }
         const double tb0 = now_s();
-        if (dhts_bam_next_batch(c, max_blocks, g->colmask, &b) != 0) { std::string m = dhts_error(c); dhts_destroy(c); fail_with(m); return; }
+        if (dhts_bam_next_batch(c, max_blocks, g->colmask, &b) != 0) { fail(); return; }
         const double tb1 = now_s(); t_gpu += tb1 - tb0; n_batches++; n_rows += b.n_rows;
         if (b.n_rows > 0) {
-            HostBatch *hb = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(g->mu);
-                g->cv_free.wait(lk, [&] { return g->cancel || !p->free_slots.empty(); });
-                if (g->cancel) break;
-                hb = p->free_slots.back(); p->free_slots.pop_back();
-            }
+            HostBatch *hb = pipe.take_slot(src);
+            if (!hb) break;
             const double tb2 = now_s(); t_slot += tb2 - tb1;
-            const uint64_t need = dhts_bam_batch_host_bytes(&b, g->colmask);
-            if (need > hb->cap) { dhts_host_free(hb->arena); hb->arena = dhts_host_alloc(need); hb->cap = hb->arena ? need : 0; }
-            // the read-back of this batch runs on a copy stream while the next batch is scanned: the batch is handed to the fill threads one
-            // turn later, when its bytes have had a whole scan's time to cross PCIe (DHTS_OVERLAP_READBACK=0: copy, wait, hand over)
-            static const bool env_serial = getenv("DHTS_OVERLAP_READBACK") && atoi(getenv("DHTS_OVERLAP_READBACK")) == 0;
-            const int frc = env_serial ? dhts_bam_batch_fetch(c, &b, g->colmask, hb->arena, hb->cap, &hb->b) : dhts_bam_batch_fetch_begin(c, &b, g->colmask, hb->arena, hb->cap, &hb->b, slot_no);
-            if ((need && !hb->arena) || frc != 0 || fetch_optional(c, g, b, hb) != 0) {
-                std::string m = hb->arena || !need ? dhts_error(c) : "read_bam: out of pinned host memory"; dhts_destroy(c); fail_with(m); return;
-            }
+            if (!pipe.reserve(hb, dhts_bam_batch_host_bytes(&b, g->colmask))) { fail_with("read_bam: out of pinned host memory"); return; }
+            if (!rb.begin(hb) || fetch_optional(c, g, b, hb) != 0) { fail(); return; }
             hb->n = b.n_rows; hb->status = b.status; hb->next = 0; hb->readers = 0; hb->retired = false;
             if (g->colmask & (1u << DHTS_BAM_QUAL)) n_qual[hb->b.qual_bits == 2 ? 0 : hb->b.qual_bits == 4 ? 1 : 2]++;
             if (!p->has_rows) { p->has_rows = true; p->first_v = dhts_voffset(c, b.first_rec_uoff); }
             p->end_v = dhts_voffset(c, b.end_uoff);
-            if (pending && !publish(pending, pending_slot)) { std::string m = dhts_error(c); dhts_destroy(c); fail_with(m); return; }
-            pending = nullptr;
-            if (env_serial) { build_qual_lut(hb); std::lock_guard<std::mutex> lk(g->mu); p->ready.push_back(hb); }
-            else { pending = hb; pending_slot = slot_no; slot_no ^= 1; }
-            if (env_serial) g->cv_ready.notify_all();
+            if (!rb.turn(hb)) { fail(); return; }
             t_fetch += now_s() - tb2;
         }
-        if (b.status != 0) { p->clean_end = b.status == 1; break; }       // end of the stream, or the silent stop at the first bad block / record (bam_reader.c:754-766)
-        { std::lock_guard<std::mutex> lk(g->mu); if (g->cancel) break; }
+        if (b.status != 0) { src.clean_end = b.status == 1; break; }       // end of the stream, or the silent stop at the first bad block / record (bam_reader.c:754-766)
+        if (pipe.cancelled()) break;
     }
-    if (pending && !publish(pending, pending_slot)) { std::string m = dhts_error(c); dhts_destroy(c); fail_with(m); return; }
+    if (!rb.flush()) { fail(); return; }
     dhts_destroy(c);
     if (trace) { uint64_t mc = 0, mb = 0; double ms = 0; dhts_debug_malloc_stats(&mc, &mb, &ms); fprintf(stderr, "[dhts] hipMalloc calls the pool could not serve so far in this process: %llu, %.2f GB, %.3f s\n", (unsigned long long)mc, 1e-9 * (double)mb, ms); }
     if (trace && (n_qual[0] + n_qual[1] + n_qual[2])) fprintf(stderr, "[dhts] producer %d QUAL over PCIe: %lld batches as 2-bit codes, %lld as 4-bit codes, %lld as characters (the batch's own alphabet: <= 4 / <= 16 / more distinct characters)\n",
                        p->rank, (long long)n_qual[0], (long long)n_qual[1], (long long)n_qual[2]);
     if (trace) fprintf(stderr, "[dhts] producer %d/%d dev %d: context %.4f s, staged at %.4f s%s, block table %.4f s, header %.4f s, open+index+header %.4f s, %lld batches %lld rows: device %.3f s, waiting for a free host slot %.3f s, read-back %.3f s, waiting for staged bytes %.3f s, %lld table extensions %.3f s, total %.3f s\n",
-                       p->rank, p->world, p->device, t_created, t_staged, from_cache ? " (file still resident in HBM)" : "", t_idx, t_hdr, t_open, (long long)n_batches, (long long)n_rows, t_gpu, t_slot, t_fetch, t_wait, (long long)n_index, t_index, now_s() - t_start);
-    { std::lock_guard<std::mutex> lk(g->mu); p->done = true; }
-    g->cv_ready.notify_all();
+                       p->rank, p->world, p->device, t_created, t_staged, from_cache ? " (file still resident in HBM)" : "", t_idx, t_hdr, t_open, (long long)n_batches, (long long)n_rows, t_gpu, t_slot, t_fetch, t_ext[0], (long long)n_index, t_ext[1], now_s() - t_start);
+    pipe.finish(src);
 }
 
 // What init does with the region of a query, for read_bam and for bam_bin_counts: the index is required, the regions are validated on the
@@ -392,22 +335,31 @@ static bool bam_region_prepare(BamBind *bind, std::vector<uint8_t> &index_bytes,
             error = rc == 1 ? err : dhts_error(bind->ctx); return false;
         }
         // the index (BAI or CSI) narrows the scan window; the device predicate decides the rows
-        FILE *f = fopen(bind->index_file.c_str(), "rb");
-        if (f) {
-            std::vector<uint8_t> ib; uint8_t tmp[65536]; size_t k;
-            while ((k = fread(tmp, 1, sizeof(tmp), f)) > 0) ib.insert(ib.end(), tmp, tmp + k);
-            fclose(f);
-            const bool known = ib.size() >= 4 && (memcmp(ib.data(), "BAI\1", 4) == 0 || memcmp(ib.data(), "CSI\1", 4) == 0 || (ib[0] == 0x1f && ib[1] == 0x8b));
-            if (known) index_bytes.swap(ib);
-        }
+        std::vector<uint8_t> ib;
+        if (read_file(bind->index_file, ib) && ib.size() >= 4 && (memcmp(ib.data(), "BAI\1", 4) == 0 || memcmp(ib.data(), "CSI\1", 4) == 0 || (ib[0] == 0x1f && ib[1] == 0x8b))) index_bytes.swap(ib);
         // only the index windows are staged (the reference seeks to them): byte ranges from the bind context, which holds the header
-        static const bool env_nosparse = getenv("DHTS_SPARSE") && atoi(getenv("DHTS_SPARSE")) == 0;
-        if (!index_bytes.empty() && !env_nosparse) {
+        if (!index_bytes.empty() && env_sparse()) {
             seg_beg.resize(4096); seg_end.resize(4096);
             if (dhts_bam_region_segments(bind->ctx, index_bytes.data(), index_bytes.size(), seg_beg.data(), seg_end.data(), 4096, &seg_count) != 0) seg_count = -1;   // fall back to the whole file
         }
     }
     return true;
+}
+
+// several GPUs on one file, every rank done: every rank's last record must end exactly where the next rank's first record begins
+static void bam_handoff_check(const BamScan *g, std::string &error) {
+    const Shard *prev = nullptr; bool prev_clean = false;
+    if (g->pipe.n_workers > 1) for (auto s : g->pipe.src) if (!s->clean_end && error.empty())
+        error = "read_bam: the stream ended on an error inside one GPU's block range; rerun with DHTS_THREADS=1 for the reference's rows-before-the-error result";
+    for (size_t k = 0; k < g->shard.size(); k++) {
+        const Shard *p = &g->shard[k]; const bool clean = g->pipe.src[k]->clean_end;
+        if (prev && p->has_rows && prev_clean && prev->end_v != p->first_v && error.empty()) {
+            char m[256]; snprintf(m, sizeof(m), "read_bam: GPU shard hand-off mismatch between ranks %d and %d (%llx vs %llx)", prev->rank, p->rank, (unsigned long long)prev->end_v, (unsigned long long)p->first_v);
+            error = m;
+        }
+        if (p->has_rows) { prev = p; prev_clean = clean; }
+        if (!clean) break;                        // the stream ended on an error inside this rank: later ranks' rows are not reachable sequentially
+    }
 }
 
 static void bam_read_global_init(duckdb_init_info info) {
@@ -429,17 +381,14 @@ static void bam_read_global_init(duckdb_init_info info) {
     }
     { std::string rg_error; if (!bam_region_prepare(bind, g->index_bytes, g->seg_beg, g->seg_end, g->seg_count, rg_error)) { init_error(info, rg_error.c_str()); delete g; return; } }
     // sequential mode unless the user asks for parallel fill (bam_reader.c:577-585: the reference goes parallel only with an index)
-    int thr = getenv("DHTS_THREADS") ? atoi(getenv("DHTS_THREADS")) : 1; if (thr < 1) thr = 1; if (thr > 64) thr = 64;
-    g->n_workers = thr;
+    const int thr = env_fill_threads();
     std::vector<int> devs = device_list();
     if (!bind->region.empty()) devs.resize(1);          // an index window is one short scan: a single device serves it
     if (dhts_bam_is_text(bind->ctx) != 0) devs.resize(1);   // SAM / FASTQ / FASTA text is one sequential scan (the C ABI refuses shards of it)
-    for (size_t k = 0; k < devs.size(); k++) {
-        Producer *p = new Producer(); p->device = devs[k]; p->rank = (int)k; p->world = (int)devs.size();
-        for (int q = 0; q < 3; q++) { HostBatch *hb = new HostBatch(); p->free_slots.push_back(hb); p->all.push_back(hb); }
-        g->prod.push_back(p);
-    }
-    for (auto p : g->prod) p->th = std::thread(producer_main, g, p);
+    g->pipe.init(devs.size(), 3, thr, dhts_host_alloc, dhts_host_free, nullptr);       // (a producer destroys its own context: the sources own none)
+    for (size_t k = 0; k < devs.size(); k++) { Shard sh; sh.device = devs[k]; sh.rank = (int)k; sh.world = (int)devs.size(); g->shard.push_back(sh); }
+    if (devs.size() > 1) g->pipe.on_all_done = [g](std::string &error) { bam_handoff_check(g, error); };
+    for (size_t k = 0; k < devs.size(); k++) g->pipe.start(k, [g, k] { producer_main(g, k); });
     API(void, duckdb_init_set_max_threads, duckdb_init_info, idx_t)(info, (idx_t)thr);
     API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, g, destroy_global);
 }
@@ -448,69 +397,104 @@ static void bam_read_local_init(duckdb_init_info info) {
     API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, new BamLocal(), destroy_local);
 }
 
-// hands the calling worker its next run of rows: the rest of the current batch (sequential mode) or a 2048-row slice of a ready batch.
-// Returns false at the end of the scan (or on a producer error: g->error).
-static bool next_rows(BamScan *g, BamLocal *l, idx_t want) {
-    std::unique_lock<std::mutex> lk(g->mu);
-    // give back what the worker holds
-    if (l->cur) {
-        HostBatch *hb = l->cur; Producer *own = l->cur_owner;
-        hb->readers--;
-        const bool finished = g->n_workers == 1 ? true : (hb->retired && hb->readers == 0);
-        if (finished) { own->free_slots.push_back(hb); g->cv_free.notify_all(); }
-        l->cur = nullptr;
-    }
-    for (;;) {
-        if (!g->error.empty()) return false;
-        // ordered mode drains the producers one after the other (file order); parallel mode takes whatever is ready
-        for (size_t k = 0; k < g->prod.size(); k++) {
-            Producer *p = g->prod[g->n_workers == 1 ? g->cur_prod : (g->cur_prod + k) % g->prod.size()];
-            while (!p->ready.empty()) {
-                HostBatch *hb = p->ready.front();
-                if (g->n_workers == 1) {
-                    p->ready.pop_front(); hb->readers = 1;
-                    l->cur = hb; l->cur_owner = p; l->pos = 0; l->end = hb->n;
-                    return true;
+// rows [s, s + take) of a host batch -> rows [row_count, row_count + take) of the output chunk
+static void bam_fill(const BamBind *bind, const BamScan *g, BamLocal *l, const HostBatch *hb, int64_t s, idx_t take, duckdb_data_chunk output, idx_t row_count) {
+    auto get_vec = API(duckdb_vector, duckdb_data_chunk_get_vector, duckdb_data_chunk, idx_t);
+    auto get_data = API(void *, duckdb_vector_get_data, duckdb_vector);
+    auto assign_len = API(void, duckdb_vector_assign_string_element_len, duckdb_vector, idx_t, const char *, idx_t);
+    const dhts_bam_batch &b = hb->b;
+    for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
+        duckdb_vector vec = get_vec(output, ci);
+        // strings of <= 12 bytes are written in place (no call, no heap); longer ones are copied into the vector's heap by the engine
+        auto put_str = [&](const dhts_strcol &h) {
+            duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
+            for (idx_t r = 0; r < take; r++) { const char *p = (const char *)h.bytes + h.off[s + r]; const uint32_t n = h.len[s + r]; if (!inl_string(d + r, p, n)) assign_len(vec, row_count + r, p, n); } };
+        auto put_name = [&](const int32_t *ids) {
+            duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
+            for (idx_t r = 0; r < take; r++) {
+                const int32_t t = ids[s + r];
+                if (t < 0) d[r] = bind->star_inl; else if (bind->ref_is_inl[t]) d[r] = bind->ref_inl[t];
+                else { const char *nm = bind->hdr.ref_name[t]; assign_len(vec, row_count + r, nm, strlen(nm)); }
+            } };
+        switch (g->column_ids[ci]) {
+        case DHTS_BAM_QNAME: put_str(b.qname); break;
+        case DHTS_BAM_FLAG: memcpy((uint16_t *)get_data(vec) + row_count, b.flag + s, take * 2); break;
+        case DHTS_BAM_RNAME: put_name(b.tid); break;
+        case DHTS_BAM_POS: memcpy((int64_t *)get_data(vec) + row_count, b.pos + s, take * 8); break;
+        case DHTS_BAM_MAPQ: memcpy((int32_t *)get_data(vec) + row_count, b.mapq + s, take * 4); break;
+        case DHTS_BAM_CIGAR: put_str(b.cigar); break;
+        case DHTS_BAM_RNEXT: put_name(b.mtid); break;
+        case DHTS_BAM_PNEXT: memcpy((int64_t *)get_data(vec) + row_count, b.pnext + s, take * 8); break;
+        case DHTS_BAM_TLEN: memcpy((int64_t *)get_data(vec) + row_count, b.tlen + s, take * 8); break;
+        case DHTS_BAM_SEQ:
+            if (!b.seq_packed) { put_str(b.seq); break; }
+            {   // the batch carries the file's 4-bit codes: expand here (seq_to_string, bam_reader.c:560-575; "*" for an empty SEQ)
+                duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
+                for (idx_t r = 0; r < take; r++) {
+                    const uint32_t n = b.seq.len[s + r];
+                    if (n == 0) { inl_string(d + r, "*", 1); continue; }
+                    if (l->seq_tmp.size() < (size_t)n + 32) l->seq_tmp.resize((size_t)n + 32 + n / 2);
+                    expand_seq(b.seq.bytes + b.seq.off[s + r], n, l->seq_tmp.data());
+                    if (!inl_string(d + r, l->seq_tmp.data(), n)) assign_len(vec, row_count + r, l->seq_tmp.data(), n);
                 }
-                if (hb->next >= hb->n) {            // every row is claimed: the last reader returns the slot
-                    p->ready.pop_front(); hb->retired = true;
-                    if (hb->readers == 0) { p->free_slots.push_back(hb); g->cv_free.notify_all(); }
-                    continue;
-                }
-                l->cur = hb; l->cur_owner = p; l->pos = hb->next; l->end = hb->next + (int64_t)want < hb->n ? hb->next + (int64_t)want : hb->n;
-                hb->next = l->end; hb->readers++;
-                return true;
             }
-            if (g->n_workers == 1) {
-                if (p->done && p->ready.empty()) {
-                    if (!p->clean_end) return false;      // the stream ended on an error inside this rank: the scan ends here, silently (bam_reader.c:754-766)
-                    if (g->cur_prod + 1 < g->prod.size()) { g->cur_prod++; k = (size_t)-1; continue; }
+            break;
+        case DHTS_BAM_QUAL:
+            if (!b.qual_bits) { put_str(b.qual); break; }
+            {   // the batch carries codes of its own alphabet: expand here (qual_to_string's characters, bam_reader.c:577-600, were made on the device)
+                duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
+                const uint8_t *stream = b.qual.bytes + 16; const uint32_t *lut = hb->qual_lut.data();
+                for (idx_t r = 0; r < take; r++) {
+                    const uint32_t n = b.qual.len[s + r];
+                    if (l->seq_tmp.size() < (size_t)n + 40) l->seq_tmp.resize((size_t)n + 40 + n / 2);
+                    expand_qual(stream, b.qual_bits, lut, b.qual.off[s + r], n, l->seq_tmp.data(), l->qual_tmp);
+                    if (!inl_string(d + r, l->seq_tmp.data(), n)) assign_len(vec, row_count + r, l->seq_tmp.data(), n);
                 }
+            }
+            break;
+        case DHTS_BAM_READ_GROUP_ID: {
+            duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
+            for (idx_t r = 0; r < take; r++) {
+                int64_t q = s + (int64_t)r;
+                if ((b.rg_valid[q >> 6] >> (q & 63)) & 1) { const char *p = (const char *)b.rg.bytes + b.rg.off[q]; const uint32_t n = b.rg.len[q]; if (!inl_string(d + r, p, n)) assign_len(vec, row_count + r, p, n); }
+                else set_null(vec, row_count + r);
+            }
+            break;
+        }
+        case DHTS_BAM_SAMPLE_ID:
+            for (idx_t r = 0; r < take; r++) {
+                int64_t q = s + (int64_t)r; int32_t k = b.rg_idx[q];
+                const char *sm = (((b.rg_valid[q >> 6] >> (q & 63)) & 1) && k >= 0) ? bind->hdr.rg_sm[k] : nullptr;
+                if (sm) assign_len(vec, row_count + r, sm, strlen(sm)); else set_null(vec, row_count + r);
+            }
+            break;
+        default: {
+            if (g->want_aux && g->column_ids[ci] == bind->aux_col_idx) {               // bam_reader.c:967-1027
+                // no tags: NULL, entry {size, 0}; the pairs go in as the attributes map of the text readers does
+                const dhts_tabix_map m = {hb->aux_off.data(), hb->aux_valid.data(), hb->aux_koff.size() - 1, hb->aux_koff.data(), (const uint8_t *)hb->aux_keys.data(), hb->aux_keys.size(),
+                                          hb->aux_voff.data(), (const uint8_t *)hb->aux_vals.data(), hb->aux_vals.size()};
+                fill_col(vec, COL_MAP, dhts_col(), &m, s, take, row_count);
                 break;
             }
-        }
-        bool all_done = true;
-        for (auto p : g->prod) if (!p->done || !p->ready.empty()) all_done = false;
-        if (all_done) {
-            // several GPUs on one file: every rank's last record must end exactly where the next rank's first record begins
-            if (g->prod.size() > 1 && !g->handoff_checked) {
-                g->handoff_checked = true;
-                const Producer *prev = nullptr;
-                if (g->n_workers > 1) for (auto p : g->prod) if (!p->clean_end && g->error.empty())
-                    g->error = "read_bam: the stream ended on an error inside one GPU's block range; rerun with DHTS_THREADS=1 for the reference's rows-before-the-error result";
-                for (auto p : g->prod) {
-                    if (prev && p->has_rows && prev->clean_end && prev->end_v != p->first_v && g->error.empty()) {
-                        char m[256]; snprintf(m, sizeof(m), "read_bam: GPU shard hand-off mismatch between ranks %d and %d (%llx vs %llx)", prev->rank, p->rank, (unsigned long long)prev->end_v, (unsigned long long)p->first_v);
-                        g->error = m;
-                    }
-                    if (p->has_rows) prev = p;
-                    if (!p->clean_end) break;                 // the stream ended on an error inside this rank: later ranks' rows are not reachable sequentially
+            const int sl = g->tag_slot[ci];
+            if (sl < 0) break;                                 // unknown ids (e.g. a row-id pseudo column) write nothing, like the reference's default arm
+            const HostTag &h = hb->tags[sl];
+            char nm[3], ty, sub; dhts_bam_std_tag_info(g->tag_ids[sl], nm, &ty, &sub);
+            if (ty == 'i') {                                    // bam_reader.c:946-950
+                memcpy((int64_t *)get_data(vec) + row_count, h.fixed.data() + s, take * 8);
+                for (idx_t r = 0; r < take; r++) if (!h.valid[s + r]) set_null(vec, row_count + r);
+            } else if (ty == 'B') {                             // bam_assign_list_int / _double bam_reader.c:106-138
+                const ListFrame f = list_entries(vec, h.off.data(), h.valid.data(), s, take, row_count, true);     // absent tag: set_null only, the entry is left untouched (bam_reader.c:927-930)
+                if (f.c1 > f.c0) memcpy((int64_t *)get_data(f.child) + f.base, h.child.data() + f.c0, (size_t)(f.c1 - f.c0) * 8);
+            } else {
+                for (idx_t r = 0; r < take; r++) {
+                    if (h.valid[s + r]) assign_len(vec, row_count + r, (const char *)h.bytes.data() + h.off[s + r], h.off[s + r + 1] - h.off[s + r]);
+                    else set_null(vec, row_count + r);
                 }
-                if (!g->error.empty()) return false;
             }
-            return false;
+            break;
         }
-        g->cv_ready.wait(lk);
+        }
     }
 }
 
@@ -519,141 +503,11 @@ static void bam_read_function(duckdb_function_info info, duckdb_data_chunk outpu
     BamScan *g = (BamScan *)API(void *, duckdb_function_get_init_data, duckdb_function_info)(info);
     BamLocal *l = (BamLocal *)API(void *, duckdb_function_get_local_init_data, duckdb_function_info)(info);
     auto set_size = API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t);
-    if (!l || !g || l->done) { set_size(output, 0); return; }                                // bam_reader.c:730-733
-    const idx_t vector_size = API(idx_t, duckdb_vector_size, void)();
-    auto get_vec = API(duckdb_vector, duckdb_data_chunk_get_vector, duckdb_data_chunk, idx_t);
-    auto get_data = API(void *, duckdb_vector_get_data, duckdb_vector);
-    auto assign_len = API(void, duckdb_vector_assign_string_element_len, duckdb_vector, idx_t, const char *, idx_t);
-    idx_t row_count = 0;
-    while (row_count < vector_size) {
-        if (!l->cur || l->pos >= l->end) {
-            if (g->n_workers > 1 && row_count > 0) break;           // parallel mode: one slice per chunk
-            if (!next_rows(g, l, vector_size)) {
-                l->done = true;
-                if (!g->error.empty()) { API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, g->error.c_str()); set_size(output, 0); return; }
-                break;
-            }
-        }
-        const HostBatch *hb = l->cur; const dhts_bam_batch &b = hb->b;
-        idx_t take = (idx_t)(l->end - l->pos); if (take > vector_size - row_count) take = vector_size - row_count;
-        const int64_t s = l->pos;
-        for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
-            duckdb_vector vec = get_vec(output, ci);
-            // strings of <= 12 bytes are written in place (no call, no heap); longer ones are copied into the vector's heap by the engine
-            auto put_str = [&](const dhts_strcol &h) {
-                duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
-                for (idx_t r = 0; r < take; r++) { const char *p = (const char *)h.bytes + h.off[s + r]; const uint32_t n = h.len[s + r]; if (!inl_string(d + r, p, n)) assign_len(vec, row_count + r, p, n); } };
-            auto put_name = [&](const int32_t *ids) {
-                duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
-                for (idx_t r = 0; r < take; r++) {
-                    const int32_t t = ids[s + r];
-                    if (t < 0) d[r] = bind->star_inl; else if (bind->ref_is_inl[t]) d[r] = bind->ref_inl[t];
-                    else { const char *nm = bind->hdr.ref_name[t]; assign_len(vec, row_count + r, nm, strlen(nm)); }
-                } };
-            switch (g->column_ids[ci]) {
-            case DHTS_BAM_QNAME: put_str(b.qname); break;
-            case DHTS_BAM_FLAG: memcpy((uint16_t *)get_data(vec) + row_count, b.flag + s, take * 2); break;
-            case DHTS_BAM_RNAME: put_name(b.tid); break;
-            case DHTS_BAM_POS: memcpy((int64_t *)get_data(vec) + row_count, b.pos + s, take * 8); break;
-            case DHTS_BAM_MAPQ: memcpy((int32_t *)get_data(vec) + row_count, b.mapq + s, take * 4); break;
-            case DHTS_BAM_CIGAR: put_str(b.cigar); break;
-            case DHTS_BAM_RNEXT: put_name(b.mtid); break;
-            case DHTS_BAM_PNEXT: memcpy((int64_t *)get_data(vec) + row_count, b.pnext + s, take * 8); break;
-            case DHTS_BAM_TLEN: memcpy((int64_t *)get_data(vec) + row_count, b.tlen + s, take * 8); break;
-            case DHTS_BAM_SEQ:
-                if (!b.seq_packed) { put_str(b.seq); break; }
-                {   // the batch carries the file's 4-bit codes: expand here (seq_to_string, bam_reader.c:560-575; "*" for an empty SEQ)
-                    duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
-                    for (idx_t r = 0; r < take; r++) {
-                        const uint32_t n = b.seq.len[s + r];
-                        if (n == 0) { inl_string(d + r, "*", 1); continue; }
-                        if (l->seq_tmp.size() < (size_t)n + 32) l->seq_tmp.resize((size_t)n + 32 + n / 2);
-                        expand_seq(b.seq.bytes + b.seq.off[s + r], n, l->seq_tmp.data());
-                        if (!inl_string(d + r, l->seq_tmp.data(), n)) assign_len(vec, row_count + r, l->seq_tmp.data(), n);
-                    }
-                }
-                break;
-            case DHTS_BAM_QUAL:
-                if (!b.qual_bits) { put_str(b.qual); break; }
-                {   // the batch carries codes of its own alphabet: expand here (qual_to_string's characters, bam_reader.c:577-600, were made on the device)
-                    duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
-                    const uint8_t *stream = b.qual.bytes + 16; const uint32_t *lut = hb->qual_lut.data();
-                    for (idx_t r = 0; r < take; r++) {
-                        const uint32_t n = b.qual.len[s + r];
-                        if (l->seq_tmp.size() < (size_t)n + 40) l->seq_tmp.resize((size_t)n + 40 + n / 2);
-                        expand_qual(stream, b.qual_bits, lut, b.qual.off[s + r], n, l->seq_tmp.data(), l->qual_tmp);
-                        if (!inl_string(d + r, l->seq_tmp.data(), n)) assign_len(vec, row_count + r, l->seq_tmp.data(), n);
-                    }
-                }
-                break;
-            case DHTS_BAM_READ_GROUP_ID: {
-                duckdb_string_t *d = (duckdb_string_t *)get_data(vec) + row_count;
-                for (idx_t r = 0; r < take; r++) {
-                    int64_t q = s + (int64_t)r;
-                    if ((b.rg_valid[q >> 6] >> (q & 63)) & 1) { const char *p = (const char *)b.rg.bytes + b.rg.off[q]; const uint32_t n = b.rg.len[q]; if (!inl_string(d + r, p, n)) assign_len(vec, row_count + r, p, n); }
-                    else set_null(vec, row_count + r);
-                }
-                break;
-            }
-            case DHTS_BAM_SAMPLE_ID:
-                for (idx_t r = 0; r < take; r++) {
-                    int64_t q = s + (int64_t)r; int32_t k = b.rg_idx[q];
-                    const char *sm = (((b.rg_valid[q >> 6] >> (q & 63)) & 1) && k >= 0) ? bind->hdr.rg_sm[k] : nullptr;
-                    if (sm) assign_len(vec, row_count + r, sm, strlen(sm)); else set_null(vec, row_count + r);
-                }
-                break;
-            default: {
-                if (g->want_aux && g->column_ids[ci] == bind->aux_col_idx) {               // bam_reader.c:967-1027
-                    auto list_size = API(idx_t, duckdb_list_vector_get_size, duckdb_vector);
-                    duckdb_list_entry *le = (duckdb_list_entry *)get_data(vec);
-                    idx_t base = list_size(vec);
-                    const uint32_t c0 = hb->aux_off[s], c1 = hb->aux_off[s + take];
-                    if (c1 > c0) { API(duckdb_state, duckdb_list_vector_reserve, duckdb_vector, idx_t)(vec, base + (c1 - c0)); API(duckdb_state, duckdb_list_vector_set_size, duckdb_vector, idx_t)(vec, base + (c1 - c0)); }
-                    duckdb_vector child = API(duckdb_vector, duckdb_list_vector_get_child, duckdb_vector)(vec);
-                    duckdb_vector kvec = API(duckdb_vector, duckdb_struct_vector_get_child, duckdb_vector, idx_t)(child, 0);
-                    duckdb_vector vvec = API(duckdb_vector, duckdb_struct_vector_get_child, duckdb_vector, idx_t)(child, 1);
-                    for (idx_t r = 0; r < take; r++) {
-                        le[row_count + r].offset = base + (hb->aux_off[s + r] - c0); le[row_count + r].length = hb->aux_off[s + r + 1] - hb->aux_off[s + r];
-                        if (!hb->aux_valid[s + r]) set_null(vec, row_count + r);            // no tags: NULL, entry {size, 0}
-                    }
-                    for (uint32_t k = c0; k < c1; k++) {
-                        assign_len(kvec, base + (k - c0), hb->aux_key[k].data(), hb->aux_key[k].size());
-                        assign_len(vvec, base + (k - c0), hb->aux_val[k].data(), hb->aux_val[k].size());
-                    }
-                    break;
-                }
-                const int sl = g->tag_slot[ci];
-                if (sl < 0) break;                                 // unknown ids (e.g. a row-id pseudo column) write nothing, like the reference's default arm
-                const HostTag &h = hb->tags[sl];
-                char nm[3], ty, sub; dhts_bam_std_tag_info(g->tag_ids[sl], nm, &ty, &sub);
-                if (ty == 'i') {                                    // bam_reader.c:946-950
-                    memcpy((int64_t *)get_data(vec) + row_count, h.fixed.data() + s, take * 8);
-                    for (idx_t r = 0; r < take; r++) if (!h.valid[s + r]) set_null(vec, row_count + r);
-                } else if (ty == 'B') {                             // bam_assign_list_int / _double bam_reader.c:106-138
-                    auto list_size = API(idx_t, duckdb_list_vector_get_size, duckdb_vector);
-                    duckdb_list_entry *le = (duckdb_list_entry *)get_data(vec);
-                    idx_t base = list_size(vec);
-                    const uint32_t c0 = h.off[s], c1 = h.off[s + take];
-                    if (c1 > c0) { API(duckdb_state, duckdb_list_vector_reserve, duckdb_vector, idx_t)(vec, base + (c1 - c0)); API(duckdb_state, duckdb_list_vector_set_size, duckdb_vector, idx_t)(vec, base + (c1 - c0)); }
-                    duckdb_vector child = API(duckdb_vector, duckdb_list_vector_get_child, duckdb_vector)(vec);
-                    for (idx_t r = 0; r < take; r++) {
-                        if (h.valid[s + r]) { le[row_count + r].offset = base + (h.off[s + r] - c0); le[row_count + r].length = h.off[s + r + 1] - h.off[s + r]; }
-                        else set_null(vec, row_count + r);          // absent tag: set_null only, the entry is left untouched (bam_reader.c:927-930)
-                    }
-                    if (c1 > c0) memcpy((int64_t *)get_data(child) + base, h.child.data() + c0, (size_t)(c1 - c0) * 8);
-                } else {
-                    for (idx_t r = 0; r < take; r++) {
-                        if (h.valid[s + r]) assign_len(vec, row_count + r, (const char *)h.bytes.data() + h.off[s + r], h.off[s + r + 1] - h.off[s + r]);
-                        else set_null(vec, row_count + r);
-                    }
-                }
-                break;
-            }
-            }
-        }
-        row_count += take; l->pos += (int64_t)take;
-    }
-    set_size(output, row_count);
+    if (!l || !g) { set_size(output, 0); return; }                                            // bam_reader.c:730-733
+    std::string err;
+    const int64_t n = g->pipe.fill_chunk(l->at, API(idx_t, duckdb_vector_size, void)(), err, [&](const HostBatch &hb, int64_t s, idx_t take, idx_t row_count) { bam_fill(bind, g, l, &hb, s, take, output, row_count); });
+    if (n < 0) API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, err.c_str());
+    set_size(output, n < 0 ? 0 : (idx_t)n);
 }
 
 extern "C" __attribute__((visibility("default"))) void register_read_bam_function(duckdb_connection connection) {                      // bam_reader.c:1044-1068

@@ -17,36 +17,22 @@ struct BcfBind {
 // copies, dhts_bcf_batch_fetch); the scan callbacks fill DataChunks from those arenas while the device works on the next batch.
 // DHTS_THREADS = 1 (default): one worker, rows in file order, full 2048-row chunks (the reference's only mode for read_bcf without
 // an index); DHTS_THREADS = k: k workers claim 2048-row slices, row order across workers unspecified.
-struct BcfHostBatch {
-    void *arena = nullptr; uint64_t cap = 0;
+struct BcfHostBatch : PipeSlot {
     std::vector<dhts_bcf_col> cols;                 // HOST pointers, projection order (deduplicated)
     std::vector<std::vector<uint32_t>> conv;        // per column: DHTS_ENC_FLOAT_TEXT children converted to float bits
-    int64_t n = 0; int status = 0; int ncols_fetched = 0;
-    int64_t next = 0; int readers = 0; bool retired = false;
+    int ncols_fetched = 0;
 };
+typedef Pipeline<BcfHostBatch> BcfPipe;
 struct BcfScan {
     BcfBind *bind = nullptr;
     std::vector<idx_t> column_ids;       // schema ids per output vector
     std::vector<int> slot;               // output vector -> index into the batch's columns (or -1 for unknown ids)
     std::vector<int32_t> proj;           // projected (deduplicated) schema columns
-    int n_workers = 1;
-    std::mutex mu; std::condition_variable cv_ready, cv_free;
-    std::deque<BcfHostBatch *> ready; std::vector<BcfHostBatch *> free_slots, all;
-    std::thread th; bool done = false, cancel = false; std::string error;
-    dhts_ctx *ctx = nullptr;             // the scan's own context (the producer stages the file into it); lives until the chunks are filled:
-    dhts_bcf_info inf;                   // its name tables -- a text scan adds the names records use without a header definition
-    ~BcfScan() {
-        { std::lock_guard<std::mutex> lk(mu); cancel = true; }
-        cv_free.notify_all(); cv_ready.notify_all();
-        if (th.joinable()) th.join();
-        if (ctx) dhts_destroy(ctx);                 // first: it waits for the copy stream, whose D2H may still be writing into an arena (error paths leave one in flight)
-        for (auto hb : all) { dhts_host_free(hb->arena); delete hb; }
-    }
+    dhts_bcf_info inf;                   // the name tables of the scan's own context -- a text scan adds the names records use without a header definition.
+    BcfPipe pipe;                        // That context (the source's ctx: the producer stages the file into it) lives until the chunks are filled: teardown destroys it
+    ~BcfScan() { pipe.teardown(); }      // (joins the producer, which reads the fields above)
 };
-struct BcfLocal {
-    bool done = false;
-    BcfHostBatch *cur = nullptr; int64_t pos = 0, end = 0;      // rows [pos, end) of `cur` are this worker's
-};
+struct BcfLocal { BcfPipe::Cursor at; };
 static void destroy_bcf_bind(void *p) { BcfBind *b = (BcfBind *)p; if (!b) return; if (b->ctx) dhts_destroy(b->ctx); delete b; }
 static void destroy_bcf_local(void *p) { delete (BcfLocal *)p; }
 static void destroy_bcf_global(void *p) { delete (BcfScan *)p; }
@@ -98,15 +84,11 @@ static void bcf_read_bind(duckdb_bind_info info) {
     const double tb2 = now_s();
     for (const std::string &f : {idx, b->path + ".csi", b->path + ".tbi"}) if (!f.empty() && file_exists(f)) { b->index_file = f; break; }
     b->has_index = !b->index_file.empty();
-    if (b->has_index && !b->regions.empty()) {
-        FILE *f = fopen(b->index_file.c_str(), "rb");
-        if (f) { uint8_t tmp[65536]; size_t k; while ((k = fread(tmp, 1, sizeof(tmp), f)) > 0) b->index_bytes.insert(b->index_bytes.end(), tmp, tmp + k); fclose(f); }
-    }
+    if (b->has_index && !b->regions.empty()) (void)read_file(b->index_file, b->index_bytes);
     {
         // only the header blocks and the index windows of the regions are staged (the reference seeks to the chunks): byte ranges from this
         // context, which holds the header.  DHTS_SPARSE=0 stages the whole file.
-        static const bool env_nosparse = getenv("DHTS_SPARSE") && atoi(getenv("DHTS_SPARSE")) == 0;
-        if (!b->index_bytes.empty() && !b->regions.empty() && !env_nosparse) {
+        if (!b->index_bytes.empty() && !b->regions.empty() && env_sparse()) {
             b->header_bytes = dhts_bcf_header_bytes(b->ctx);
             b->seg_beg.resize(4096); b->seg_end.resize(4096);
             if (b->header_bytes == 0 || dhts_bcf_region_segments(b->ctx, b->region.c_str(), b->index_bytes.data(), b->index_bytes.size(), b->seg_beg.data(), b->seg_end.data(), 4096, &b->seg_count) != 0) b->seg_count = -1;
@@ -141,39 +123,44 @@ static bool bcf_next_region(BcfBind *bind, dhts_ctx *c, size_t *next_region) {
     return false;
 }
 
+// the bytes of a batch have landed: Float fields of a transcript arrive as text -- (float)strtod, NaN unless the whole token converts
+// (vep_parse_float, src/vep_parser.c:222-235)
+static void bcf_convert_text_floats(const BcfBind *bind, BcfHostBatch *hb) {
+    hb->conv.assign((size_t)hb->ncols_fetched, std::vector<uint32_t>());
+    for (int i = 0; i < hb->ncols_fetched; i++) {
+        const dhts_bcf_col &h = hb->cols[i];
+        if (bind->inf.cols[h.col].encoding != DHTS_ENC_FLOAT_TEXT) continue;
+        std::vector<uint32_t> &cv = hb->conv[i]; cv.assign(h.child_n + 1, 0);
+        std::string tok;
+        for (uint64_t k = 0; k < h.child_n; k++) {
+            if (h.child_valid && !h.child_valid[k]) continue;
+            tok.assign((const char *)h.bytes + h.child_off[k], h.child_off[k + 1] - h.child_off[k]);
+            char *end = nullptr; const double v = strtod(tok.c_str(), &end);
+            const float f = (end == tok.c_str() || *end) ? NAN : (float)v;
+            memcpy(&cv[k], &f, 4);
+        }
+    }
+}
+
 static void bcf_producer_main(BcfScan *g) {
-    BcfBind *bind = g->bind;
-    auto finish = [&](const std::string &err) {
-        std::lock_guard<std::mutex> lk(g->mu);
-        if (!err.empty() && g->error.empty()) g->error = err;
-        g->done = true; g->cv_ready.notify_all();
-    };
+    BcfBind *bind = g->bind; BcfPipe &pipe = g->pipe; BcfPipe::Source &src = *pipe.src[0];
+    auto finish = [&](const std::string &err) { pipe.finish(src, err); };
     static const bool trace = getenv("DHTS_TRACE") != nullptr;       // stage timings on stderr
     const double t_start = now_s();
     (void)dhts_bind_thread_near_device(bind->device);          // (as read_bam's producers: thread, staging readers and pinned arenas on the GPU's NUMA node)
-    dhts_ctx *c = g->ctx = dhts_create(bind->device);
+    dhts_ctx *c = dhts_create(bind->device);
+    src.ctx = c;
     if (!c) { finish(no_device_message("read_bcf")); return; }
     dhts_set_super_blocks(c, 196608);
     const double t_ctx = now_s() - t_start;
     // a plain whole-file scan starts decoding while the file is still being staged (as read_bam does): the block table is built over the
     // resident prefix and extended as more bytes arrive.  DHTS_STREAM=0, region queries and uncompressed text stage first.
-    static const bool env_nostream = getenv("DHTS_STREAM") && atoi(getenv("DHTS_STREAM")) == 0;
-    const bool streaming = bind->regions.empty() && !env_nostream && bind->seg_count < 0 && dhts_bcf_is_text(bind->ctx) != 2;
+    const bool streaming = bind->regions.empty() && env_stream() && bind->seg_count < 0 && dhts_bcf_is_text(bind->ctx) != 2;
     int staged_all = 1;
     int orc = bind->seg_count >= 0 ? dhts_open_path_segments(c, bind->path.c_str(), bind->header_bytes, bind->seg_beg.data(), bind->seg_end.data(), bind->seg_count)
               : streaming ? dhts_open_path_async(c, bind->path.c_str()) : dhts_open_path(c, bind->path.c_str());
     if (orc == 0 && !streaming && (dhts_bgzf_index(c) <= 0 || dhts_bcf_open(c, bind->tidy) != 0)) orc = -1;
-    if (orc == 0 && streaming) {
-        // the header needs the first blocks only: 32 MiB to start with, four times more whenever that is not enough
-        uint64_t want = 32u << 20;
-        for (;;) {
-            const int64_t f = dhts_stage_wait(c, want, &staged_all);
-            if (f < 0) { orc = -1; break; }
-            if (dhts_bgzf_index_staged(c) > 0 && dhts_bcf_open(c, bind->tidy) == 0) break;
-            if (staged_all) { orc = -1; break; }
-            want *= 4;
-        }
-    }
+    if (orc == 0 && streaming) orc = stream_open(c, 32u << 20, &staged_all, [&](dhts_ctx *x) { return dhts_bcf_open(x, bind->tidy); });
     if (orc != 0 || dhts_bcf_info_get(c, &g->inf) != 0) {
         finish(std::string("Failed to open BCF/VCF file: ") + bind->path); return;
     }
@@ -184,67 +171,32 @@ static void bcf_producer_main(BcfScan *g) {
     const double t_region = now_s() - t_start;
     if (trace) fprintf(stderr, "[dhts] read_bcf producer dev %d: context %.4f s, staged + block table + header at %.4f s (%s, %llu bytes resident), first region set at %.4f s\n", bind->device, t_ctx, t_open,
                        bind->seg_count >= 0 ? "header + index windows" : streaming ? "streaming" : "whole file", (unsigned long long)dhts_resident_bytes(c), t_region);
-    static const int64_t env_mb = getenv("DHTS_BATCH_BLOCKS") ? atoll(getenv("DHTS_BATCH_BLOCKS")) : 0;
-    const int64_t max_blocks = env_mb > 0 ? env_mb : 4096;
-    BcfHostBatch *pending = nullptr; int pending_slot = 0, slot_no = 0;
-    auto publish = [&](BcfHostBatch *hb, int sl) -> bool {          // sl < 0: the bytes are already there
-        if (sl >= 0 && dhts_bcf_batch_fetch_wait(c, sl) != 0) return false;
-        hb->conv.assign((size_t)hb->ncols_fetched, std::vector<uint32_t>());
-        for (int i = 0; i < hb->ncols_fetched; i++) {
-            const dhts_bcf_col &h = hb->cols[i];
-            if (bind->inf.cols[h.col].encoding != DHTS_ENC_FLOAT_TEXT) continue;
-            // Float fields of a transcript arrive as text: (float)strtod, NaN unless the whole token converts (vep_parse_float, src/vep_parser.c:222-235)
-            std::vector<uint32_t> &cv = hb->conv[i]; cv.assign(h.child_n + 1, 0);
-            std::string tok;
-            for (uint64_t k = 0; k < h.child_n; k++) {
-                if (h.child_valid && !h.child_valid[k]) continue;
-                tok.assign((const char *)h.bytes + h.child_off[k], h.child_off[k + 1] - h.child_off[k]);
-                char *end = nullptr; const double v = strtod(tok.c_str(), &end);
-                const float f = (end == tok.c_str() || *end) ? NAN : (float)v;
-                memcpy(&cv[k], &f, 4);
-            }
-        }
-        { std::lock_guard<std::mutex> lk(g->mu); g->ready.push_back(hb); }
-        g->cv_ready.notify_all();
-        return true;
-    };
+    const int64_t max_blocks = env_batch_blocks(4096);
+    dhts_bcf_batch b;
+    // the previous batch has this batch's scan to cross PCIe; then it is finished (text floats) and handed to the fill threads
+    auto rb = make_readback(pipe, src, !env_overlap_readback(),
+                            [&](BcfHostBatch *hb) { return dhts_bcf_batch_fetch(c, &b, hb->arena, hb->cap, hb->cols.data()) == 0; },
+                            [&](BcfHostBatch *hb, int sl) { return dhts_bcf_batch_fetch_begin(c, &b, hb->arena, hb->cap, hb->cols.data(), sl) == 0; },
+                            [&](int sl) { return dhts_bcf_batch_fetch_wait(c, sl) == 0; }, [&](BcfHostBatch *hb) { bcf_convert_text_floats(bind, hb); });
     for (;;) {
-        dhts_bcf_batch b;
-        if (streaming && !staged_all && dhts_blocks_ahead(c) < max_blocks) {
-            // not enough known blocks for a full batch: wait for (at least) another 128 MiB of the file, then extend the block table
-            int64_t f = dhts_stage_wait(c, 0, &staged_all);
-            if (f >= 0 && !staged_all) f = dhts_stage_wait(c, (uint64_t)f + (128u << 20), &staged_all);
-            if (f < 0 || dhts_bgzf_index_staged(c) < 0) { finish(dhts_error(c)); return; }
-        }
+        if (streaming && stream_extend(c, max_blocks, &staged_all) < 0) { finish(dhts_error(c)); return; }
         if (dhts_bcf_next_batch(c, max_blocks, &b) != 0) { finish(dhts_error(c)); return; }
         if (b.n_rows > 0) {
-            BcfHostBatch *hb = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(g->mu);
-                g->cv_free.wait(lk, [&] { return g->cancel || !g->free_slots.empty(); });
-                if (g->cancel) break;
-                hb = g->free_slots.back(); g->free_slots.pop_back();
-            }
-            const uint64_t need = dhts_bcf_batch_host_bytes(c);
-            if (need > hb->cap) { dhts_host_free(hb->arena); hb->arena = dhts_host_alloc(need); hb->cap = hb->arena ? need : 0; }
+            BcfHostBatch *hb = pipe.take_slot(src);
+            if (!hb) break;
+            if (!pipe.reserve(hb, dhts_bcf_batch_host_bytes(c))) { finish("read_bcf: out of pinned host memory"); return; }
             hb->cols.assign((size_t)b.n_cols, dhts_bcf_col());
-            static const bool env_serial = getenv("DHTS_OVERLAP_READBACK") && atoi(getenv("DHTS_OVERLAP_READBACK")) == 0;
-            const int frc = env_serial ? dhts_bcf_batch_fetch(c, &b, hb->arena, hb->cap, hb->cols.data()) : dhts_bcf_batch_fetch_begin(c, &b, hb->arena, hb->cap, hb->cols.data(), slot_no);
-            if ((need && !hb->arena) || frc != 0) { finish(hb->arena || !need ? dhts_error(c) : "read_bcf: out of pinned host memory"); return; }
+            if (!rb.begin(hb)) { finish(dhts_error(c)); return; }
             hb->n = b.n_rows; hb->status = b.status; hb->next = 0; hb->readers = 0; hb->retired = false; hb->ncols_fetched = b.n_cols;
-            // the previous batch has had this batch's scan to cross PCIe: finish it (text floats) and hand it to the fill threads
-            if (pending && !publish(pending, pending_slot)) { finish(dhts_error(c)); return; }
-            pending = nullptr;
-            if (env_serial) { if (!publish(hb, -1)) { finish(dhts_error(c)); return; } }
-            else { pending = hb; pending_slot = slot_no; slot_no ^= 1; }
+            if (!rb.turn(hb)) { finish(dhts_error(c)); return; }
         }
         if (b.status != 0) {                                     // EOF, or the silent stop at the first bad record (bcf_reader.c:1319-1349)
             if (!bind->regions.empty() && bcf_next_region(bind, c, &next_region)) continue;
             break;
         }
-        { std::lock_guard<std::mutex> lk(g->mu); if (g->cancel) break; }
+        if (pipe.cancelled()) break;
     }
-    if (pending && !publish(pending, pending_slot)) { finish(dhts_error(c)); return; }
+    if (!rb.flush()) { finish(dhts_error(c)); return; }
     finish("");
 }
 static void bcf_read_global_init(duckdb_init_info info) {
@@ -259,44 +211,15 @@ static void bcf_read_global_init(duckdb_init_info info) {
     g->bind = bind;
     Projection pj; map_projection(info, (idx_t)bind->inf.n_cols, pj);
     g->column_ids.swap(pj.column_ids); g->slot.swap(pj.slot); g->proj.swap(pj.proj);
-    int thr = getenv("DHTS_THREADS") ? atoi(getenv("DHTS_THREADS")) : 1; if (thr < 1) thr = 1; if (thr > 64) thr = 64;
-    g->n_workers = thr;
-    for (int q = 0; q < 3; q++) { BcfHostBatch *hb = new BcfHostBatch(); g->free_slots.push_back(hb); g->all.push_back(hb); }
-    g->th = std::thread(bcf_producer_main, g);
+    const int thr = env_fill_threads();
+    g->pipe.init(1, 3, thr, dhts_host_alloc, dhts_host_free, [](void *c) { dhts_destroy((dhts_ctx *)c); });
+    g->pipe.start(0, [g] { bcf_producer_main(g); });
     API(void, duckdb_init_set_max_threads, duckdb_init_info, idx_t)(info, (idx_t)thr);
     API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, g, destroy_bcf_global);
 }
 
 static void bcf_read_local_init(duckdb_init_info info) {
     API(void, duckdb_init_set_init_data, duckdb_init_info, void *, duckdb_delete_callback_t)(info, new BcfLocal(), destroy_bcf_local);
-}
-
-// rows of the next ready batch for this worker (ordered mode: the whole batch; parallel mode: a slice); false = the scan is over
-static bool bcf_next_rows(BcfScan *g, BcfLocal *l, idx_t want) {
-    std::unique_lock<std::mutex> lk(g->mu);
-    if (l->cur) {
-        BcfHostBatch *hb = l->cur;
-        hb->readers--;
-        if (g->n_workers == 1 || (hb->retired && hb->readers == 0)) { g->free_slots.push_back(hb); g->cv_free.notify_all(); }
-        l->cur = nullptr;
-    }
-    for (;;) {
-        if (!g->error.empty()) return false;
-        while (!g->ready.empty()) {
-            BcfHostBatch *hb = g->ready.front();
-            if (g->n_workers == 1) { g->ready.pop_front(); hb->readers = 1; l->cur = hb; l->pos = 0; l->end = hb->n; return true; }
-            if (hb->next >= hb->n) {
-                g->ready.pop_front(); hb->retired = true;
-                if (hb->readers == 0) { g->free_slots.push_back(hb); g->cv_free.notify_all(); }
-                continue;
-            }
-            l->cur = hb; l->pos = hb->next; l->end = hb->next + (int64_t)want < hb->n ? hb->next + (int64_t)want : hb->n;
-            hb->next = l->end; hb->readers++;
-            return true;
-        }
-        if (g->done) return false;
-        g->cv_ready.wait(lk);
-    }
 }
 
 static size_t bcf_fixed_width(const dhts_bcf_colinfo &ci) {
@@ -310,10 +233,6 @@ static void bcf_fill(const BcfBind *bind, const BcfScan *g, const BcfHostBatch *
     auto get_vec = API(duckdb_vector, duckdb_data_chunk_get_vector, duckdb_data_chunk, idx_t);
     auto get_data = API(void *, duckdb_vector_get_data, duckdb_vector);
     auto assign_len = API(void, duckdb_vector_assign_string_element_len, duckdb_vector, idx_t, const char *, idx_t);
-    auto list_size = API(idx_t, duckdb_list_vector_get_size, duckdb_vector);
-    auto list_reserve = API(duckdb_state, duckdb_list_vector_reserve, duckdb_vector, idx_t);
-    auto list_set_size = API(duckdb_state, duckdb_list_vector_set_size, duckdb_vector, idx_t);
-    auto list_child = API(duckdb_vector, duckdb_list_vector_get_child, duckdb_vector);
     for (size_t ci = 0; ci < g->column_ids.size(); ci++) {
         if (g->slot[ci] < 0) continue;                          // ids outside the schema write nothing
         const dhts_bcf_col &h = hb->cols[g->slot[ci]];
@@ -338,15 +257,8 @@ static void bcf_fill(const BcfBind *bind, const BcfScan *g, const BcfHostBatch *
             continue;
         }
         // LIST: entries {offset = current child size, length}; children appended in row order (bcf_reader.c:1403-1424, 1436-1461, 1584-1610)
-        duckdb_list_entry *le = (duckdb_list_entry *)get_data(vec);
-        idx_t base = list_size(vec);
-        const uint32_t c0 = h.off[s], c1 = h.off[s + take];
-        if (c1 > c0) { list_reserve(vec, base + (c1 - c0)); list_set_size(vec, base + (c1 - c0)); }
-        duckdb_vector child = list_child(vec);
-        for (idx_t r = 0; r < take; r++) {
-            le[row_count + r].offset = base + (h.off[s + r] - c0); le[row_count + r].length = h.off[s + r + 1] - h.off[s + r];
-            if (!h.valid[s + r]) set_null(vec, row_count + r);
-        }
+        const ListFrame f = list_entries(vec, h.off, h.valid, s, take, row_count);
+        const idx_t base = f.base; const uint32_t c0 = f.c0, c1 = f.c1; duckdb_vector child = f.child;
         if (c1 > c0) {
             const std::vector<uint32_t> &cv32 = hb->conv[g->slot[ci]];
             if (names) for (uint32_t k = c0; k < c1; k++) { const char *nm = name_of((int32_t)h.child_fixed[k]); assign_len(child, base + (k - c0), nm, strlen(nm)); }
@@ -371,25 +283,11 @@ static void bcf_read_function(duckdb_function_info info, duckdb_data_chunk outpu
     BcfScan *g = (BcfScan *)API(void *, duckdb_function_get_init_data, duckdb_function_info)(info);
     BcfLocal *l = (BcfLocal *)API(void *, duckdb_function_get_local_init_data, duckdb_function_info)(info);
     auto set_size = API(void, duckdb_data_chunk_set_size, duckdb_data_chunk, idx_t);
-    if (!l || !g || l->done) { set_size(output, 0); return; }                                 // bcf_reader.c:1166-1169
-    const idx_t vector_size = API(idx_t, duckdb_vector_size, void)();
-    idx_t row_count = 0;
-    while (row_count < vector_size) {
-        if (!l->cur || l->pos >= l->end) {
-            if (g->n_workers > 1 && row_count > 0) break;       // parallel mode: one slice per chunk
-            if (!bcf_next_rows(g, l, vector_size)) {
-                l->done = true;
-                std::string err; { std::lock_guard<std::mutex> lk(g->mu); err = g->error; }
-                if (!err.empty()) { API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, err.c_str()); set_size(output, 0); return; }
-                break;
-            }
-        }
-        idx_t take = (idx_t)(l->end - l->pos); if (take > vector_size - row_count) take = vector_size - row_count;
-        bcf_fill(bind, g, l->cur, l->pos, take, output, row_count);
-        row_count += take; l->pos += (int64_t)take;
-    }
-    if (l->done && l->cur) { std::lock_guard<std::mutex> lk(g->mu); l->cur->readers--; if (g->n_workers == 1 || (l->cur->retired && l->cur->readers == 0)) { g->free_slots.push_back(l->cur); g->cv_free.notify_all(); } l->cur = nullptr; }
-    set_size(output, row_count);
+    if (!l || !g) { set_size(output, 0); return; }                                            // bcf_reader.c:1166-1169
+    std::string err;
+    const int64_t n = g->pipe.fill_chunk(l->at, API(idx_t, duckdb_vector_size, void)(), err, [&](const BcfHostBatch &hb, int64_t s, idx_t take, idx_t row_count) { bcf_fill(bind, g, &hb, s, take, output, row_count); });
+    if (n < 0) API(void, duckdb_function_set_error, duckdb_function_info, const char *)(info, err.c_str());
+    set_size(output, n < 0 ? 0 : (idx_t)n);
 }
 
 extern "C" __attribute__((visibility("default"))) void register_read_bcf_function(duckdb_connection connection) {                       // bcf_reader.c:2055-2080

@@ -63,8 +63,7 @@ static void bam_bedcov_init(duckdb_init_info info) {
         if (rc == 0 && !bind->index_bytes.empty()) rc = dhts_bam_load_index(c, bind->index_bytes.data(), bind->index_bytes.size());
     }
     if (rc == 0) rc = dhts_bam_bedcov_open(c, g->bed, &bind->P);
-    static const int64_t env_mb = getenv("DHTS_BATCH_BLOCKS") ? atoll(getenv("DHTS_BATCH_BLOCKS")) : 0;
-    if (rc == 0 && dhts_bam_bedcov_scan(c, env_mb > 0 ? env_mb : 0) < 0) {
+    if (rc == 0 && dhts_bam_bedcov_scan(c, env_batch_blocks(0)) < 0) {
         // a stream that ends on an error ends the scan silently, its rows counted (bam_reader.c:754-766); a call that failed is the error
         dhts_bedcov_stats st;
         if (dhts_bam_bedcov_stats(c, &st) != 0 || st.status == 0) rc = -1;

@@ -92,8 +92,7 @@ static void bam_bedgraph_init(duckdb_init_info info) {
     }
     // (the depth table is made here, not at bind: overlapping regions and a table over the cap are this call's errors)
     if (rc == 0) rc = dhts_bam_bedgraph_open(c, &bind->P, g->bed);
-    static const int64_t env_mb = getenv("DHTS_BATCH_BLOCKS") ? atoll(getenv("DHTS_BATCH_BLOCKS")) : 0;
-    if (rc == 0 && dhts_bam_bedgraph_scan(c, env_mb > 0 ? env_mb : 0) < 0) {
+    if (rc == 0 && dhts_bam_bedgraph_scan(c, env_batch_blocks(0)) < 0) {
         // a stream that ends on an error ends the scan silently, its rows counted (bam_reader.c:754-766); a call that failed is the error
         dhts_bedgraph_stats st;
         if (dhts_bam_bedgraph_stats(c, &st) != 0 || st.status == 0) rc = -1;

@@ -73,8 +73,7 @@ static void bam_bedgraph_export_init(duckdb_init_info info) {
         if (rc == 0 && !bind->index_bytes.empty()) rc = dhts_bam_load_index(c, bind->index_bytes.data(), bind->index_bytes.size());
     }
     if (rc == 0) rc = dhts_bam_bedgraph_open(c, &bind->P, bed);
-    static const int64_t env_mb = getenv("DHTS_BATCH_BLOCKS") ? atoll(getenv("DHTS_BATCH_BLOCKS")) : 0;
-    if (rc == 0 && dhts_bam_bedgraph_scan(c, env_mb > 0 ? env_mb : 0) < 0) {
+    if (rc == 0 && dhts_bam_bedgraph_scan(c, env_batch_blocks(0)) < 0) {
         dhts_bedgraph_stats st;                                // (a stream that ends on an error has its rows counted and written; a call that failed is the error)
         if (dhts_bam_bedgraph_stats(c, &st) != 0 || st.status == 0) rc = -1;
     }

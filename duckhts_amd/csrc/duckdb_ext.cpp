@@ -1,6 +1,6 @@
 // duckdb_ext.cpp -- DuckDB C-API extension surface (outer drop-in boundary) over the MI355X scan path.
 //
-// The table functions live in the parts included below, one per reader family, over the shared helpers of duckdb_surface.h:
+// The table functions live in the parts included below, one per reader family, over the shared helpers of duckdb_surface.h; read_bam and read_bcf run the batch pipeline of duckdb_pipeline.h (producer threads, pinned slots, parallel fill):
 //   duckdb_bam.inc read_bam, duckdb_bins.inc bam_bin_counts, duckdb_bedcov.inc bam_bedcov, duckdb_bcf.inc read_bcf, duckdb_seq.inc read_fastq / read_fasta, duckdb_interval.inc read_bed / fasta_nuc, duckdb_interval_algebra.inc interval_merge / interval_overlap,
 //   duckdb_tabix.inc read_tabix / read_gtf / read_gff, duckdb_udf.inc the k-mer family, duckdb_bedgraph.inc bam_bedgraph, duckdb_depth_hist.inc bam_depth_hist, duckdb_bedgraph_export.inc bam_bedgraph_export; duckdb_tools.cpp (its own translation unit) the writers.
 // The htslib calls underneath are replaced by include/duckhts_amd.h (HIP kernels); DuckDB is reached only
@@ -12,14 +12,11 @@
 // unchanged.  This file also carries a weak definition of that global and a weak duckhts_init_c_api, which
 // are what a stand-alone libduckhts_amd.so uses; strong definitions from src/duckhts.c win at link time.
 #include "duckdb_surface.h"
+#include "duckdb_pipeline.h"
 #include "bam_filter_check.h"
 
-#include <time.h>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
 #include <cmath>
-#include <thread>
+#include <mutex>
 
 // duckdb_ext_api_v1 viewed as an array of function pointers (duckdb_surface.h: API).  Weak: the definition
 // DUCKDB_EXTENSION_GLOBAL emits in a reference-built src/duckhts.c (duckdb_extension.h:1151) replaces it.
@@ -31,7 +28,6 @@ extern "C" __attribute__((visibility("default"))) void dhts_set_duckdb_api(const
 }
 
 extern "C" void dhts_debug_malloc_stats(uint64_t *calls, uint64_t *bytes, double *seconds);
-static double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 
 #include "duckdb_bam.inc"
 #include "duckdb_bins.inc"

@@ -48,8 +48,7 @@ static dhts_ctx *ivl_open_file(const char *fn, const std::string &path, std::str
     if (dhts_open_path(c, path.c_str()) != 0) { msg = "read_bed: failed to open file during init"; dhts_destroy(c); return nullptr; }
     (void)dhts_bgzf_index(c);                                  // (text that is not BGZF fails here and is taken as text by dhts_bed_open)
     if (dhts_bed_open(c) != 0) { msg = "read_bed: failed to open file during init"; dhts_destroy(c); return nullptr; }
-    static const int64_t env_mb = getenv("DHTS_BATCH_BLOCKS") ? atoll(getenv("DHTS_BATCH_BLOCKS")) : 0;
-    if (dhts_ivl_load(c, env_mb > 0 ? env_mb : 0) != 0) { msg = dhts_error(c); dhts_destroy(c); return nullptr; }
+    if (dhts_ivl_load(c, env_batch_blocks(0)) != 0) { msg = dhts_error(c); dhts_destroy(c); return nullptr; }
     return c;
 }
 static void interval_init(duckdb_init_info info) {

@@ -1,6 +1,7 @@
 // duckdb_surface.h -- what the DuckDB table functions share (duckdb_ext.cpp with its duckdb_*.inc parts, duckdb_tools.cpp): one
-// definition per idiom of the C-API surface.  Registration, parameter access, result columns, the bind-time context, the file
-// helpers of the region readers, the pinned read-back arena, the projection map and the chunk loop over a batch of dhts_col columns.
+// definition per idiom of the C-API surface.  Registration, parameter access, result columns, the environment switches, the bind-time
+// context, the file helpers of the region readers, the streaming open, the pinned read-back arena, the projection map, the LIST / MAP entry
+// frame and the chunk loop over a batch of dhts_col columns.  (The batch pipeline of read_bam and read_bcf is duckdb_pipeline.h.)
 // static / inline only: every translation unit that includes it gets its own copy, nothing here is exported.
 #ifndef DUCKHTS_DUCKDB_SURFACE_H
 #define DUCKHTS_DUCKDB_SURFACE_H
@@ -11,6 +12,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include <string>
 #include <vector>
 
@@ -115,6 +117,21 @@ static inline std::vector<int> device_list() {
     if (d.empty()) d.push_back(getenv("DHTS_DEVICE") ? atoi(getenv("DHTS_DEVICE")) : 0);
     return d;
 }
+// ---- the scan's environment switches, each read once per process -------------------------------------------------------------------
+static inline bool env_is_zero(const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; }
+static inline int64_t env_batch_blocks(int64_t dflt) {                 // DHTS_BATCH_BLOCKS: BGZF blocks per batch (every caller has its own default)
+    static const int64_t v = getenv("DHTS_BATCH_BLOCKS") ? atoll(getenv("DHTS_BATCH_BLOCKS")) : 0;
+    return v > 0 ? v : dflt;
+}
+static inline int env_fill_threads() {                                 // DHTS_THREADS: workers that fill chunks, 1..64 (1: rows in file order)
+    const int t = getenv("DHTS_THREADS") ? atoi(getenv("DHTS_THREADS")) : 1;
+    return t < 1 ? 1 : t > 64 ? 64 : t;
+}
+static inline bool env_stream() { static const bool v = !env_is_zero("DHTS_STREAM"); return v; }                       // 0: stage the whole file before the scan starts
+static inline bool env_overlap_readback() { static const bool v = !env_is_zero("DHTS_OVERLAP_READBACK"); return v; }   // 0: copy a batch, wait, hand it over
+static inline bool env_sparse() { static const bool v = !env_is_zero("DHTS_SPARSE"); return v; }                       // 0: a region query stages the whole file
+static inline double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
+
 static inline int env_device() { return getenv("DHTS_DEVICE") ? atoi(getenv("DHTS_DEVICE")) : 0; }
 static inline std::string no_device_message(const char *fn_name) { return std::string(fn_name) + ": no MI355X (gfx950) device available; this build has no CPU fallback"; }
 // a context on `device` (default: the first of device_list()); nullptr with err = the function's no-device message
@@ -133,6 +150,10 @@ static inline bool read_file(const std::string &path, std::string &out) {
     while ((n = fread(buf, 1, sizeof(buf), f)) > 0) out.append(buf, n);
     fclose(f);
     return true;
+}
+static inline bool read_file(const std::string &path, std::vector<uint8_t> &out) {
+    std::string s; if (!read_file(path, s)) return false;
+    out.assign(s.begin(), s.end()); return true;
 }
 // the 18 bytes of a BGZF block header: gzip, deflate, FEXTRA, subfield 'B' 'C'
 static inline bool file_is_bgzf(const std::string &path) {
@@ -154,6 +175,30 @@ static inline int stage_region_windows(dhts_ctx *c, const std::string &path, reg
     *seg_rc = segments(c, region.c_str(), index.data(), index.size(), beg, end, 4096, &cnt);
     if (*seg_rc != 0 || cnt < min_count) return WINDOWS_NOT_STAGED;
     return dhts_open_path_segments(c, path.c_str(), 0, beg, end, cnt) != 0 ? WINDOWS_OPEN_FAILED : WINDOWS_STAGED;
+}
+
+// ---- a scan that starts while the file is still being staged (dhts_open_path_async): the block table is built over the resident prefix ----
+// The header needs the first blocks only: `want` bytes to start with, four times more whenever open(c) cannot read it from those.
+template <class Open>
+static inline int stream_open(dhts_ctx *c, uint64_t want, int *staged_all, Open open) {
+    for (;;) {
+        if (dhts_stage_wait(c, want, staged_all) < 0) return -1;
+        if (dhts_bgzf_index_staged(c) > 0 && open(c) == 0) return 0;
+        if (*staged_all) return -1;
+        want *= 4;
+    }
+}
+// Before a batch: with fewer than max_blocks known blocks ahead, wait for (at least) another 128 MiB of the file, then extend the block
+// table.  0: nothing to do, 1: extended (seconds[0] waiting for bytes, seconds[1] in the table), -1: failed (dhts_error).
+static inline int stream_extend(dhts_ctx *c, int64_t max_blocks, int *staged_all, double *seconds = nullptr) {
+    if (*staged_all || dhts_blocks_ahead(c) >= max_blocks) return 0;
+    const double t0 = now_s();
+    int64_t f = dhts_stage_wait(c, 0, staged_all);
+    if (f >= 0 && !*staged_all) f = dhts_stage_wait(c, (uint64_t)f + (128u << 20), staged_all);
+    const double t1 = now_s();
+    if (f < 0 || dhts_bgzf_index_staged(c) < 0) return -1;
+    if (seconds) { seconds[0] += t1 - t0; seconds[1] += now_s() - t1; }
+    return 1;
 }
 
 // ---- pinned host memory a batch is read back into; grows with a quarter of slack, kept from batch to batch --------------------------
@@ -181,6 +226,22 @@ static inline void map_projection(duckdb_init_info info, idx_t limit, Projection
         }
         p.slot.push_back(at);
     }
+}
+
+// ---- the entries of a LIST / MAP vector for rows [s, s + take): row r owns the children off[r] .. off[r + 1] - 1, which the caller appends
+// behind the vector's current child size, in row order.  A row whose valid byte is 0 is NULL; its entry {offset, 0} is written all the same,
+// unless null_keeps_entry: read_bam's absent B tag sets NULL and leaves the entry untouched (src/bam_reader.c:927-930).
+struct ListFrame { idx_t base; uint32_t c0, c1; duckdb_vector child; };      // children c0 .. c1 - 1 go to child rows base ..
+static inline ListFrame list_entries(duckdb_vector vec, const uint32_t *off, const uint8_t *valid, int64_t s, idx_t take, idx_t row_count, bool null_keeps_entry = false) {
+    duckdb_list_entry *le = (duckdb_list_entry *)API(void *, duckdb_vector_get_data, duckdb_vector)(vec);
+    ListFrame f; f.base = API(idx_t, duckdb_list_vector_get_size, duckdb_vector)(vec); f.c0 = off[s]; f.c1 = off[s + (int64_t)take];
+    if (f.c1 > f.c0) { API(duckdb_state, duckdb_list_vector_reserve, duckdb_vector, idx_t)(vec, f.base + (f.c1 - f.c0)); API(duckdb_state, duckdb_list_vector_set_size, duckdb_vector, idx_t)(vec, f.base + (f.c1 - f.c0)); }
+    f.child = API(duckdb_vector, duckdb_list_vector_get_child, duckdb_vector)(vec);
+    for (idx_t r = 0; r < take; r++) {
+        if (valid[s + r] || !null_keeps_entry) { le[row_count + r].offset = f.base + (off[s + r] - f.c0); le[row_count + r].length = off[s + r + 1] - off[s + r]; }
+        if (!valid[s + r]) set_null(vec, row_count + r);
+    }
+    return f;
 }
 
 // ---- the chunk loop of the one-thread readers over a batch of dhts_col columns read back into host memory ----------------------------
@@ -229,20 +290,12 @@ static inline void fill_col(duckdb_vector vec, int kind, const dhts_col &hc, con
     case COL_MAP: {
         // entries {offset = current child size, length}, keys and values appended in row order (fill_attr_map src/tabix_reader.c:412-494)
         const dhts_tabix_map &m = *map;
-        duckdb_list_entry *le = (duckdb_list_entry *)get_data(vec);
-        const idx_t base = API(idx_t, duckdb_list_vector_get_size, duckdb_vector)(vec);
-        const uint32_t c0 = m.pair_off[s], c1 = m.pair_off[s + (int64_t)take];
-        if (c1 > c0) { API(duckdb_state, duckdb_list_vector_reserve, duckdb_vector, idx_t)(vec, base + (c1 - c0)); API(duckdb_state, duckdb_list_vector_set_size, duckdb_vector, idx_t)(vec, base + (c1 - c0)); }
-        duckdb_vector child = API(duckdb_vector, duckdb_list_vector_get_child, duckdb_vector)(vec);
-        duckdb_vector kvec = API(duckdb_vector, duckdb_struct_vector_get_child, duckdb_vector, idx_t)(child, 0);
-        duckdb_vector vvec = API(duckdb_vector, duckdb_struct_vector_get_child, duckdb_vector, idx_t)(child, 1);
-        for (idx_t r = 0; r < take; r++) {
-            le[row_count + r].offset = base + (m.pair_off[s + r] - c0); le[row_count + r].length = m.pair_off[s + r + 1] - m.pair_off[s + r];
-            if (!m.valid[s + r]) set_null(vec, row_count + r);
-        }
-        for (uint32_t k = c0; k < c1; k++) {
-            assign_len(kvec, base + (k - c0), (const char *)m.key_bytes + m.key_off[k], m.key_off[k + 1] - m.key_off[k]);
-            assign_len(vvec, base + (k - c0), (const char *)m.val_bytes + m.val_off[k], m.val_off[k + 1] - m.val_off[k]);
+        const ListFrame f = list_entries(vec, m.pair_off, m.valid, s, take, row_count);
+        duckdb_vector kvec = API(duckdb_vector, duckdb_struct_vector_get_child, duckdb_vector, idx_t)(f.child, 0);
+        duckdb_vector vvec = API(duckdb_vector, duckdb_struct_vector_get_child, duckdb_vector, idx_t)(f.child, 1);
+        for (uint32_t k = f.c0; k < f.c1; k++) {
+            assign_len(kvec, f.base + (k - f.c0), (const char *)m.key_bytes + m.key_off[k], m.key_off[k + 1] - m.key_off[k]);
+            assign_len(vvec, f.base + (k - f.c0), (const char *)m.val_bytes + m.val_off[k], m.val_off[k + 1] - m.val_off[k]);
         }
         break;
     }

@@ -291,7 +291,7 @@ int main(int argc, char **argv) {
     if (!tf) { printf("ERROR catalog: table function %s not registered\n", argv[2]); return 3; }
 
     const char *proj = NULL, *out = NULL;
-    int threads = 0, repeat = 1;
+    int threads = 0, repeat = 1, limit_first = 0;
     static char names[16][32], vals[16][512]; int n_named = 0;
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "-n") && i + 1 < argc) {
@@ -304,6 +304,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
         else if (!strcmp(argv[i], "-t") && i + 1 < argc) threads = atoi(argv[++i]);       /* worker threads offered to the scan (<= max_threads it asks for) */
         else if (!strcmp(argv[i], "-l") && i + 1 < argc) g_limit = strtoull(argv[++i], NULL, 10);
+        else if (!strcmp(argv[i], "-L") && i + 1 < argc) { g_limit = strtoull(argv[++i], NULL, 10); limit_first = 1; }   /* -l for the first run only: the runs behind it (-r) take everything */
         else if (!strcmp(argv[i], "-r") && i + 1 < argc) repeat = atoi(argv[++i]);        /* run the query this many times in one process (warm runs) */
     }
     for (int rep = 0; rep < repeat; rep++) {
@@ -336,6 +337,7 @@ int main(int argc, char **argv) {
         if (failed) return 3;
         clock_gettime(CLOCK_MONOTONIC, &t1);
         const double sec = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+        if (limit_first) g_limit = 0;
         if (repeat > 1) printf("RUN %d seconds=%.6f rows=%llu threads=%d\n", rep, sec, (unsigned long long)total, nthr);
         if (rep == repeat - 1) printf("OK rows=%llu chunks=%llu columns=%d max_threads=%llu\n", (unsigned long long)total, (unsigned long long)chunks, b.ncol, (unsigned long long)g.max_threads);
     }

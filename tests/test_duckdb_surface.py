@@ -124,11 +124,11 @@ def expect_chunks(exp, proj):
         yield c1 - c0, [(names[j], exp[names[j]][c0:c1]) for j in proj]
 
 
-def compare(path_bytes, proj=None, tmp_path=None):
+def compare(path_bytes, proj=None, tmp_path=None, env=None, exp=None):
     fn = os.path.join(str(tmp_path), "in.bam")
     open(fn, "wb").write(path_bytes)
-    exp = orc.bam_read(path_bytes)
-    rc, out, dump = run_host(fn, proj=proj)
+    exp = exp or orc.bam_read(path_bytes)
+    rc, out, dump = run_host(fn, proj=proj, env=env)
     assert rc == 0, out
     schema, chunks = parse_chunks(dump)
     assert schema == SCHEMA
@@ -231,11 +231,11 @@ def test_read_bcf_bind_errors_without_gpu_dependency():
         assert "unknown named parameter" not in out
 
 
-def compare_bcf(data, tmp_path, tidy=False, proj=None):
+def compare_bcf(data, tmp_path, tidy=False, proj=None, env=None, exp=None):
     fn = os.path.join(str(tmp_path), "in.bcf")
     open(fn, "wb").write(data)
-    exp = orc.bcf_read(data, tidy)
-    rc, out, dump = run_host(fn, named=[("tidy_format", "true")] if tidy else (), proj=proj, fn="read_bcf")
+    exp = exp or orc.bcf_read(data, tidy)
+    rc, out, dump = run_host(fn, named=[("tidy_format", "true")] if tidy else (), proj=proj, fn="read_bcf", env=env)
     assert rc == 0, out
     schema, chunks = parse_chunks(dump)
     want_schema = [(c["name"], CANON2DUCK[c["type"]]) if not c["is_list"] else (c["name"], LIST, CANON2DUCK[c["type"]]) for c in exp["cols"]]
@@ -582,3 +582,55 @@ def test_a_scan_that_is_abandoned_early_closes_cleanly(tmp_path):
     # one process: LIMIT first, then everything
     r = subprocess.run([HOST, duckhts_amd.LIB_PATH, "read_bcf", os.path.join(os.path.dirname(__file__), "golden", "vcf_file.bcf"), "-l", "1"], capture_output=True, text=True)
     assert r.returncode == 0 and "OK rows=15 " in r.stdout                                   # (a file smaller than one chunk)
+
+
+# ---- the pipeline's other forms: the serial read-back (DHTS_OVERLAP_READBACK=0) and the staged-first scan (DHTS_STREAM=0), on files of more
+# batches than the three slots of a producer, one worker: rows in file order, chunk for chunk the oracle's -----------------------------------
+PIPELINE_FORMS = [{"DHTS_OVERLAP_READBACK": "0"}, {"DHTS_STREAM": "0"}, {"DHTS_OVERLAP_READBACK": "0", "DHTS_STREAM": "0"}]
+_forms_ref = {}
+
+
+def _forms_file(kind):
+    """the file of a reader and the oracle's table of it, made once for the three forms"""
+    if kind not in _forms_ref:
+        from duckhts_amd import synth
+        if kind == "bam":
+            data = synth.bam_file(60000, seed=31)
+            _forms_ref[kind] = (data, orc.bam_read(data))
+        else:
+            data = synth.bcf_file(12000, seed=9) if hasattr(synth, "bcf_file") else synth.bcf_segment(12000, seed=9)[0].tobytes()
+            _forms_ref[kind] = (data, orc.bcf_read(data, False))
+    return _forms_ref[kind]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", PIPELINE_FORMS, ids=lambda e: "+".join(sorted(e)))
+def test_read_bam_serial_readback_and_staged_first(tmp_path, form):
+    """60,000 records in batches of 7 BGZF blocks: the slots recycle; rows and chunk sizes equal the oracle's exactly"""
+    data, exp = _forms_file("bam")
+    assert exp["n_rows"] == 60000
+    compare(data, tmp_path=tmp_path, env=dict(form, DHTS_BATCH_BLOCKS="7"), exp=exp)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", PIPELINE_FORMS, ids=lambda e: "+".join(sorted(e)))
+def test_read_bcf_serial_readback_and_staged_first(tmp_path, form):
+    """12,000 records in batches of 3 BGZF blocks, the columns test_read_bcf_parallel_fill projects: file order, the oracle's table"""
+    data, exp = _forms_file("bcf")
+    ncol = len(exp["cols"])
+    assert exp["n_rows"] == 12000
+    compare_bcf(data, tmp_path, proj=list(range(min(ncol, 14))) + [ncol - 1], env=dict(form, DHTS_BATCH_BLOCKS="3"), exp=exp)
+
+
+@pytest.mark.gpu
+def test_read_bcf_abandoned_under_limit_then_scanned_in_full(tmp_path):
+    """the BCF twin of the abandoned-scan test: with one BGZF block per batch the producer has filled its three slots and waits for a free
+    one when the engine, after one chunk, tears the scan down; the teardown returns and the full scan behind it in the same process is complete"""
+    data, exp = _forms_file("bcf")
+    fn = os.path.join(str(tmp_path), "l.bcf")
+    open(fn, "wb").write(data)
+    r = subprocess.run([HOST, duckhts_amd.LIB_PATH, "read_bcf", fn, "-L", "1", "-r", "2"], capture_output=True, text=True, env=dict(os.environ, DHTS_BATCH_BLOCKS="1"), timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    runs = [l for l in r.stdout.splitlines() if l.startswith("RUN ")]
+    assert len(runs) == 2 and " rows=2048 " in runs[0] and f" rows={exp['n_rows']} " in runs[1], r.stdout
+    assert f"OK rows={exp['n_rows']} " in r.stdout

@@ -165,6 +165,10 @@ class IvlStats(C.Structure):
                 ("sort_passes", C.c_int32), ("status", C.c_int32)]
 
 
+class IvlNearestStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_unmatched", C.c_uint64), ("end_sort_passes", C.c_uint32), ("status", C.c_int32)]
+
+
 class TabixMap(C.Structure):
     _fields_ = [("pair_off", C.c_void_p), ("valid", C.c_void_p), ("n_pairs", C.c_uint64), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p), ("key_nbytes", C.c_uint64),
                 ("val_off", C.c_void_p), ("val_bytes", C.c_void_p), ("val_nbytes", C.c_uint64)]
@@ -239,7 +243,10 @@ BEDGRAPH_EXPORT_INDEX = {"none": 0, "tbi": 1, "csi": 2}                     # th
 ROWS_TEXT_LDS_BYTES = 16384                                                 # csrc/rows_text.hip: RTX_LDS_BYTES, the longest span of 256 rows the write pass stages in LDS
 INTERVAL_MERGE_COLUMNS = ["chrom", "start", "end", "n_merged"]
 INTERVAL_OVERLAP_COLUMNS = ["chrom", "start", "end", "left_row", "right_start", "right_end", "right_row", "overlap"]
-INTERVAL_DTYPES = (np.int32,) + (np.int64,) * 7                              # chrom: the context's name id; every other column an int64
+INTERVAL_NEAREST_COLUMNS = INTERVAL_OVERLAP_COLUMNS + ["distance"]
+INTERVAL_TIES = {"all": 0, "first": 1}                                      # the C ABI's ties
+INTERVAL_MAX_K = 1 << 20
+INTERVAL_DTYPES = (np.int32,) + (np.int64,) * 8                              # chrom: the context's name id; every other column an int64
 INTERVAL_MODES = {"any": 0, "contain": 1, "within": 2}                      # the C ABI's mode
 INTERVAL_MAX_GAP = 1 << 40
 IVL_SORT_TILE = 4096                                                        # csrc/interval_sort.hip: IVL_SORT_TILE, the pairs one workgroup of the sort ranks
@@ -285,7 +292,7 @@ EXPORTS = ["dhts_abi_version", "dhts_device_count", "dhts_create", "dhts_destroy
            "dhts_bedgraph_export",
            "dhts_bam_hist_open", "dhts_bam_hist_accumulate", "dhts_bam_hist_scan", "dhts_bam_hist_stats", "dhts_bam_hist_next", "dhts_bam_hist_batch_host_bytes", "dhts_bam_hist_batch_fetch",
            "dhts_ivl_load", "dhts_ivl_stats_get", "dhts_ivl_chrom_name", "dhts_ivl_merge_open", "dhts_ivl_merge_next", "dhts_ivl_overlap_open", "dhts_ivl_overlap_next",
-           "dhts_ivl_batch_host_bytes", "dhts_ivl_batch_fetch",
+           "dhts_ivl_batch_host_bytes", "dhts_ivl_batch_fetch", "dhts_ivl_nearest_open", "dhts_ivl_nearest_next", "dhts_ivl_nearest_stats_get",
            "dhts_tabix_open", "dhts_tabix_set_conf", "dhts_tabix_index_conf", "dhts_tabix_sniff", "dhts_tabix_resolve_schema", "dhts_tabix_set_schema", "dhts_tabix_set_projection",
            "dhts_tabix_set_region", "dhts_tabix_load_index", "dhts_tabix_region_segments", "dhts_tabix_next_batch", "dhts_tabix_batch_host_bytes", "dhts_tabix_batch_fetch",
            "dhts_udf_upload", "dhts_udf_apply", "dhts_udf_result_host_bytes", "dhts_udf_fetch", "dhts_udf_seq_kmers", "dhts_udf_kmers_host_bytes", "dhts_udf_kmers_fetch"]
@@ -412,6 +419,9 @@ def lib():
         L.dhts_ivl_batch_host_bytes.restype = C.c_uint64
         L.dhts_ivl_batch_host_bytes.argtypes = [C.POINTER(BedBatch)]
         L.dhts_ivl_batch_fetch.argtypes = [C.c_void_p, C.POINTER(BedBatch), C.c_void_p, C.c_uint64, C.POINTER(BcfCol)]
+        L.dhts_ivl_nearest_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]
+        L.dhts_ivl_nearest_next.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(BedBatch)]
+        L.dhts_ivl_nearest_stats_get.argtypes = [C.c_void_p, C.POINTER(IvlNearestStats)]
         L.dhts_debug_ivl_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int32)]
         L.dhts_debug_ivl_ms.restype = C.c_double
         L.dhts_debug_ivl_ms.argtypes = [C.c_void_p, C.c_int]
@@ -1182,6 +1192,29 @@ class Context:
         self._chk(self.L.dhts_ivl_overlap_next(self.h, max_rows, mask, C.byref(b)))
         return self._ivl_fetch(b, mask, INTERVAL_OVERLAP_COLUMNS)
 
+    def ivl_nearest_open(self, right, k=1, max_distance=None, ties="all"):
+        """after ivl_load on both contexts (one device): right's end order built when it has none, every left row's nearest rows selected"""
+        if ties not in INTERVAL_TIES:
+            raise DhtsError("interval_nearest: ties must be 'all' or 'first'")
+        if not 1 <= int(k) <= INTERVAL_MAX_K:
+            raise DhtsError("interval_nearest: k must be between 1 and 1048576")
+        if max_distance is not None and int(max_distance) < 0:
+            raise DhtsError("interval_nearest: max_distance must not be negative")
+        self._chk(self.L.dhts_ivl_nearest_open(self.h, right.h if right is not None else None, int(k), -1 if max_distance is None else int(max_distance), INTERVAL_TIES[ties]))
+
+    def ivl_nearest_next(self, max_rows=0, columns=None):
+        """the next page of whole left rows: ({"n_rows", "chrom": the left context's int32 name ids, the other columns int64 arrays; None for
+        a column `columns` leaves out}, status)"""
+        mask = sum(1 << INTERVAL_NEAREST_COLUMNS.index(k) for k in (INTERVAL_NEAREST_COLUMNS if columns is None else columns))
+        b = BedBatch()
+        self._chk(self.L.dhts_ivl_nearest_next(self.h, max_rows, mask, C.byref(b)))
+        return self._ivl_fetch(b, mask, INTERVAL_NEAREST_COLUMNS)
+
+    def ivl_nearest_stats(self):
+        st = IvlNearestStats()
+        self._chk(self.L.dhts_ivl_nearest_stats_get(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in IvlNearestStats._fields_}
+
     def debug_ivl_sort(self, keys, rank):
         """tests, tools/bench_intervals.py: the sort alone.  keys: uint64, compared unsigned; rank: uint32 per row, the more significant part.
         (the row numbers in sorted order as uint32, the radix passes that were run)"""
@@ -1193,7 +1226,8 @@ class Context:
         return out[:len(k)], int(passes.value)
 
     def debug_ivl_ms(self, what):
-        """tools/bench_intervals.py: device milliseconds of a part (0 load, 1 sort, 2 index, 3 merge, 4 overlap count, 5 overlap write, 16 + p sort pass p)"""
+        """tools/bench_intervals.py: device milliseconds of a part (0 load, 1 sort, 2 index, 3 merge, 4 overlap count, 5 overlap write, 6 nearest end
+        order, 7 nearest selection, 8 nearest write, 16 + p sort pass p)"""
         return float(self.L.dhts_debug_ivl_ms(self.h, what))
 
     # ---- bam_bedgraph_export ----
@@ -2546,6 +2580,40 @@ def interval_overlap(left, right, mode="any", columns=None, device=0, max_rows=0
             stats.update({k: v for k, v in st.items() if k not in ("status", "n_runs")})
             stats["right"] = {k: v for k, v in rctx.ivl_stats().items() if k not in ("status", "n_runs", "n_pairs")}
         return _interval_result(lctx, parts, INTERVAL_OVERLAP_COLUMNS, st["status"])
+    finally:
+        if rctx is not None:
+            rctx.close()
+        lctx.close()
+
+
+def interval_nearest(left, right, k=1, max_distance=None, ties="all", columns=None, device=0, max_rows=0, max_blocks=0, stats=None):
+    """interval_nearest(path, right_path :=, k := 1, max_distance := NULL, ties := 'all' | 'first'): for every valid row of the left BED (paths or
+    bytes) the k nearest valid rows of the right BED on its chrom, selected and written on the device (the contract: include/duckhts_amd.h).
+    {"n_rows", "chrom": list of bytes, "start", "end", "left_row", "right_start", "right_end", "right_row", "overlap", "distance": int64 arrays --
+    None for a column `columns` leaves out --, "pages", "status"}, ordered by left_row, then (right_start, right_row).  stats (a dict) receives the
+    left file's n_rows, n_skipped, n_chroms, n_name_runs and sort_passes, the result's n_pairs, n_unmatched and end_sort_passes, and the right
+    file's under "right"."""
+    if right is None:
+        raise DhtsError("interval_nearest requires right_path")
+    if not 1 <= int(k) <= INTERVAL_MAX_K:
+        raise DhtsError("interval_nearest: k must be between 1 and 1048576")
+    if max_distance is not None and int(max_distance) < 0:
+        raise DhtsError("interval_nearest: max_distance must not be negative")
+    if ties not in INTERVAL_TIES:
+        raise DhtsError("interval_nearest: ties must be 'all' or 'first'")
+    lctx, rctx = _bed_ctx(device, left), None
+    try:
+        rctx = _bed_ctx(device, right)
+        lctx.ivl_load(max_blocks)
+        rctx.ivl_load(max_blocks)
+        lctx.ivl_nearest_open(rctx, k, max_distance, ties)
+        parts = _drain(lambda: lctx.ivl_nearest_next(max_rows, columns))
+        st = lctx.ivl_stats()
+        if stats is not None:
+            stats.update({k_: v for k_, v in st.items() if k_ not in ("status", "n_runs", "n_pairs")})
+            stats.update({k_: v for k_, v in lctx.ivl_nearest_stats().items() if k_ != "status"})
+            stats["right"] = {k_: v for k_, v in rctx.ivl_stats().items() if k_ not in ("status", "n_runs", "n_pairs")}
+        return _interval_result(lctx, parts, INTERVAL_NEAREST_COLUMNS, st["status"])
     finally:
         if rctx is not None:
             rctx.close()

@@ -25,6 +25,7 @@
 #include "bam_depth_hist.hip"
 #include "interval_sort.hip"
 #include "interval_algebra.hip"
+#include "interval_nearest.hip"
 #include "rows_text.hip"
 #include "gzip_serial.hip"
 #include "bam_tags.hip"
@@ -302,8 +303,13 @@ struct IvlState {
     DevBuf rank_of_id, rank_row, key[2], row[2], counts, part, bits;
     DevBuf s_beg, s_end, s_id, s_rank, rank_first, pair, pmax, bmax;
     DevBuf hidx, run_head, rank_of_left, cnt, cut;
-    DevBuf out[8]; std::vector<dhts_col> cols;
+    DevBuf out[9]; std::vector<dhts_col> cols;
     double ms[32] = {0};
+    // interval_nearest (interval_nearest.hip, dhts_interval_nearest.inc): as the right file, the ends in (rank, end) order, built on the first
+    // open that names this context as right; as the left file, the parameters, every row's D and tie quota beside cnt, and the result's stats
+    bool end_ready = false, near_open = false; int32_t end_sort_passes = 0, near_ties = 0; int64_t near_k = 1, near_max_distance = -1;
+    uint64_t near_pairs = 0, near_unmatched = 0;
+    DevBuf e_end, near_dist, near_quota;
 };
 // seq_* / cigar_* / flag functions on device columns (seq_udf.hip, dhts_seq_udf.inc): two upload slots for arguments, two result sets used in
 // turn (the result of the last call may be the argument of this one), and the columns of the last seq_kmers batch
@@ -605,7 +611,7 @@ static void reset_file_state(dhts_ctx *c) {
     stop_stager(c);
     c->huff_b0 = c->huff_nb = 0; c->file_off = 0; c->file_size = 0; c->seg_split = 0; c->seg_file_off = 0; c->partial_tail = false; c->segs.clear(); c->cache_hit = false; c->gz_plain = c->gz_error = false; c->gz_len = 0; c->plain_text = false; c->vcf_text = false; c->sam_text = false; c->fastq = 0; c->fa.text_ready = false; c->nuc.open = false; c->bins.open = false; c->cov.open = false; c->dep.open = false; c->text_any = false; c->bed.open = false; c->tbx.open = false;
     c->n_blocks = 0; c->bgzf_status = 0; c->bam_open = false; c->range_cut = false; c->last_batch_rows = -1; c->carry_len = 0; c->next_block = 0; c->stream_done = false; c->first_batch = true;
-    c->ivl.loaded = c->ivl.too_many = c->ivl.merge_open = c->ivl.ov_open = false;      // (an interval table is its file's)
+    c->ivl.loaded = c->ivl.too_many = c->ivl.merge_open = c->ivl.ov_open = c->ivl.end_ready = c->ivl.near_open = false;      // (an interval table is its file's)
     memset(c->tile_stats, 0, sizeof(c->tile_stats));
     c->last_stream = BamStream{};                             // (dhts_debug_tile_scan and the passes that read the latest batch refuse until a batch of the new file has been read)
     c->h_coff.clear(); c->h_clen.clear(); c->h_isize.clear(); c->h_uoff.clear();
@@ -672,6 +678,7 @@ int dhts_open_tiled(dhts_ctx *c, const void *head, uint64_t n_head, const void *
 #include "dhts_bam_bedgraph_export.inc"
 #include "dhts_bam_depth_hist.inc"
 #include "dhts_interval.inc"
+#include "dhts_interval_nearest.inc"
 #include "dhts_seq_udf.inc"
 #include "dhts_fetch.inc"
 

@@ -199,7 +199,7 @@ static int ivl_build_index(dhts_ctx *c) {
 int dhts_ivl_load(dhts_ctx *c, int64_t max_blocks) {
     if (!c) return -1;
     IvlState &S = c->ivl;
-    S.loaded = S.too_many = S.merge_open = S.ov_open = false; S.status = 0; S.right = nullptr;
+    S.loaded = S.too_many = S.merge_open = S.ov_open = S.end_ready = S.near_open = false; S.status = 0; S.right = nullptr; S.end_sort_passes = 0;
     S.n_rows = S.n_valid = S.n_skipped = S.n_name_runs = S.n_runs = S.n_pairs = S.cursor = 0; S.sort_passes = 0;
     S.names.clear(); S.id_of.clear(); S.rank_of.clear();
     for (double &x : S.ms) x = 0;
@@ -280,7 +280,7 @@ int dhts_ivl_merge_open(dhts_ctx *c, int64_t max_gap) {
         HIPCHK(c, hipGetLastError());
     }
     S.ms[IVL_MS_MERGE] = clk.stop();
-    S.n_runs = runs; S.cursor = 0; S.ov_open = false; S.merge_open = true;
+    S.n_runs = runs; S.cursor = 0; S.ov_open = S.near_open = false; S.merge_open = true;
     return 0;
 }
 int dhts_ivl_merge_next(dhts_ctx *c, int64_t max_rows, uint32_t colmask, dhts_ivl_batch *out) {
@@ -353,7 +353,7 @@ int dhts_ivl_overlap_open(dhts_ctx *c, dhts_ctx *r, int32_t mode) {
     S.ms[IVL_MS_COUNT] = clk.stop();
     HIPCHK(c, hipStreamSynchronize(c->stream));
     S.ms[IVL_MS_WRITE] = 0;
-    S.n_pairs = pairs; S.cursor = 0; S.right = r; S.merge_open = false; S.ov_open = true;
+    S.n_pairs = pairs; S.cursor = 0; S.right = r; S.merge_open = S.near_open = false; S.ov_open = true;
     return 0;
 }
 int dhts_ivl_overlap_next(dhts_ctx *c, int64_t max_rows, uint32_t colmask, dhts_ivl_batch *out) {

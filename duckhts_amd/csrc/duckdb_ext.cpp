@@ -35,6 +35,7 @@ extern "C" void dhts_debug_malloc_stats(uint64_t *calls, uint64_t *bytes, double
 #include "duckdb_seq.inc"
 #include "duckdb_interval.inc"
 #include "duckdb_interval_algebra.inc"
+#include "duckdb_interval_nearest.inc"
 #include "duckdb_bedcov.inc"
 #include "duckdb_coverage.inc"
 #include "duckdb_depth.inc"
@@ -68,6 +69,7 @@ extern "C" __attribute__((visibility("default"), weak)) bool duckhts_init_c_api(
     // fasta_nuc follows read_bed (src/duckhts.c:59-60), behind a variable of its own: DHTS_NUC_FUNCTIONS=1
     if (const char *e = getenv("DHTS_NUC_FUNCTIONS")) if (atoi(e) == 1) register_fasta_nuc_function(conn);
     if (const char *e = getenv("DHTS_ALGEBRA_FUNCTIONS")) if (atoi(e) == 1) { register_interval_merge_function(conn); register_interval_overlap_function(conn); }   // interval_merge, interval_overlap: their place in src/interval_udf.c (PLAN.md 10.5.2), behind a variable of their own
+    if (const char *e = getenv("DHTS_NEAREST_FUNCTIONS")) if (atoi(e) == 1) register_interval_nearest_function(conn);   // interval_nearest: behind the two, its place in src/interval_udf.c, under a variable of its own
     // the k-mer family follows tabix_index and precedes read_tabix (src/duckhts.c:66), behind a variable of its own: DHTS_KMER_FUNCTIONS=1
     if (const char *e = getenv("DHTS_KMER_FUNCTIONS")) if (atoi(e) == 1) register_kmer_udf_functions(conn);
     // read_tabix, read_gtf, read_gff close the list (src/duckhts.c:67-69), opt-in: DHTS_TABIX_FUNCTIONS=1

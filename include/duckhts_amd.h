@@ -1316,6 +1316,54 @@ int dhts_ivl_overlap_next(dhts_ctx *left, int64_t max_rows, uint32_t colmask, dh
 uint64_t dhts_ivl_batch_host_bytes(const dhts_ivl_batch *b);
 int dhts_ivl_batch_fetch(dhts_ctx *bed, const dhts_ivl_batch *b, void *dst, uint64_t cap, dhts_col *out_cols);
 
+/* ---- interval nearest: interval_nearest ----------------------------------------------------------
+ * interval_nearest(path, right_path :=, k := 1, max_distance := NULL, ties := 'all' | 'first'): for every row of the left file the k nearest
+ * rows of the right file on its chrom.  It completes the plan's Layer 1 (.github/PLAN.md 10.5.2 / 10.7.1); the reference has no code for it and
+ * cgranges no model, so the rules below are the specification.  They follow `bedtools closest -k -t all|first` in the coordinates and orders of
+ * interval_overlap.
+ *   Rows, validity, row numbers and chrom comparison are those of the block above: only valid rows take part, invalid ones keep their number
+ *     and are counted in n_skipped (dhts_ivl_stats_get); a left chrom the right file lacks gives no rows.
+ *   For a valid left row l = [s, e) and a valid right row r = [rs, re) of the same chrom:
+ *     distance = max(0, rs - e, s - re), the gap in bases: 0 for rows that overlap or touch, as touching rows merge at max_gap = 0.
+ *       `bedtools closest -d` prints this plus one for rows that do not overlap.  With positions in [-2^62, 2^62) every distance fits an
+ *       int64; the largest is 2^63 - 1.
+ *     overlap = max(0, min(e, re) - max(s, rs)), as in interval_overlap.
+ *   Candidates of l: the right rows of its chrom with distance <= max_distance, all of them when max_distance is absent (-1 in this ABI),
+ *     ranked by (distance, right_start, right_row).
+ *     ties = 'first' emits the first min(k, candidates) of that ranking.
+ *     ties = 'all' (the default): when there are more than k candidates, every candidate whose distance is at most that of the k-th.
+ *     A left row with no candidate emits nothing and is counted in n_unmatched.  No column is ever NULL.
+ *   Columns: chrom, start, end, left_row, right_start, right_end, right_row, overlap, distance -- interval_overlap's eight in its order, then
+ *     distance.  Order: by left_row; within a left row by (right_start, right_row): interval_overlap's order, not distance order.
+ *   Paging: whole left rows, as for interval_overlap (0 = 1,048,576 rows; at least one left row a page).
+ *   Limits: k 1 .. 1,048,576 ("interval_nearest: k must be between 1 and 1048576"); max_distance >= 0 ("interval_nearest: max_distance must
+ *     not be negative"); ties ("interval_nearest: ties must be 'all' or 'first'"); fewer than 2^32 - 16 rows per file.
+ *   Not in this contract: strand or direction restriction (bedtools -D, -iu / -id); ignoring overlaps (-io); unmatched left rows (a left
+ *     join); distance-ordered output (ORDER BY distance in SQL).
+ *   Method: beside the index of the block above the right file gets a second order, its ends sorted by (chrom rank, end) with the same radix
+ *     sort, built on the first dhts_ivl_nearest_open that names the context as right and dropped by dhts_ivl_load.  Selection, one lane per
+ *     left row with binary searches alone: the rows within D number nb(e + D + 1) - ne(s - D) (starts in front, ends in front); the rows
+ *     farther than 0 are two sequences sorted by distance, and the k-th distance is found by the partition search of two sorted sequences in
+ *     O(log k).  The count, D and the tie quota are stored per left row; a 64-bit carry gives the offsets; a write pass per page walks the
+ *     start order from the first row whose running maximum end admits a hit, 64-row blocks skipped (csrc/interval_nearest.hip).
+ * One result is open per context: dhts_ivl_nearest_open closes a merge or overlap result, and their opens close this one.  Every error is
+ * prefixed "interval_nearest:". */
+enum { DHTS_IVL_NEAR_CHROM = 0, DHTS_IVL_NEAR_START, DHTS_IVL_NEAR_END, DHTS_IVL_NEAR_LEFT_ROW, DHTS_IVL_NEAR_RIGHT_START, DHTS_IVL_NEAR_RIGHT_END,
+       DHTS_IVL_NEAR_RIGHT_ROW, DHTS_IVL_NEAR_OVERLAP, DHTS_IVL_NEAR_DISTANCE, DHTS_IVL_NEAR_COL_COUNT };
+enum { DHTS_IVL_TIES_ALL = 0, DHTS_IVL_TIES_FIRST = 1 };
+#define DHTS_IVL_MAX_K 1048576
+typedef struct {
+    uint64_t n_pairs;            /* rows of the result                                                          */
+    uint64_t n_unmatched;        /* valid left rows without a candidate                                         */
+    uint32_t end_sort_passes;    /* radix passes of the right context's end sort (of 12)                        */
+    int32_t status;              /* as dhts_ivl_stats.status of the left context                                */
+} dhts_ivl_nearest_stats;
+/* left and right: two loaded contexts on one device; right has to stay as it is while the result is paged out.  max_distance -1: none.  Every
+ * left row's count is taken here.  The batches are dhts_ivl_batch with DHTS_IVL_NEAR_COL_COUNT columns, fetched with dhts_ivl_batch_fetch. */
+int dhts_ivl_nearest_open(dhts_ctx *left, dhts_ctx *right, int64_t k, int64_t max_distance, int32_t ties);
+int dhts_ivl_nearest_next(dhts_ctx *left, int64_t max_rows, uint32_t colmask, dhts_ivl_batch *out);
+int dhts_ivl_nearest_stats_get(dhts_ctx *left, dhts_ivl_nearest_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

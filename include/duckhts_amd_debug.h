@@ -107,7 +107,9 @@ int dhts_debug_tr_diag(dhts_ctx *, unsigned long long *out16, int reset);
  * in all pairs is skipped). */
 int dhts_debug_ivl_sort(dhts_ctx *, const uint64_t *keys_u64, const uint32_t *rank_u32, uint64_t n, uint32_t *rows_out_u32, int32_t *passes);
 /* tools/bench_intervals.py: device time in milliseconds of the parts of the last dhts_ivl_load (0 load, 1 sort, 2 index), dhts_ivl_merge_open
- * (3), dhts_ivl_overlap_open (4: the count pass and its carry) and of the write passes of the pages taken since (5), and of sort pass p (16 + p) */
+ * (3), dhts_ivl_overlap_open (4: the count pass and its carry) and of the write passes of the pages taken since (5), and of sort pass p (16 + p);
+ * of the last dhts_ivl_nearest_open on the left context: 6 the end sort and gather of the right context (0 when it had its end order already;
+ * the right context keeps the figure under 6 as well), 7 the selection pass and its carry, 8 the write passes of the pages taken since */
 double dhts_debug_ivl_ms(dhts_ctx *, int what);
 
 #ifdef __cplusplus

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times interval_merge / interval_overlap on the device and prints ONE JSON line.
+"""Times interval_merge / interval_overlap / interval_nearest on the device and prints ONE JSON line.
 
 Seeded BED text is made in memory at every size of --sizes (default 10^6 and 10^7 rows) in five shapes:
     tiling       sorted, back to back on 6 chroms
@@ -14,7 +14,10 @@ per pair and pass (the count reads the key, the scatter reads and writes key and
 8.0 TB/s HBM peak of MI355X_MICROARCH.md.  "host_build_ms": the index build the BAM join still uses (dhts_bam_set_overlap_intervals: a host
 std::stable_sort and five uploads) for the same intervals, wall clock around the call, alternating with the device build in the same run;
 "device_build_ms" is the sort plus the index on the device, by events, and "device_build_wall_ms" the wall clock around the whole load less
-the load part."""
+the load part.  The nearest legs run behind the overlap in the same repeat, at k = 1 and k = 8 (ties 'all', no max_distance), every page written
+and none fetched: "nearest_k1" / "nearest_k8" hold n_pairs, n_unmatched, end_sort_passes and the end sort with its gather, the selection pass with its
+carry and the write passes (dhts_debug_ivl_ms 6 / 7 / 8) -- to be read beside overlap_count_ms and overlap_write_ms of the same run.  The right
+context is loaded anew in every repeat, so the k = 1 leg builds the end order and the k = 8 leg finds it there."""
 import argparse
 import ctypes as C
 import json
@@ -32,6 +35,7 @@ import duckhts_amd   # noqa: E402
 HBM_PEAK = 8.0e12
 SHAPES = ("tiling", "shuffled", "alternating", "right_span", "left_span")
 N_CHROMS = 6
+NEAREST_K = (1, 8)
 
 
 def make_rows(shape, n, seed):
@@ -83,6 +87,7 @@ def run(shape, n, repeats, device, bam):
     lctx, rctx = bed_ctx(bed_text(*left), device), bed_ctx(bed_text(*right), device)
     tid, beg, end = right[0].astype(np.int32), right[1].astype(np.int64), right[2].astype(np.int64)
     t = {k: [] for k in ("load", "sort", "index", "merge", "overlap_count", "overlap_write", "device_build", "device_build_wall", "host_build")}
+    near = {k: {"stats": None, "end_order": [], "select": [], "write": []} for k in NEAREST_K}
     passes = [[] for _ in range(duckhts_amd.IVL_SORT_MAX_PASSES)]
     st = pairs = runs = None
     try:
@@ -103,11 +108,21 @@ def run(shape, n, repeats, device, bam):
                 if b.status != 0:
                     break
             st, pairs = rctx.ivl_stats(), lctx.ivl_stats()["n_pairs"]
+            ms_overlap = (lctx.debug_ivl_ms(4), lctx.debug_ivl_ms(5))
+            for k in NEAREST_K:
+                lctx.ivl_nearest_open(rctx, k)
+                while True:
+                    lctx._chk(lctx.L.dhts_ivl_nearest_next(lctx.h, 0, 0x1ff, C.byref(b)))
+                    if b.status != 0:
+                        break
+                near[k]["stats"] = lctx.ivl_nearest_stats()
+                if rep:
+                    near[k]["end_order"].append(lctx.debug_ivl_ms(6)); near[k]["select"].append(lctx.debug_ivl_ms(7)); near[k]["write"].append(lctx.debug_ivl_ms(8))
             if rep == 0:
                 continue
             ms = [rctx.debug_ivl_ms(k) for k in range(3)]
             t["load"].append(ms[0]); t["sort"].append(ms[1]); t["index"].append(ms[2]); t["merge"].append(ms_merge)
-            t["overlap_count"].append(lctx.debug_ivl_ms(4)); t["overlap_write"].append(lctx.debug_ivl_ms(5))
+            t["overlap_count"].append(ms_overlap[0]); t["overlap_write"].append(ms_overlap[1])
             t["device_build"].append(ms[1] + ms[2]); t["device_build_wall"].append((w1 - w0) * 1e3 - ms[0]); t["host_build"].append((w2 - w1) * 1e3)
             for p in range(duckhts_amd.IVL_SORT_MAX_PASSES):
                 passes[p].append(rctx.debug_ivl_ms(16 + p))
@@ -119,6 +134,9 @@ def run(shape, n, repeats, device, bam):
     out = {"shape": shape, "rows": n, "sort_passes": st["sort_passes"], "n_name_runs": st["n_name_runs"], "n_runs": runs, "n_pairs": pairs}
     out.update({k + "_ms": spread(v) for k, v in t.items()})
     out["sort_pass_ms"] = {str(p): spread(passes[p]) for p in ran}
+    for k in NEAREST_K:
+        out["nearest_k%d" % k] = dict({f: near[k]["stats"][f] for f in ("n_pairs", "n_unmatched", "end_sort_passes")},
+                                      **{f + "_ms": spread(near[k][f]) for f in ("end_order", "select", "write")})
     out["sort_hbm_share"] = round(32.0 * st["n_rows"] * len(ran) / (pass_ms * 1e-3) / HBM_PEAK, 4) if pass_ms > 0 else None
     return out
 
